@@ -11,10 +11,17 @@ One timed step = draw augmentation parameters (host, reference RNG order) -> cut
 device -> forward (batch-statistics BN, dropout) -> custom_loss -> backward -> [all-reduce] ->
 fused Adam + l2 with the 1-cycle learning rate of that iteration.  Frames and labels are resident in
 HBM before the timed region starts.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the
+benchmark measures: the host enqueue cost into an idle GPU, the sustained leg, the per-family rooflines, the
+predict / 331x331 / other-backbone / bf16x3-alone legs and the CPU baseline.  `--dump-outputs DIR` writes
+what the last timed step computed as DIR/<name>.npy (the inputs are seeded: the same arguments give the same
+inputs, so two builds can be compared output for output).
 """
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -51,6 +58,32 @@ METRIC = "training images/sec on 512\u00d7384 fake-ESPI, Xception backbone, 1/2/
 
 
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "hbm_traffic_current.json")
+
+DUMP_LIMIT_BYTES = 64 << 20
+# elements of the flat weight and gradient buffers that --dump-outputs writes: the buffers hold 77 M fp32 values
+# each at the benchmark geometry (310 MB), beyond what the dump may take
+DUMP_PARAM_SAMPLE = 4 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as <outdir>/<name>.npy, float64 kept, anything else as float32."""
+    arrays = {k: np.ascontiguousarray(v if v.dtype == np.float64 else v.astype(np.float32)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+
+
+def train_outputs(eng):
+    """What a caller of Engine.train_step holds after the step: the loss vector it returns, the network's predictions
+    for the batch, and a fixed seeded sample of the updated weights and of the gradient they were updated with."""
+    import torch
+    idx = torch.randint(eng.n_theta, (min(DUMP_PARAM_SAMPLE, eng.n_theta),), generator=torch.Generator().manual_seed(0))
+    idx = idx.sort().values.to(eng.theta.device)
+    return {"loss_out": eng.loss_out.cpu().numpy(), "predictions": eng.out.cpu().numpy(),
+            "weights_sample": eng.theta[idx].cpu().numpy(), "weight_grads_sample": eng.grad[idx].cpu().numpy()}
 
 
 def kernel_source_hash():
@@ -473,12 +506,14 @@ def secondary(args):
         step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    out = {"metric": "%s images/sec, %s backbone (secondary measurement)" % (args.mode, args.backbone),
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, train_outputs(eng) if args.mode == "train" else {"predictions": eng.out.cpu().numpy()})
+    out = {"metric":"%s images/sec, %s backbone (secondary measurement)" % (args.mode, args.backbone),
            "value": round(b * args.steps / dt, 2), "unit": "images/sec", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3), "dtype": DTYPE if args.backbone != "InceptionResNetV2" else "f32",
            "data": "synthetic (uniform noise)",
            "config": {"workload": "%s, %s, %dx%d frames, batch %d" % (args.mode, args.backbone, w, h, b)}}
-    if not args.no_kernel_timers:       # the GEMM family of this configuration against the fp32 MFMA peak (HIP events)
+    if args.full and not args.no_kernel_timers:     # the GEMM family of this configuration against the fp32 MFMA peak (HIP events)
         tim = time_families(eng, step, args.steps, torch.cuda.synchronize)
         if "gemm" in tim.totals():
             out["roofline"] = dict(gemm_roofline_block(tim, args.steps),
@@ -487,10 +522,11 @@ def secondary(args):
     print(json.dumps(out))
 
 
-def predict_measure(X_pool, dev, steps, warmup, host_frames=1024):
+def predict_measure(X_pool, dev, steps, warmup, host_frames=1024, full=True, dump=None):
     """BASELINE configs[4] on frames already resident in HBM (X_pool [n,384,512,1] on `dev`, n a multiple of 128):
-    hipGraph-captured forward of batch 128 (Engine.predict_step), the eager-launch rate, the family rooflines from
-    HIP events, and Model.predict over HOST frames (pinned ring + copy stream: PCIe-inclusive, never `value`)."""
+    hipGraph-captured forward of batch 128 (Engine.predict_step); full=True adds the eager-launch rate, the family
+    rooflines from HIP events, and Model.predict over HOST frames (pinned ring + copy stream: PCIe-inclusive, never
+    `value`).  dump: directory for the predictions of the last timed forward (--dump-outputs)."""
     import torch
     from spnet_amd.engine import Engine, KernelTimer
     from spnet_amd.models import Model
@@ -516,6 +552,12 @@ def predict_measure(X_pool, dev, steps, warmup, host_frames=1024):
         return time.perf_counter() - t0
 
     dt = timed(steps, True)
+    if dump:
+        dump_outputs(dump, {"predictions": eng.out.cpu().numpy()})
+    timed_out = {"frames_per_sec": round(PB * steps / dt, 1), "ms_per_step": round(1e3 * dt / steps, 3), "steps": steps,
+                 "batch": PB, "pool_frames": pool}
+    if not full:
+        return timed_out
     dt_eager = timed(steps, False)
     tim = time_families(eng, lambda: step(False), steps, torch.cuda.synchronize)
     tot = tim.totals()
@@ -543,9 +585,8 @@ def predict_measure(X_pool, dev, steps, warmup, host_frames=1024):
     del m
     torch.cuda.empty_cache()
     note = "HIP events around every launch of the family during %d eager forwards after the timed region" % n_prof
-    return {
-        "frames_per_sec": round(PB * steps / dt, 1), "ms_per_step": round(1e3 * dt / steps, 3), "steps": steps,
-        "batch": PB, "pool_frames": pool, "eager_frames_per_sec": round(PB * steps / dt_eager, 1),
+    return dict(timed_out, **{
+        "eager_frames_per_sec": round(PB * steps / dt_eager, 1),
         "host_streamed_frames_per_sec": round(nh / dt_host, 1),
         "host_streamed_u8_frames_per_sec": host_u8,
         "host_frames_note": "Model.predict over %d host frames: pageable -> pinned ring -> HBM on a copy stream, "
@@ -559,7 +600,7 @@ def predict_measure(X_pool, dev, steps, warmup, host_frames=1024):
                                "algorithmic_bytes_per_step": round(d_bytes / n_prof),
                                "bytes_per_step_of_layers_fused_into_gemm_epilogues": round(max(DW_FWD_BYTES_PER_IMAGE * PB - d_bytes / n_prof, 0.0)),
                                "launches_per_step": d_n / n_prof, "ms_per_step": round(d_ms / n_prof, 3), "measured": note},
-    }
+    })
 
 
 def predict_bench(args):
@@ -575,8 +616,8 @@ def predict_bench(args):
     dev = parallel.local_device()
     torch.cuda.set_device(dev)
     X_pool, _ = F.generate_device(pool, seed=11, device=str(dev))
-    r = predict_measure(X_pool, dev, args.steps, args.warmup)
-    print(json.dumps({
+    r = predict_measure(X_pool, dev, args.steps, args.warmup, full=args.full, dump=args.dump_outputs)
+    out = {
         "metric": "inference frames/sec, predict_spnet.py path (model.predict), Xception, batch 128 over 512x384 frames "
                   "(BASELINE configs[4]; secondary to the training metric)",
         "value": r["frames_per_sec"], "unit": "frames/sec", "n_gpus": 1, "steps": args.steps,
@@ -584,12 +625,15 @@ def predict_bench(args):
         "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
         "config": {"workload": "configs[4]: inference-only forward, Xception, 512x384 fake-ESPI frames, batch 128, "
                                "hipGraph-captured plan, frames resident in HBM", "batch": PB, "frame_hw": [H, W],
-                   "pool_frames": pool, "eager_frames_per_sec": r["eager_frames_per_sec"],
-                   "host_frames_streamed_frames_per_sec": r["host_streamed_frames_per_sec"],
-                   "host_frames_u8_streamed_frames_per_sec": r["host_streamed_u8_frames_per_sec"],
-                   "host_frames_note": r["host_frames_note"]},
-        "roofline": r["roofline"], "roofline_secondary": r["roofline_secondary"],
-    }), flush=True)
+                   "pool_frames": pool},
+    }
+    if args.full:
+        out["config"].update({"eager_frames_per_sec": r["eager_frames_per_sec"],
+                              "host_frames_streamed_frames_per_sec": r["host_streamed_frames_per_sec"],
+                              "host_frames_u8_streamed_frames_per_sec": r["host_streamed_u8_frames_per_sec"],
+                              "host_frames_note": r["host_frames_note"]})
+        out.update(roofline=r["roofline"], roofline_secondary=r["roofline_secondary"])
+    print(json.dumps(out), flush=True)
 
 
 def layout_331_measure(dev, steps=20, warmup=3):
@@ -867,15 +911,22 @@ def main():
                          "the 256 MiB Infinity Cache)")
     ap.add_argument("--pool-source", choices=["device", "host"], default="device",
                     help="device: frames rasterised in HBM by csrc/espi.hip (SURVEY 8f-2); host: the PIL generator")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure everything else the line can carry: host enqueue cost, "
+                         "sustained leg, per-family rooflines, the secondary legs and the CPU baseline (each of them "
+                         "can be left out again with the options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--sustained-seconds", type=float, default=6.0,
-                    help="after the timed region keep stepping for this long and report the rate separately "
+                    help="--full: after the timed region keep stepping for this long and report the rate separately "
                          "(clocks under sustained load); 0 = skip")
     ap.add_argument("--cpu-baseline-steps", type=int, default=5)
     ap.add_argument("--cpu-baseline-batch", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timers", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-timers", action="store_true", help="--full without the per-family rooflines")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the configs[4] inference leg and the 331x331 layout leg appended to the N=1 line")
+                    help="--full without the configs[4] inference leg, the 331x331 layout leg and the other legs "
+                         "appended to the N=1 line")
     ap.add_argument("--mode", choices=["train", "predict"], default="train",
                     help="predict: inference-only forward (BASELINE configs[4]); secondary, not the headline metric")
     ap.add_argument("--height", type=int, default=H)
@@ -951,7 +1002,7 @@ def run(args):
     t_gen = time.perf_counter()
     # host frames: the whole pool, the CPU baseline's sample, or none at all (generate() forks only while no HIP
     # context can exist in this process -- not under a profiler's preloaded runtime, fake_espi.gpu_may_be_live)
-    need_cpu = world == 1 and not args.no_cpu_baseline
+    need_cpu = args.full and world == 1 and not args.no_cpu_baseline
     n_host = args.pool if args.pool_source == "host" else (64 if need_cpu else 0)
     X_u8 = Y_host = None
     if n_host:
@@ -969,6 +1020,7 @@ def run(args):
         X_pool = torch.from_numpy(F.to_network_input(X_u8)).to(dev)
         Y_pool = torch.from_numpy(Y_host).to(dev)
     np.random.seed(1 + rank)
+    random.seed(1 + rank)           # (the blur gate's kernel-size draw: the same inputs in every run of a command)
 
     eng = Engine(H, W, BATCH, device=str(dev), seed=0, rank=rank)
     aug = DeviceAugmenter(X_pool)
@@ -1028,6 +1080,8 @@ def run(args):
         sys.stderr.write("trace: wall %.2f ms; GPU ms per step: %s\n" % (1e3 * dt, " ".join("%.2f" % evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))))
         sys.stderr.write("trace: host ms per step: %s\n" % " ".join("%.1f" % v for v in hts))
     loss = float(out[5])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(eng))
     # N > 1: what an 8-GPU shortfall would be made of -- the part of the gradient all-reduce the main stream WAITS for
     # between the end of backward and the optimizer (everything else ran underneath backward), the bytes, the bucket plan
     comm = None
@@ -1047,14 +1101,16 @@ def run(args):
 
     # Host cost of enqueueing ONE step into an idle GPU (the figure above is taken under queue back-pressure: the
     # host runs ahead until the launch queue is full and then waits for the GPU, so it reads ~ the GPU step time).
-    t_idle = []
-    for _ in range(3):
+    t_host_idle = None
+    if args.full:
+        t_idle = []
+        for _ in range(3):
+            fence()
+            t1 = time.perf_counter()
+            step()
+            t_idle.append(time.perf_counter() - t1)
         fence()
-        t1 = time.perf_counter()
-        step()
-        t_idle.append(time.perf_counter() - t1)
-    fence()
-    t_host_idle = min(t_idle)
+        t_host_idle = min(t_idle)
 
     n_ranks_seen, backend = 1, None
     if world > 1:                # every rank must agree on the timed region before anything is derived from it
@@ -1070,7 +1126,7 @@ def run(args):
     # step COUNT is fixed from the timed region's rate, identically on every rank (a time-based exit would let ranks
     # leave the loop after different numbers of collectives).
     sustained = None
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         n_s = max(20, int(args.sustained_seconds / (dt / args.steps) / 20 + 1) * 20)
         fence()
         t1 = time.perf_counter()
@@ -1088,7 +1144,7 @@ def run(args):
     # Roofline leg: the same K steps replayed with every kernel on ONE stream (no weight-gradient overlap),
     # so that a kernel's HIP-event duration is its own and not that of two kernels sharing the chip.
     timer = entry_times = None
-    if not args.no_kernel_timers:
+    if args.full and not args.no_kernel_timers:
         eng.wgrad_stream = None
         step()
         fence()
@@ -1112,9 +1168,10 @@ def run(args):
                        "devices_visible": torch.cuda.device_count(), "final_loss": round(loss, 6),
                        "wgrad_overlap": not args.no_overlap, "arithmetic": ARITHMETIC,
                        "host_enqueue_ms_per_step_backpressured": round(1e3 * t_host / args.steps, 3),
-                       "host_enqueue_ms_per_step_gpu_idle": round(1e3 * t_host_idle, 3),
                        "pool_source": args.pool_source, "pool_generation_s": round(t_gen, 1)},
         }
+        if t_host_idle is not None:
+            result["config"]["host_enqueue_ms_per_step_gpu_idle"] = round(1e3 * t_host_idle, 3)
         if comm is not None:
             result["config"]["comm"] = comm
         if sustained is not None:
@@ -1196,7 +1253,7 @@ def run(args):
                 result["roofline_other"] = other_family_rooflines(entry_times, args.steps)
                 result["roofline_other"]["measured"] = ("HIP events around every launching entry point of the C ABI (spnet_amd._lib.set_tracer) "
                                                         "during %d further steps on one stream; bytes: bench.algorithmic_bytes" % args.steps)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             # the secondary configurations, in the same driver-witnessed line (N = 1 only; ~10 s): BASELINE configs[4]
             # (predict_spnet.py:84-87's FPS) on the resident pool, and the reference's own 331x331 layout
             del eng, aug
@@ -1208,7 +1265,7 @@ def run(args):
             result["roofline_alt"] = bf16x3_alt_measure(dev)
             result["roofline_alt"]["train_step"] = exact_chain_step_measure(dev, X_pool)
             eng = aug = None
-        if world == 1 and not args.no_cpu_baseline:
+        if need_cpu:
             del eng, aug, X_pool
             torch.cuda.empty_cache()
             result["cpu_baseline"] = cpu_baseline(X_u8, Y_host, args.cpu_baseline_steps, args.cpu_baseline_batch)

@@ -103,7 +103,7 @@ def test_bench_self_launched_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(PYTHONPATH=ROOT, SPNET_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--pool", "128", "--sustained-seconds", "0"],
+                        "--pool", "128", "--sustained-seconds", "0", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -121,11 +121,12 @@ def test_bench_self_launched_two_ranks_on_one_gpu():
     assert abs(sum(comm["buckets"]["mb"]) + comm["buckets"]["tail_at_end_of_backward_mb"] - 309739008 / 2 ** 20) < 1.0
 
 
-def test_bench_default_line_carries_every_block():
-    """The driver's N = 1 command with short step counts: one JSON line with the roofline of the dominant family, the
-    secondary family by sub-family (and, inside `roofline`, by arithmetic), the predict / 331 x 331 / other-backbone legs,
-    `roofline_alt` (the bf16x3 kernel isolated, and the all-fp32-chain train step beside the product's) and the CPU baseline
-    (one short oracle step here) -- every leg of the default run executes, none is skipped by a flag."""
+def test_bench_full_line_carries_every_block():
+    """The driver's N = 1 command with --full and short step counts: one JSON line with the roofline of the dominant
+    family, the secondary family by sub-family (and, inside `roofline`, by arithmetic), the predict / 331 x 331 /
+    other-backbone legs, `roofline_alt` (the bf16x3 kernel isolated, and the all-fp32-chain train step beside the
+    product's) and the CPU baseline (one short oracle step here) -- every leg of the full run executes, none is skipped
+    by a flag."""
     import json
     import torch
     if not torch.cuda.is_available():
@@ -133,7 +134,7 @@ def test_bench_default_line_carries_every_block():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--pool", "256",
-                        "--sustained-seconds", "0", "--cpu-baseline-steps", "1", "--cpu-baseline-batch", "2"],
+                        "--sustained-seconds", "0", "--cpu-baseline-steps", "1", "--cpu-baseline-batch", "2", "--full"],
                        env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -174,3 +175,35 @@ def test_bench_default_line_carries_every_block():
     assert alt["max_rel_err_vs_f64"] < 5e-7 and alt["avg_launch_us"] > 0 and 0 < alt["frac"] < 1
     assert alt["bit_identical_to_fp32_a_kernel"] and alt["wgrad_from_planes_us"] > 0
     assert out["cpu_baseline"]["kind"] in ("port", "reference") and out["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """The driver's plain N = 1 command: only the timed steps -- the headline fields, none of the --full legs -- and
+    --dump-outputs writes what the last timed step computed: the loss vector, the batch's predictions and seeded samples
+    of the updated weights and their gradient, float32, within 64 MB."""
+    import json
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                        "--pool", "256", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 4 and out["warmup"] == 2 and out["unit"] == "images/sec" and out["higher_is_better"] is True
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 32 * 1e3 / out["ms_per_step"]) < 0.01 * out["value"]
+    assert "bf16x3" in out["dtype"]
+    for key in ("roofline", "roofline_secondary", "roofline_other", "roofline_alt", "cpu_baseline", "predict", "layout_331",
+                "kernel_families", "irv2", "mobilenet", "sustained"):
+        assert key not in out, key
+    arrays = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(tmp_path)}
+    assert sorted(arrays) == ["loss_out", "predictions", "weight_grads_sample", "weights_sample"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["predictions"].shape == (32, 576) and arrays["weights_sample"].shape == arrays["weight_grads_sample"].shape
+    assert abs(float(arrays["loss_out"][5]) - out["config"]["final_loss"]) <= 1e-5 * max(1.0, abs(out["config"]["final_loss"]))
+    assert np.count_nonzero(arrays["weight_grads_sample"]) > arrays["weight_grads_sample"].size // 2

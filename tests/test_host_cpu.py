@@ -375,6 +375,7 @@ def test_bench_self_launches_its_ranks_on_gloo():
     returns the child's exit code (--launch-check: rendezvous + one all-reduce, no kernels, so it runs here)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["SPNET_DIST_BACKEND"] = "gloo"      # (also where a GPU is visible: RCCL refuses two ranks on one device)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launch-check"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -396,6 +397,7 @@ def test_bench_launches_eight_ranks_and_reports_a_failing_rank():
     named rank raise after the rendezvous), not only with torchrun's summary."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["SPNET_DIST_BACKEND"] = "gloo"      # (also where a GPU is visible: RCCL refuses two ranks on one device)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--launch-check"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -420,25 +422,37 @@ def test_stream_accessor_resolves_with_a_public_fallback(monkeypatch):
     assert kind == "public" and fn is _lib._public_stream
 
 
-def test_fork_is_refused_under_a_preloaded_profiler(monkeypatch):
+_FORK_CHECK = r'''
+import os, sys, numpy as np
+sys.path.insert(0, sys.argv[1])
+from spnet_amd import fake_espi as F
+for k in list(os.environ):
+    if k.startswith(("ROCPROF", "ROCP_")):
+        del os.environ[k]
+os.environ.pop("LD_PRELOAD", None)
+os.environ.pop("HSA_TOOLS_LIB", None)
+assert not F.gpu_may_be_live()
+os.environ["LD_PRELOAD"] = "/opt/rocm/lib/rocprofiler-sdk/librocprofiler-sdk-tool.so"
+assert F.gpu_may_be_live()
+del os.environ["LD_PRELOAD"]
+os.environ["ROCPROF_OUTPUT_PATH"] = "/tmp/x"
+assert F.gpu_may_be_live()
+X, lab = F.generate(16, seed=3, workers=4)        # serial under the "profiler"; same frames as the forked path
+del os.environ["ROCPROF_OUTPUT_PATH"]
+X2, lab2 = F.generate(16, seed=3, workers=4)
+assert np.array_equal(X, X2) and lab == lab2
+print("fork check ok")
+'''
+
+
+def test_fork_is_refused_under_a_preloaded_profiler(tmp_path):
     """rocprofv3 initialises the HIP runtime before Python starts (torch.cuda.is_initialized() stays False): the
-    frame generator and the PNG loader must not fork then."""
-    from spnet_amd import fake_espi as F
-    for k in list(os.environ):
-        if k.startswith(("ROCPROF", "ROCP_")):
-            monkeypatch.delenv(k)
-    monkeypatch.delenv("LD_PRELOAD", raising=False)
-    monkeypatch.delenv("HSA_TOOLS_LIB", raising=False)
-    assert not F.gpu_may_be_live()
-    monkeypatch.setenv("LD_PRELOAD", "/opt/rocm/lib/rocprofiler-sdk/librocprofiler-sdk-tool.so")
-    assert F.gpu_may_be_live()
-    monkeypatch.delenv("LD_PRELOAD")
-    monkeypatch.setenv("ROCPROF_OUTPUT_PATH", "/tmp/x")
-    assert F.gpu_may_be_live()
-    X, lab = F.generate(16, seed=3, workers=4)        # serial under the "profiler"; same frames as the forked path
-    monkeypatch.delenv("ROCPROF_OUTPUT_PATH")
-    X2, lab2 = F.generate(16, seed=3, workers=4)
-    assert np.array_equal(X, X2) and lab == lab2
+    frame generator and the PNG loader must not fork then.  Checked in a fresh interpreter: when the suite runs on a
+    GPU machine, earlier tests have initialised torch.cuda in this one, and gpu_may_be_live() is rightly True here."""
+    script = tmp_path / "fork_check.py"
+    script.write_text(_FORK_CHECK)
+    r = subprocess.run([sys.executable, str(script), ROOT], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "fork check ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 def test_cpu_share_for_the_baseline():
@@ -448,6 +462,21 @@ def test_cpu_share_for_the_baseline():
     assert 1 <= n <= share["affinity_cpus"] and n <= 32
     if share["cgroup_quota_cpus"]:
         assert n <= int(share["cgroup_quota_cpus"] + 0.5)
+
+
+def test_bench_dump_outputs_dtypes_and_limit(tmp_path):
+    """--dump-outputs writes <name>.npy as float32 (float64 stays float64) and refuses more than 64 MB in all."""
+    sys.path.insert(0, ROOT)
+    import bench
+    bench.dump_outputs(str(tmp_path / "d"), {"a": np.arange(6, dtype=np.int32).reshape(2, 3), "b": np.ones(4),
+                                             "c": np.full(3, 0.5, np.float16)})
+    got = {f: np.load(str(tmp_path / "d" / f)) for f in sorted(os.listdir(tmp_path / "d"))}
+    assert sorted(got) == ["a.npy", "b.npy", "c.npy"]
+    assert got["a.npy"].dtype == np.float32 and got["a.npy"].tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert got["b.npy"].dtype == np.float64 and got["c.npy"].dtype == np.float32
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "e"), {"x": np.zeros(16 << 20, np.float32), "y": np.zeros(1, np.float32)})
+    assert not os.path.exists(tmp_path / "e")
 
 
 def test_irv2_sibling_groups_and_parameter_packs():

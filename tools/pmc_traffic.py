@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Fold two rocprofv3 PMC passes (--pmc FETCH_SIZE and --pmc WRITE_SIZE, each with --kernel-trace) over
-`bench.py --steps K --warmup W --no-cpu-baseline --no-kernel-timers` into profiles/<tag>_hbm_traffic.json:
+`bench.py --steps K --warmup W --full --no-cpu-baseline --no-kernel-timers` into profiles/<tag>_hbm_traffic.json:
 HBM bytes per launch for the kernel families bench.py reports.
 
 Corrections (MI355X_MICROARCH.md, 'HBM'): counters are in KB; on gfx950 FETCH_SIZE tallies 128-byte requests as

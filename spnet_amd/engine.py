@@ -477,6 +477,154 @@ def _glorot_fans(name, shape):
     return shape[0], shape[1]
 
 
+class WeightSet:
+    """The weights of one model, shared by every launch plan (Engine) over them -- the training plan, the inference plans, a
+    fit() at another batch size: the flat buffers and their layout, the optimizer state, and the copies of theta that every
+    plan reads (W^T of the blended pointwise kernels, the bf16x3 planes).
+
+    theta_ver counts the changes of theta (init, load, optimizer step), stats_ver those of stats (init, load, training
+    forward).  Every copy derived from them, here or in a plan (Engine.refresh), records the version(s) it was computed at
+    and is recomputed when they moved."""
+
+    def __init__(self, H, W, n_out=576, backbone="Xception", device="cuda:0", seed=0, rank=0):
+        lay = param_layout(H, W, n_out, backbone)
+        self.p_off, self.s_off, self.l2_n, self.rest_lo = lay["p_off"], lay["s_off"], lay["l2_n"], lay["rest_lo"]
+        self.n_theta, self.spec_order = lay["n_theta"], lay["spec_order"]
+        self.dev = torch.device(device)
+        self.theta = torch.zeros(self.n_theta, device=self.dev, dtype=torch.float32)
+        self.stats = torch.zeros(lay["n_stats"], device=self.dev, dtype=torch.float32)
+        self.grad = self.m = self.v = None          # alloc_train_state()
+        # Optimizer iteration count and dropout seed: every plan advances the same ones, so a second fit() with another
+        # batch size continues Adam's bias correction and the dropout seed sequence instead of restarting them.
+        self.t = 0
+        self.drop_seed = 12345 + 7919 * int(rank)
+        self.theta_ver = self.stats_ver = 0
+        self.wT = {}            # pointwise kernel name -> W^T ([cout][cin])
+        self.planes = {}        # pointwise kernel name -> [forward planes, data-gradient planes] (csrc/x3t.h)
+        # (job tables: None when the set of buffers changed; *_at: the theta_ver the copies were made at)
+        self._wT_jobs = self._wT_at = self._planes_jobs = self._planes_at = None
+        self.init_weights(seed)
+
+    def alloc_train_state(self):
+        """grad and the Adam moments m, v: allocated once, by the first training plan over these weights."""
+        if self.grad is None:
+            self.grad, self.m, self.v = (torch.zeros(self.n_theta, device=self.dev, dtype=torch.float32) for _ in range(3))
+
+    def init_weights(self, seed=0):
+        """Keras defaults: glorot_uniform kernels, zeros bias/beta, ones gamma, moving stats 0/1."""
+        self.theta_ver += 1
+        self.stats_ver += 1
+        g = torch.Generator().manual_seed(seed)
+        host = torch.zeros(self.n_theta, dtype=torch.float32)
+        for name, (off, n, shape) in self.p_off.items():
+            if name.endswith("/gamma"):
+                host[off:off + n] = 1.0
+            elif name.endswith("kernel"):
+                fi, fo = _glorot_fans(name, shape)
+                lim = math.sqrt(6.0 / (fi + fo))
+                host[off:off + n] = ((torch.rand(n, generator=g, dtype=torch.float64) * 2 - 1) * lim).float()
+        self.theta.copy_(host)
+        hs = torch.zeros(self.stats.numel(), dtype=torch.float32)
+        for name, (off, n, _) in self.s_off.items():
+            if name.endswith("moving_variance"):
+                hs[off:off + n] = 1.0
+        self.stats.copy_(hs)
+        if self.m is not None:
+            self.m.zero_()
+            self.v.zero_()
+        self.t = 0
+
+    def state_dict(self):
+        """name -> CPU tensor in Keras layout (trainable + moving statistics)."""
+        out = OrderedDict()
+        for name in self.spec_order:
+            if name in self.p_off:
+                off, n, shape = self.p_off[name]
+                out[name] = self.theta[off:off + n].reshape(shape).cpu().clone()
+            else:
+                off, n, shape = self.s_off[name]
+                out[name] = self.stats[off:off + n].reshape(shape).cpu().clone()
+        return out
+
+    def load_state_dict(self, sd):
+        self.theta_ver += 1
+        self.stats_ver += 1
+        for name in self.spec_order:
+            t = torch.as_tensor(np.asarray(sd[name]), dtype=torch.float32).reshape(-1)
+            if name in self.p_off:
+                off, n, _ = self.p_off[name]
+                dst = self.theta
+            else:
+                off, n, _ = self.s_off[name]
+                dst = self.stats
+            if t.numel() != n:
+                raise ValueError("shape mismatch for %s: got %d values, need %d" % (name, t.numel(), n))
+            dst[off:off + n].copy_(t.to(self.dev))
+
+    def grad_dict(self):
+        return OrderedDict((name, self.grad[off:off + n].reshape(shape).cpu().clone())
+                           for name, (off, n, shape) in self.p_off.items())
+
+    def transposed(self, wname):
+        """W^T buffer ([cout][cin]) of a pointwise kernel; kept current by refresh_transposes()."""
+        if wname not in self.wT:
+            self.wT[wname] = torch.empty(self.p_off[wname][1], device=self.dev, dtype=torch.float32)
+            self._wT_jobs = self._wT_at = None
+        return self.wT[wname]
+
+    def refresh_transposes(self):
+        """One batched launch: W^T of the pointwise kernels whose data-gradient GEMM blends the BatchNorm backward
+        into its A operand (Pointwise.blend) -- that kernel exists in the forward operand form only.  (Round 2 also
+        measured ALL data-gradient GEMMs on transposed copies: the forward form is no faster than the K-major-B
+        form, 61.5 vs 69.2 us on 6144x728x728, so the other layers read W in place.)"""
+        if self._wT_at == self.theta_ver:
+            return
+        if self.wT:
+            if self._wT_jobs is None:
+                flat, mr, mc = [], 1, 1
+                for name, dst in self.wT.items():
+                    off, n, shape = self.p_off[name]
+                    R, C = int(shape[-2]), int(shape[-1])          # [cin][cout] (1x1 HWIO kernels: trailing two dims)
+                    flat += [self.theta.data_ptr() + 4 * off, dst.data_ptr(), R, C]
+                    mr, mc = max(mr, R), max(mc, C)
+                self._wT_jobs = (torch.tensor(flat, dtype=torch.int64, device=self.dev), len(self.wT), mr, mc)
+            table, nj, mr, mc = self._wT_jobs
+            L.spnet_transpose_batched(table.data_ptr(), nj, mr, mc, _stream())
+        self._wT_at = self.theta_ver
+
+    def need_planes(self, wname, fwd, dgrad):
+        """bf16x3 operand planes of a pointwise kernel, allocated once per weight set: a later plan finds them, and adds
+        the data-gradient planes an inference plan had no use for."""
+        ent = self.planes.setdefault(wname, [None, None])
+        cin, cout = (int(v) for v in self.p_off[wname][2][-2:])
+        for i, (want, R, K) in enumerate(((fwd, cout, cin), (dgrad, cin, cout))):
+            if want and ent[i] is None:
+                ent[i] = torch.zeros(3 * int(L.spnet_bf16x3_plane_elems(R, K)), dtype=torch.int16, device=self.dev)
+                self._planes_jobs = self._planes_at = None
+
+    def refresh_planes(self):
+        """The weights split into their bf16 planes, both operand forms, ONE batched launch."""
+        if self._planes_at == self.theta_ver:
+            return
+        if self.planes:
+            if self._planes_jobs is None:
+                flat, mx = [], 1
+                for wname, (pf, pd) in self.planes.items():
+                    off, n, shape = self.p_off[wname]
+                    cin, cout = int(shape[-2]), int(shape[-1])
+                    w = self.theta.data_ptr() + 4 * off
+                    if pf is not None:      # forward: B element (n = cout, k = cin) = W[k][n]
+                        flat += [w, pf.data_ptr(), cin, cout, 1, cout]
+                        mx = max(mx, pf.numel() // 3)
+                    if pd is not None:      # data gradient dX = dY W^T: (n = cin, k = cout) = W[n][k]
+                        flat += [w, pd.data_ptr(), cout, cin, cout, 1]
+                        mx = max(mx, pd.numel() // 3)
+                self._planes_jobs = (torch.tensor(flat, dtype=torch.int64, device=self.dev), len(flat) // 6, mx)
+            table, nj, mx = self._planes_jobs
+            L.spnet_split_bf16x3_batched(table.data_ptr(), nj, mx, _stream())
+        self._planes_at = self.theta_ver
+
+
 class Engine:
     def __init__(self, H, W, batch, n_out=576, device="cuda:0", loss_type="same", seed=0,
                  train=True, adam_eps=1e-7, share_from=None, rank=0, sigmoid_cols=None, backbone="Xception",
@@ -518,58 +666,37 @@ class Engine:
         self.loss_type = loss_type
         self.train_capable = bool(train)
         self.adam_eps = adam_eps
-        # Optimizer iteration count and dropout seed live beside theta/m/v: every plan over one weight set
-        # (other batch sizes, the inference plans) advances the SAME counters, so a second fit() with another
-        # batch size continues Adam's bias correction and the dropout seed sequence instead of restarting them.
-        self._opt = share_from._opt if share_from is not None else {"t": 0, "drop_seed": 12345 + 7919 * int(rank)}
         self.prof = None                # KernelTimer or None
-        self._pw_layers = []            # every Pointwise of this plan (their bf16x3 weight planes: _build_planes)
+        self._pw_layers = []            # every Pointwise of this plan (their bf16x3 weight planes: WeightSet.need_planes)
+        self._bns = []                  # every BN of this plan (their inference coefficients: refresh)
+        self._irv2 = None               # the IRv2Backbone node, if any (its gathered group operands: refresh)
         self.deferred_wgrads = []       # (x, dy, gw, cin, cout, M) of layers whose dW waits for the batched launch
         self.dw_reduce_jobs = []        # (partials, grad, rows, 9*C) of every depthwise layer
         self._dw_reduce_table = None
         self._wgrad_table = None
         self._first_middle = None
-        # The three run-time switches of the engine (DESIGN.md section 2 lists them with the tests that run the non-default
+        # The two run-time switches of the engine (DESIGN.md section 2 lists them with the tests that run the non-default
         # branch): SPNET_OVERLAP_WGRAD=0 -- weight gradients on the main stream instead of a side stream joined before
-        # Adam; SPNET_TRAIN_GRAPH=1 -- the single-GPU train step as a hipGraph; SPNET_GEMM_TILES=0 (_load_tile_table) --
-        # the library's own tile choice instead of the in-step autotuned table.
+        # Adam; SPNET_GEMM_TILES=0 (_load_tile_table) -- the library's own tile choice instead of the in-step autotuned table.
         self.overlap_wgrad = os.environ.get("SPNET_OVERLAP_WGRAD", "1") != "0"
-        # Optional: capture the single-GPU train step as a hipGraph after one eager step.  Off by default:
-        # measured on MI355X / ROCm 7.2 the replay of this ~400-node two-stream graph takes 13.8 ms against
-        # 13.4 ms for the eager launches (single stream: 13.5 either way) -- the host enqueues a step in
-        # 4.3 ms and runs ahead of the GPU, so launch overhead is not what limits the step.
-        self.use_graph = os.environ.get("SPNET_TRAIN_GRAPH", "0") == "1"
         torch.cuda.set_device(self.dev)
-        # Inference coefficients (scale|shift from the moving statistics, one tiny kernel per BatchNorm) are
-        # recomputed only when the weights or statistics changed since this plan last did: [version] is shared
-        # by all plans over one weight set and bumped by every training forward / optimizer step / load.
-        self._wver = share_from._wver if share_from is not None else [0]
-        # W^T of every pointwise kernel (name -> tensor), shared by all plans; [_tver] counts changes of theta,
-        # [_wT_ver] is the value of _tver the transposes were last refreshed at.
-        self._wT = share_from._wT if share_from is not None else {}
-        self._tver = share_from._tver if share_from is not None else [0]
-        self._wT_ver = share_from._wT_ver if share_from is not None else [-1]
-        self._wT_jobs = None
-        # bf16x3 operand planes of the pointwise kernels (name -> (forward planes, data-gradient planes)), shared by all
-        # plans over one weight set; [_planes_ver] = the value of _tver they were last split at
-        self._planes = share_from._planes if share_from is not None else {}
-        self._planes_ver = share_from._planes_ver if share_from is not None else [-1]
-        self._planes_gen = share_from._planes_gen if share_from is not None else [0]      # bumped by every allocation
-        self._planes_jobs = None
         self._igraph = None             # captured inference forward (predict_step)
-        self._coeff_ver = -1
-        self._infer_fresh = True
-        if share_from is not None:      # second plan (other batch size / inference) over the SAME weights
-            for a in ("p_off", "s_off", "l2_n", "rest_lo", "n_theta", "theta", "stats", "spec_order"):
-                setattr(self, a, getattr(share_from, a))
-            if self.train_capable:
-                for a in ("grad", "m", "v"):
-                    setattr(self, a, getattr(share_from, a))
+        # (theta_ver, stats_ver) the BatchNorm inference coefficients of this plan were computed at (None: never, or a
+        # training forward has overwritten them with batch statistics since)
+        self._coeffs_at = None
+        if share_from is not None:      # another plan (other batch size / inference) over the SAME weights
+            self.weights = w = share_from.weights
         else:
-            self._build_params(seed)
+            self.weights = w = WeightSet(self.H, self.W, self.n_out, backbone, device, seed, rank)
+        if self.train_capable:
+            w.alloc_train_state()
+        self.p_off, self.s_off, self.l2_n, self.rest_lo = w.p_off, w.s_off, w.l2_n, w.rest_lo
+        self.n_theta, self.theta, self.stats = w.n_theta, w.theta, w.stats
         self.update_mask = None         # optional flat 0/1 tensor: frozen parameters are skipped by Adam
         self._build_graph()
-        self._build_planes()
+        for pw in self._pw_layers:
+            if pw.x3_fwd or pw.x3_dgrad:
+                w.need_planes(pw.wname, pw.x3_fwd, pw.x3_dgrad)
 
     @property
     def pointwise(self):
@@ -582,59 +709,39 @@ class Engine:
         """zeroed bf16x3 plane set of an [R][K] matrix (csrc/x3t.h): the pad rows / columns are never written"""
         return torch.zeros(3 * int(L.spnet_bf16x3_plane_elems(R, K)), dtype=torch.int16, device=self.dev)
 
+    # ------------------------------------------------------------------ parameters (WeightSet)
+    grad = property(lambda self: self.weights.grad)
+    m = property(lambda self: self.weights.m)
+    v = property(lambda self: self.weights.v)
+
     @property
     def t(self):
         """optimizer iterations done (shared by all plans over this weight set)"""
-        return self._opt["t"]
+        return self.weights.t
 
     @t.setter
     def t(self, v):
-        self._opt["t"] = int(v)
+        self.weights.t = int(v)
 
     @property
     def drop_seed(self):
-        return self._opt["drop_seed"]
+        return self.weights.drop_seed
 
     @drop_seed.setter
     def drop_seed(self, v):
-        self._opt["drop_seed"] = int(v) & 0xFFFFFFFF
-
-    # ------------------------------------------------------------------ parameters
-    def _build_params(self, seed):
-        lay = param_layout(self.H, self.W, self.n_out, self.backbone)
-        for k in ("p_off", "s_off", "l2_n", "rest_lo", "n_theta", "spec_order"):
-            setattr(self, k, lay[k])
-        s_off = lay["n_stats"]
-        z = lambda n: torch.zeros(n, device=self.dev, dtype=torch.float32)
-        self.theta = z(self.n_theta)
-        self.stats = z(s_off)
-        if self.train_capable:
-            self.grad, self.m, self.v = z(self.n_theta), z(self.n_theta), z(self.n_theta)
-        self.init_weights(seed)
+        self.weights.drop_seed = int(v) & 0xFFFFFFFF
 
     def init_weights(self, seed=0):
-        """Keras defaults: glorot_uniform kernels, zeros bias/beta, ones gamma, moving stats 0/1."""
-        self._wver[0] += 1
-        self._tver[0] += 1
-        g = torch.Generator().manual_seed(seed)
-        host = torch.zeros(self.n_theta, dtype=torch.float32)
-        for name, (off, n, shape) in self.p_off.items():
-            if name.endswith("/gamma"):
-                host[off:off + n] = 1.0
-            elif name.endswith("kernel"):
-                fi, fo = _glorot_fans(name, shape)
-                lim = math.sqrt(6.0 / (fi + fo))
-                host[off:off + n] = ((torch.rand(n, generator=g, dtype=torch.float64) * 2 - 1) * lim).float()
-        self.theta.copy_(host)
-        hs = torch.zeros(self.stats.numel(), dtype=torch.float32)
-        for name, (off, n, _) in self.s_off.items():
-            if name.endswith("moving_variance"):
-                hs[off:off + n] = 1.0
-        self.stats.copy_(hs)
-        if self.train_capable:
-            self.m.zero_()
-            self.v.zero_()
-        self.t = 0
+        self.weights.init_weights(seed)
+
+    def state_dict(self):
+        return self.weights.state_dict()
+
+    def load_state_dict(self, sd):
+        self.weights.load_state_dict(sd)
+
+    def grad_dict(self):
+        return self.weights.grad_dict()
 
     def P(self, name):
         off, n, shape = self.p_off[name]
@@ -647,37 +754,6 @@ class Engine:
     def S(self, name):
         off, n, shape = self.s_off[name]
         return self.stats[off:off + n]
-
-    def state_dict(self):
-        """name -> CPU tensor in Keras layout (trainable + moving statistics)."""
-        out = OrderedDict()
-        for name in self.spec_order:
-            if name in self.p_off:
-                off, n, shape = self.p_off[name]
-                out[name] = self.theta[off:off + n].reshape(shape).cpu().clone()
-            else:
-                off, n, shape = self.s_off[name]
-                out[name] = self.stats[off:off + n].reshape(shape).cpu().clone()
-        return out
-
-    def load_state_dict(self, sd):
-        self._wver[0] += 1
-        self._tver[0] += 1
-        for name in self.spec_order:
-            t = torch.as_tensor(np.asarray(sd[name]), dtype=torch.float32).reshape(-1)
-            if name in self.p_off:
-                off, n, _ = self.p_off[name]
-                dst = self.theta
-            else:
-                off, n, _ = self.s_off[name]
-                dst = self.stats
-            if t.numel() != n:
-                raise ValueError("shape mismatch for %s: got %d values, need %d" % (name, t.numel(), n))
-            dst[off:off + n].copy_(t.to(self.dev))
-
-    def grad_dict(self):
-        return OrderedDict((name, self.grad[off:off + n].reshape(shape).cpu().clone())
-                           for name, (off, n, shape) in self.p_off.items())
 
     # ------------------------------------------------------------------ graph construction
     def new(self, *shape):
@@ -711,6 +787,7 @@ class Engine:
             return self._build_mobilenet(d.y)
         if self.backbone == "InceptionResNetV2":
             net = IRv2Backbone(self, d.y); n.append(net)
+            self._irv2 = net
             self.backbone_out = net.y
             return self._build_head(net.y)
         # ---- Xception entry flow, block 1
@@ -768,14 +845,11 @@ class Engine:
             self._head_parts = int(L.spnet_adam_parts(self._head_hi))
             self._rest_parts = int(L.spnet_adam_parts(self.n_theta - self._head_hi))
             self._opt_stream = None
-            self._head_done = False
             # per-step scalars the kernels read from device memory: [lr_t (f32), dropout seed (u32)]
             self.step_params = torch.zeros(4, device=self.dev, dtype=torch.int32)
             self._step_upload = L.AsyncUploader(self.dev, depth=8)
             self.lr_ptr = self.step_params.data_ptr()
             self.seed_ptr = self.step_params.data_ptr() + 4
-            self._graph = None
-            self._graph_warm = 0
 
     # ------------------------------------------------------------------ execution
     def forward(self, X=None, training=False):
@@ -784,34 +858,47 @@ class Engine:
             raise RuntimeError("engine was built with train=False")
         if X is not None:
             self.x_in.copy_(X.reshape(self.x_in.shape))
+        self.refresh(training)
         if training:
-            self._wver[0] += 1              # moving statistics move; this plan's scale|shift now hold batch statistics
-            self._coeff_ver = -1
-        else:
-            self._infer_fresh = self._coeff_ver != self._wver[0]
-        self.refresh_planes()               # (on THIS stream, before any branch reads them)
+            self.weights.stats_ver += 1     # moving statistics move; this plan's scale|shift now hold batch statistics
+            self._coeffs_at = None
         for node in self.nodes:
             node.fwd(training)
         if self.sigmoid_cols is not None:
             L.spnet_selective_sigmoid(L.ptr(self.out), None, self.B, self.n_out, self.sigmoid_cols[0],
                                       self.sigmoid_cols[1], 0, _stream())
-        if not training:
-            self._coeff_ver = self._wver[0]
         return self.out
+
+    def refresh(self, training):
+        """The one freshness rule for the copies derived from the weights: each records the version(s) of theta / stats
+        it was computed at, and this launches exactly those that are stale and that a pass of this kind reads -- the
+        bf16x3 planes, the IRv2 group operands, W^T (training: read by backward) and the BatchNorm inference coefficients
+        (inference; from theta AND stats).  On the main stream, ahead of every reader on every stream (a strided block's
+        residual convolution runs on the side stream)."""
+        w = self.weights
+        w.refresh_planes()
+        if training:
+            w.refresh_transposes()
+        if self._irv2 is not None:
+            self._irv2.refresh_wm()
+        if not training and self._coeffs_at != (w.theta_ver, w.stats_ver):
+            for bn in self._bns:
+                bn.infer()
+            self._coeffs_at = (w.theta_ver, w.stats_ver)
 
     def predict_step(self, use_graph=None):
         """Inference forward of self.x_in -> self.out as ONE hipGraph replay (BASELINE configs[4]: predict_spnet.py's
-        model.predict loop).  The plan is static, so the ~110 launches of a forward are captured once per plan; the
-        BatchNorm inference coefficients are refreshed by an eager forward whenever the weights or moving statistics
-        changed since this plan last ran (the graph itself holds no weight-dependent host decisions).
+        model.predict loop).  The plan is static, so the ~110 launches of a forward are captured once per plan, behind
+        an eager forward that brought every derived copy up to date; before a replay, refresh() launches those that went
+        stale since (the graph itself holds no weight-dependent host decisions).
         use_graph=False keeps the eager launches."""
         if use_graph is False or self.prof is not None:
             return self.forward(None, training=False)
-        if self._coeff_ver != self._wver[0] or self._igraph is None:
-            out = self.forward(None, training=False)          # eager: also recomputes scale|shift of every BatchNorm
-            if self._igraph is None:
-                self._igraph = _capture(lambda: self.forward(None, training=False))
+        if self._igraph is None:
+            out = self.forward(None, training=False)
+            self._igraph = _capture(lambda: self.forward(None, training=False))
             return out
+        self.refresh(False)
         self._igraph.replay()
         return self.out
 
@@ -825,9 +912,7 @@ class Engine:
             L.spnet_selective_sigmoid(L.ptr(self.out), L.ptr(self.dout), self.B, self.n_out, self.sigmoid_cols[0],
                                       self.sigmoid_cols[1], 1, _stream())
         self.deferred_wgrads = []
-        if self._wT_ver[0] != self._tver[0]:    # weights were loaded / re-initialised since the last optimizer step
-            self.refresh_transposes()
-        self.refresh_planes()
+        self.refresh(True)                      # (weights loaded / re-initialised since the forward)
         for node in reversed(self.nodes):
             g = node.bwd(g)
             if node is self._first_middle:      # (flushing in 2 or 4 smaller batches measured no faster)
@@ -840,78 +925,6 @@ class Engine:
         self.reduce_depthwise_wgrads()
         if self.wgrad_stream is not None:      # every weight gradient must have landed before the optimizer
             torch.cuda.current_stream().wait_stream(self.wgrad_stream)
-
-    def _build_planes(self):
-        """bf16x3 operand planes for every pointwise kernel of this plan that a bf16x3 launch will read (allocated once per
-        weight set: a later plan over the same weights finds them, and adds the data-gradient planes an inference plan
-        had no use for)."""
-        for pw in self._pw_layers:
-            if not (pw.x3_fwd or pw.x3_dgrad):
-                continue
-            ent = self._planes.setdefault(pw.wname, [None, None])
-            if pw.x3_fwd and ent[0] is None:
-                ent[0] = torch.zeros(3 * int(L.spnet_bf16x3_plane_elems(pw.cout, pw.cin)), dtype=torch.int16, device=self.dev)
-                self._planes_gen[0] += 1
-            if pw.x3_dgrad and ent[1] is None:
-                ent[1] = torch.zeros(3 * int(L.spnet_bf16x3_plane_elems(pw.cin, pw.cout)), dtype=torch.int16, device=self.dev)
-                self._planes_gen[0] += 1
-        if self._planes_jobs is None or self._planes_jobs[1] != self._planes_gen[0]:
-            self._planes_ver[0] = -1
-
-    def refresh_planes(self):
-        """The weights split into their bf16 planes, both operand forms, ONE batched launch -- whenever theta changed since
-        the last split (optimizer step, load, re-initialisation).  Called at the start of forward() / backward() on the
-        main stream: the split is ordered in front of every consumer on every stream (a strided block's residual
-        convolution runs on the side stream)."""
-        if self.pointwise != "bf16x3" or not self._planes or self._planes_ver[0] == self._tver[0]:
-            return
-        if self._planes_jobs is None or self._planes_jobs[1] != self._planes_gen[0]:
-            flat, mx = [], 1
-            for wname, (pf, pd) in self._planes.items():
-                off, n, shape = self.p_off[wname]
-                cin, cout = int(shape[-2]), int(shape[-1])
-                w = self.theta.data_ptr() + 4 * off
-                if pf is not None:      # forward: B element (n = cout, k = cin) = W[k][n]
-                    flat += [w, pf.data_ptr(), cin, cout, 1, cout]
-                    mx = max(mx, pf.numel() // 3)
-                if pd is not None:      # data gradient dX = dY W^T: (n = cin, k = cout) = W[n][k]
-                    flat += [w, pd.data_ptr(), cout, cin, cout, 1]
-                    mx = max(mx, pd.numel() // 3)
-            if self._planes_jobs is not None:     # a captured graph may still hold the old table's address: keep it alive,
-                self._planes_tables_kept = getattr(self, "_planes_tables_kept", []) + [self._planes_jobs[0]]
-                self._graph = self._igraph = None     # ... and re-capture with the new one
-            self._planes_jobs = (torch.tensor(flat, dtype=torch.int64, device=self.dev), self._planes_gen[0], len(flat) // 6, mx)
-        table, _, nj, mx = self._planes_jobs
-        L.spnet_split_bf16x3_batched(table.data_ptr(), nj, mx, _stream())
-        self._planes_ver[0] = self._tver[0]
-
-    def transposed(self, wname):
-        """W^T buffer ([cout][cin]) of a pointwise kernel; kept current by refresh_transposes()."""
-        if wname not in self._wT:
-            off, n, shape = self.p_off[wname]
-            self._wT[wname] = self.new(n)
-            self._wT_ver[0] = -1
-        return self._wT[wname]
-
-    def refresh_transposes(self):
-        """One batched launch: W^T of the pointwise kernels whose data-gradient GEMM blends the BatchNorm backward
-        into its A operand (Pointwise.blend) -- that kernel exists in the forward operand form only.  (Round 2 also
-        measured ALL data-gradient GEMMs on transposed copies: the forward form is no faster than the K-major-B
-        form, 61.5 vs 69.2 us on 6144x728x728, so the other layers read W in place.)"""
-        if not self._wT:
-            self._wT_ver[0] = self._tver[0]
-            return
-        if self._wT_jobs is None or self._wT_jobs[1] != len(self._wT):
-            flat, mr, mc = [], 1, 1
-            for name, dst in self._wT.items():
-                off, n, shape = self.p_off[name]
-                R, C = int(shape[-2]), int(shape[-1])          # [cin][cout] (1x1 HWIO kernels: trailing two dims)
-                flat += [self.theta.data_ptr() + 4 * off, dst.data_ptr(), R, C]
-                mr, mc = max(mr, R), max(mc, C)
-            self._wT_jobs = (torch.tensor(flat, dtype=torch.int64, device=self.dev), len(self._wT), mr, mc)
-        table, nj, mr, mc = self._wT_jobs
-        L.spnet_transpose_batched(table.data_ptr(), nj, mr, mc, _stream())
-        self._wT_ver[0] = self._tver[0]
 
     def reduce_depthwise_wgrads(self):
         """Fold the partial sums every fused depthwise backward left behind into the 34 depthwise weight
@@ -1071,7 +1084,6 @@ class Engine:
         leg) run it in line.  Measured (tools/ab_engine_flags.py early_head=True,False, one box): 10.000 against
         10.048 ms per step -- the 0.34 ms of launches that leave the dependency chain come back as slower neighbours,
         the step is bound by what its kernels move, not by their order."""
-        self._head_done = True
         side = self.wgrad_stream
         if side is None:
             self._adam_range(0, grad_scale)
@@ -1084,28 +1096,22 @@ class Engine:
         with torch.cuda.stream(opt):
             self._adam_range(0, grad_scale)
 
-    def adam_step(self, lr=None, grad_scale=1.0):
+    def adam_step(self, lr=None, grad_scale=1.0, head_done=False):
         """Fused Keras-Adam + l2 over the flat buffers, in two ranges (the Dense head's kernel; everything else) so that
         the first can run early (adam_head_early) -- the same two launches, the same bits, wherever they run.
-        lr=None: the step size already sits in device memory (train_step); a float: stand-alone use."""
+        lr=None: the step size already sits in device memory (train_step); a float: stand-alone use.
+        head_done: adam_head_early has run the head range in this step's backward."""
         if lr is not None:
             self._upload_step_params(lr)
-        self._wver[0] += 1
-        if self._head_done:
+        if head_done:
             if self._opt_stream is not None:
                 torch.cuda.current_stream().wait_stream(self._opt_stream)
         else:
             self._adam_range(0, grad_scale)
-        self._head_done = False
         self._adam_range(1, grad_scale)
         L.spnet_adam_l2_sum(L.ptr(self.sq_scratch), self._head_parts + self._rest_parts, L2_COEF, self.loss_out[6:].data_ptr(),
                             _stream())
-        self._tver[0] += 1
-        self.refresh_transposes()
-        # ... and the bf16x3 planes of the new weights, here and not lazily at the next forward: a captured train step
-        # (SPNET_TRAIN_GRAPH=1) then always contains the split, whatever ran between the warm step and the capture
-        # (round-4 ADVICE: a predict / validation pass in between left the planes "fresh" and the graph without a split)
-        self.refresh_planes()
+        self.weights.theta_ver += 1
 
     def train_step(self, X, Y, lr, reducer=None):
         """augmented batch X -> forward -> custom_loss -> backward -> (all-reduce) -> Adam(+l2).
@@ -1117,32 +1123,16 @@ class Engine:
         if Y is not None:
             self.y_true.copy_(Y.reshape(self.y_true.shape))
         self._upload_step_params(lr)
-        if reducer is None and self.use_graph and self.update_mask is None and self.prof is None:
-            # Single GPU: the step is a fixed sequence of ~500 launches on two streams -> captured ONCE as
-            # a hipGraph and replayed (host enqueue 1.9 ms instead of 4.4 ms per step).
-            if self._graph is None and self._graph_warm >= 1:
-                self._graph = _capture(lambda: self._step_body(None, 1.0))
-            if self._graph is not None:
-                self._graph.replay()
-                # the host bookkeeping _step_body does outside the launches: weights, moving statistics and the
-                # transposed copies changed (the replay refreshed the latter itself), and this plan's BatchNorm
-                # scale|shift hold batch statistics again -- predict_step must rebuild its coefficients
-                self._wver[0] += 2
-                self._coeff_ver = -1
-                self._tver[0] += 1
-                self._wT_ver[0] = self._tver[0]
-                self._planes_ver[0] = self._tver[0]
-                return self.loss_out
-            self._graph_warm += 1
-        self._step_body(reducer, None)
+        self._step_body(reducer)
         return self.loss_out
 
-    def _step_body(self, reducer, scale):
+    def _step_body(self, reducer):
         self.forward(None, training=True)
         self.loss(None)
+        head_done = reducer is None and self.early_head
         if reducer is None:
-            scale = 1.0 if scale is None else scale
-            self.backward(after_head=(lambda: self.adam_head_early(scale)) if self.early_head else None)
+            scale = 1.0
+            self.backward(after_head=(lambda: self.adam_head_early(scale)) if head_done else None)
         else:
             reducer.side_stream = self.wgrad_stream
             # (the head's optimizer step stays behind finish() here: launching it behind the head buckets' all-reduce is the
@@ -1159,7 +1149,7 @@ class Engine:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()
                 ev.append((e0, e1))
-        self.adam_step(None, scale)
+        self.adam_step(None, scale, head_done)
 
     def grad_buckets(self, bucket_bytes=32 << 20):
         """plan_grad_buckets over this plan's nodes: (buckets [(lo, hi, trigger node)], tail [(lo, hi)])."""
@@ -1421,8 +1411,12 @@ class Pointwise:
         # one or two column tiles; measured on MI355X (tools/gemm_sweep.py blend, us incl. the BN kernels):
         #   cin 128 (M 372,000): 242 -> 202     cin 256 (M 94,752): 163 -> 189     cin 728 (M 6,144): 85 -> 99
         self.blend = bool(allow_blend and eng.train_capable and cin <= 128)
-        self.wT = eng.transposed(wname) if self.blend else None     # [cout][cin]: forward operand form for the blend
+        self.wT = eng.weights.transposed(wname) if self.blend else None     # [cout][cin]: forward operand form for the blend
         self.defer_wgrad = defer_wgrad      # dW is left to Engine.flush_deferred_wgrads() (one batched launch)
+
+    def planes(self, form):
+        """bf16x3 planes of the kernel (WeightSet.need_planes): form 0 the forward operand, 1 the data-gradient one"""
+        return self.e.weights.planes[self.wname][form]
 
     def _x3(self, tag, A, lda, planes, C, ldc, N, K, colstats_region=None):
         """One bf16x3 launch: C[M][N] = A[M][K] x planes (+ BatchNorm column sums of C); returns the partial row count."""
@@ -1465,7 +1459,7 @@ class Pointwise:
         """Forward from the planes of x (written by the producing depthwise kernel); with colstats_region the BatchNorm
         column sums of y are left there and the partial row count is returned."""
         tag = "x3p aB" if colstats_region is None else "x3p aB+stats"
-        return self._x3p(tag, zp, self.e._planes[self.wname][0], y, self.cout, self.cin, colstats_region)
+        return self._x3p(tag, zp, self.planes(0), y, self.cout, self.cin, colstats_region)
 
     def bwd_p(self, zp, dyp, dx):
         """Backward from planes: dW = z^T dy by spnet_gemm_bf16x3_wgrad_batched (deferred into the engine's batched launch,
@@ -1476,18 +1470,18 @@ class Pointwise:
         else:
             e._flush_x3_wgrads([("x3", zp, dyp, self.gw, self.cin, self.cout, self.M)])
         if dx is not None:
-            self._x3p("x3p ab", dyp, e._planes[self.wname][1], dx, self.cin, self.cout)
+            self._x3p("x3p ab", dyp, self.planes(1), dx, self.cin, self.cout)
 
     def fwd(self, x, y):
         if self.x3_fwd and self.e.pointwise == "bf16x3":
-            self._x3("x3 aB", x, self.cin, self.e._planes[self.wname][0], y, self.cout, self.cout, self.cin)
+            self._x3("x3 aB", x, self.cin, self.planes(0), y, self.cout, self.cout, self.cin)
             return
         _gemm(x, K_MAJOR, self.cin, self.w, OUT_MAJOR, self.cout, y, self.cout, self.M, self.cout, self.cin, self.e)
 
     def fwd_colstats(self, x, y, region=WS_BNP):
         """Forward + BatchNorm column sums of y left in `region`; returns the partial row count."""
         if self.x3_fwd and self.e.pointwise == "bf16x3":
-            return self._x3("x3 aB+stats", x, self.cin, self.e._planes[self.wname][0], y, self.cout, self.cout, self.cin,
+            return self._x3("x3 aB+stats", x, self.cin, self.planes(0), y, self.cout, self.cout, self.cin,
                             colstats_region=region)
         return _gemm_colstats(x, self.cin, self.w, self.cout, y, self.cout, self.M, self.cout, self.cin, self.e,
                               region=region)
@@ -1509,7 +1503,7 @@ class Pointwise:
                 _gemm(x, OUT_MAJOR, self.cin, dy, OUT_MAJOR, self.cout, self.gw, self.cout, self.cin, self.cout,
                       self.M, e, region=WS_GEMM2)
         if dx is not None and self.x3_dgrad and e.pointwise == "bf16x3":
-            self._x3("x3 ab", dy, self.cout, e._planes[self.wname][1], dx, self.cin, self.cin, self.cout)
+            self._x3("x3 ab", dy, self.cout, self.planes(1), dx, self.cin, self.cin, self.cout)
         elif dx is not None:    # dx[M,cin] = dy[M,cout] @ W^T: W read in place as a K-major B operand
             _gemm(dy, K_MAJOR, self.cout, self.w, K_MAJOR, self.cout, dx, self.cin, self.M, self.cin, self.cout, e)
 
@@ -1602,6 +1596,7 @@ class BN:
         self.gamma, self.beta = eng.P(name + "/gamma"), eng.P(name + "/beta")
         self.mm, self.mv = eng.S(name + "/moving_mean"), eng.S(name + "/moving_variance")
         self.ss = eng.new(2 * C)                 # [scale | shift], valid after finalize()/infer()
+        eng._bns.append(self)
         if eng.train_capable:
             self.ggamma, self.gbeta = eng.G(name + "/gamma"), eng.G(name + "/beta")
             self.save = eng.new(2 * C)           # [batch mean | invstd]
@@ -1649,8 +1644,7 @@ class BN:
                                 BN_EPS, BN_MOMENTUM, _stream())
 
     def infer(self):
-        if not self.e._infer_fresh:          # scale|shift of this plan are still valid for the current weights
-            return
+        """scale|shift from the moving statistics (Engine.refresh, when the weights or statistics moved)"""
         L.spnet_bn_infer_coeffs(self.C, L.ptr(self.gamma), L.ptr(self.beta), L.ptr(self.mm), L.ptr(self.mv),
                                 L.ptr(self.ss), BN_EPS, _stream())
 
@@ -1860,9 +1854,8 @@ class SepConvBN:
                     and ((self.M + 191) // 192) * ((self.cout + 95) // 96) >= e.fuse_min_tiles):
                 # inference: pointwise GEMM + this BatchNorm's affine + the consumer's ReLU and depthwise in ONE launch,
                 # the result written as the consumer's z planes (spnet_gemm_bf16x3_pp_dwfwd); yp is never written
-                self.bn.infer()
                 t0 = prof.start() if prof is not None else None
-                L.spnet_gemm_bf16x3_pp_dwfwd(L.ptr(self.zp), L.ptr(e._planes[self.pw.wname][0]), e.B, self.H, self.W, self.cin,
+                L.spnet_gemm_bf16x3_pp_dwfwd(L.ptr(self.zp), L.ptr(self.pw.planes(0)), e.B, self.H, self.W, self.cin,
                                              self.cout, L.ptr(self.bn.ss), nxt.relu_in, L.ptr(nxt.wd), L.ptr(nxt.zp), _stream())
                 if prof is not None:
                     prof.stop("gemm", t0, 2.0 * self.M * self.cin * self.cout, ("x3p aB+dwfwd", self.M, self.cout, self.cin))
@@ -1872,7 +1865,6 @@ class SepConvBN:
                 self.pw.fwd_p(self.zp, self.yp)
             else:
                 self.pw.fwd(self.z, self.yp)
-            self.bn.infer()
         if self.mode == "apply":
             self.bn.apply(self.yp, self.y, self.act, self.residual)
 
@@ -1897,7 +1889,7 @@ class SepConvBN:
                 st = self.src.stats_bn if self.src.stats_bn is not None else sb
                 prof = e.prof
                 t0 = prof.start() if prof is not None else None
-                L.spnet_gemm_bf16x3_pp_dwbwd(L.ptr(self.dyp), L.ptr(e._planes[self.pw.wname][1]), e.B, self.H, self.W, self.cin,
+                L.spnet_gemm_bf16x3_pp_dwbwd(L.ptr(self.dyp), L.ptr(self.pw.planes(1)), e.B, self.H, self.W, self.cin,
                                              self.cout, L.ptr(self.src.t), L.ptr(self.wd), L.ptr(self.dx), self.relu_in,
                                              L.ptr(add), L.ptr(self.wpart), sb.scale_ptr if sb else None,
                                              sb.shift_ptr if sb else None, st.mean_ptr if st else None,
@@ -2012,7 +2004,6 @@ class StridedBlock(Node):
             self.bnr.finalize(self.pwr.fwd_colstats(self.xs, self.yr, region=region), region=region)
         else:
             self.pwr.fwd(self.xs, self.yr)
-            self.bnr.infer()
         if side is not None:
             torch.cuda.set_stream(main)
         self.u1.fwd(training)
@@ -2116,7 +2107,7 @@ class IRv2Backbone(Node):
         # BatchNormalization (_IRGroup).  In training every member needs its one consumer to be a k x k convolution or a
         # Concatenate (they leave the masked gradient and the BatchNorm sums in the group's blocks): true for every
         # group of the network.
-        self.groups, self._wm_jobs, self._wm_ver = [], None, -1
+        self.groups, self._wm_jobs, self._wm_at = [], None, None
         consumer = {}
         for o in self.ops:
             for t in o.srcs():
@@ -2194,10 +2185,11 @@ class IRv2Backbone(Node):
         return self.ones[C]
 
     def refresh_wm(self):
-        """The kernels of every sibling group gathered side by side into its GEMM operand: one launch for the network."""
-        if not self.groups:
-            return
+        """The kernels of every sibling group gathered side by side into its GEMM operand: one launch for the network,
+        whenever theta changed since the last gather (Engine.refresh)."""
         e = self.e
+        if not self.groups or self._wm_at == e.weights.theta_ver:
+            return
         if self._wm_jobs is None:
             flat, mx = [], 4
             for G in self.groups:
@@ -2207,13 +2199,9 @@ class IRv2Backbone(Node):
             self._wm_jobs = (torch.tensor(flat, dtype=torch.int64, device=e.dev), len(flat) // 6, mx)
         table, nj, mx = self._wm_jobs
         L.spnet_copy_cols_batched(table.data_ptr(), nj, mx, _stream())
-        self._wm_ver = e._tver[0]
+        self._wm_at = e.weights.theta_ver
 
     def fwd(self, training):
-        # (training: every step follows an optimizer step -- and a captured step replays without host code, so the gather
-        # is part of the step; inference: only when the weights changed since the last gather)
-        if training or self._wm_ver != self.e._tver[0]:
-            self.refresh_wm()
         for o in self.ops:
             o.fwd(training)
 
@@ -2736,7 +2724,6 @@ class MobileBlock(Node):
             self.bn.finalize(self.pw.fwd_colstats(self.bn_dw.y, self.yp))
         else:
             self.pw.fwd(self.bn_dw.y, self.yp)
-            self.bn.infer()
         self.bn.apply(self.yp, self.y, ACT_RELU6)
 
     def bwd(self, g):

@@ -250,10 +250,6 @@ class Model:
         key = (int(batch), bool(train))
         if key not in self._engines:
             root = self._root
-            if root is not None and train and not hasattr(root, "grad"):
-                torch = _torch()
-                for a in ("grad", "m", "v"):       # optimizer state lives beside the weights it updates
-                    setattr(root, a, torch.zeros(root.n_theta, device=root.dev, dtype=torch.float32))
             eng = self._Engine(self.H, self.W, batch, n_out=self.Y0size, device=self.device, loss_type=cf.loss_type,
                                seed=self.seed, train=train, adam_eps=ADAM_EPS, share_from=root, rank=self.rank,
                                sigmoid_cols=(cf.ind_noobj, cf.vars_per_pred) if self.compound else None,

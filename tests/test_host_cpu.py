@@ -169,6 +169,39 @@ def test_parameter_layout_and_layer_table():
     assert z.tolist() == [[1, 2, 10, 3, 4, 11, 5, 6, 12]]
 
 
+def test_weight_set_on_the_cpu():
+    """WeightSet, the weights every plan over one model shares: deterministic initialisation per seed, an exact
+    state_dict round trip, both versions bumped by init and load (what the derived copies are checked against), and ONE
+    grad / m / v however many training plans ask for them."""
+    import torch
+    from spnet_amd.engine import WeightSet
+    h, w = 64, 96
+    a, b, c = (WeightSet(h, w, device="cpu", seed=s) for s in (3, 3, 4))
+    assert torch.equal(a.theta, b.theta) and torch.equal(a.stats, b.stats)
+    assert not torch.equal(a.theta, c.theta)
+    assert float(a.theta.abs().max()) > 0 and float(a.stats.max()) == 1.0
+    sd = c.state_dict()
+    g = torch.Generator().manual_seed(0)
+    for k in sd:
+        if "/moving_" in k:                                                   # non-default moving statistics
+            sd[k] = torch.rand(sd[k].shape, generator=g) + 0.5
+    vers = (a.theta_ver, a.stats_ver)
+    a.load_state_dict(sd)
+    assert (a.theta_ver, a.stats_ver) == (vers[0] + 1, vers[1] + 1)
+    back = a.state_dict()
+    assert list(back) == list(sd) and all(torch.equal(back[k], sd[k]) for k in sd)
+    assert torch.equal(a.theta, c.theta) and not torch.equal(a.stats, c.stats)
+    a.init_weights(3)
+    assert (a.theta_ver, a.stats_ver) == (vers[0] + 2, vers[1] + 2)
+    assert torch.equal(a.theta, b.theta) and torch.equal(a.stats, b.stats)
+    assert a.grad is None
+    a.alloc_train_state()
+    first = (a.grad, a.m, a.v)
+    a.alloc_train_state()
+    assert all(x is y for x, y in zip(first, (a.grad, a.m, a.v)))
+    assert len({id(x) for x in first}) == 3 and all(x.numel() == a.n_theta for x in first)
+
+
 def test_fake_espi_generator_is_deterministic_and_encodable():
     from spnet_amd import fake_espi as F
     X1, l1 = F.generate(4, seed=3, workers=1)

@@ -2,7 +2,7 @@
 """Dev tool (GPU box): the benchmark train step (Xception, batch 32, 384x512, fixed frames) on two engines that differ in one
 constructor flag, alternating in ONE process (cdna_hip_programming.md rule 24).
 usage: ab_engine_flags.py flag=valueA,valueB [rounds] [steps]     e.g.  fuse_dw_bwd=True,False
-       ab_engine_flags.py attr:name=valueA,valueB ...             sets an attribute after construction (attr:use_graph=True,False)"""
+       ab_engine_flags.py attr:name=valueA,valueB ...             sets an attribute after construction"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

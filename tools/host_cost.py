@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Host-side cost of enqueueing ONE train step on an idle GPU (eager launches vs hipGraph replay)."""
+"""Host-side cost of enqueueing ONE train step on an idle GPU (two streams, and the weight gradients on the main stream)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -7,8 +7,7 @@ from spnet_amd.engine import Engine
 eng = Engine(384, 512, 32, device="cuda:0", seed=0)
 X = torch.rand(32, 384, 512, 1, device="cuda") * 2 - 1
 Y = torch.rand(32, 576, device="cuda")
-for mode in ("eager", "graph", "eager-noverlap"):
-    eng.use_graph = (mode == "graph")
+for mode in ("eager", "eager-noverlap"):
     if mode == "eager-noverlap":
         eng.wgrad_stream = None
     for _ in range(3):

@@ -48,7 +48,7 @@ for i, n in enumerate(eng.nodes):
     wrap(n, "fwd", (nm, "fwd"))
     if not PREDICT:
         wrap(n, "bwd", (nm, "bwd"))
-for m in (() if PREDICT else ("flush_deferred_wgrads", "reduce_depthwise_wgrads", "adam_step", "loss", "refresh_planes")):
+for m in (() if PREDICT else ("flush_deferred_wgrads", "reduce_depthwise_wgrads", "adam_step", "loss", "refresh")):
     wrap(eng, m, (m, ""))
 R = 5
 e0, e1 = ev(), ev()
@@ -68,5 +68,5 @@ for nm in names:
     sb += b
     print("%-34s %8.3f %8.3f" % (nm, f, b))
 print("%-34s %8.3f %8.3f" % ("sum over nodes", sf, sb))
-for m in (() if PREDICT else ("flush_deferred_wgrads", "reduce_depthwise_wgrads", "adam_step", "loss", "refresh_planes")):
+for m in (() if PREDICT else ("flush_deferred_wgrads", "reduce_depthwise_wgrads", "adam_step", "loss", "refresh")):
     print("%-34s %8.3f" % (m, ms((m, ""))))

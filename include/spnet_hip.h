@@ -456,6 +456,26 @@ int spnet_dropout(const float* x, float* y, long n, unsigned seed, float rate, c
 int spnet_fake_espi(const float* waves, const float* nodes, const int* nnode, int N, int H, int W, unsigned seed,
                     int noise, float* out_f, unsigned char* out_u8, void* stream);
 
+/* ---- band-pass mix-up (spnet/augmentation.py:10-62; csrc/bandpass.hip) ------------------------------------------- */
+/* Frames x [*][H][W], one channel, 16 <= H, W <= 2048; x_kind 0 = uint8, 1 = fp32 pixel units (0..255), 2 = fp32 network
+ * units ([-1,1], pixel = (x/2 + 1/2) * 255).  A window is the 16 x 16 block of the centred spectrum, frequencies k, l in
+ * [-8, 8), as [16][16] complex (re, im) fp32, row k + 8, column l + 8.  ws: spnet_bandpass_ws(N, H, W) floats (-1 = the
+ * dimensions are not supported).
+ *   spnet_bandpass_project  win[n] = window of x[n] after cv2.flip(x[n], flip[n]) (flip NULL or a code outside
+ *                           {-1, 0, 1}: not flipped) -- the real-image table of the mix-up.
+ *   spnet_bandpass_apply    frame m = x[sel[m]] (sel NULL: x[m]; sel clamped to [0, n_src)), mixed with window
+ *                           table[row[m]] (row clamped to [0, n_table)) scaled by s[m]; the complex magnitude of the
+ *                           inverse, min-max normalised to [0, 255] (a constant becomes 0), clipped.  Written to the same
+ *                           frame index of out_f (f_kind 0 = pixel units, 1 = network units) and / or out_u8 (round half to
+ *                           even, saturated).  out_f may be x (fp32 kinds) and out_u8 may be x (uint8) when sel holds no
+ *                           index twice.  Deterministic: a frame's bits do not depend on the batch around it. */
+long spnet_bandpass_ws(int N, int H, int W);
+int spnet_bandpass_project(const void* x, int x_kind, int N, int H, int W, const int* flip, float* win, float* ws,
+                           void* stream);
+int spnet_bandpass_apply(const void* x, int x_kind, const int* sel, int n_src, int N, int H, int W, const float* table,
+                         int n_table, const int* row, const float* s, float* out_f, int f_kind, unsigned char* out_u8,
+                         float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

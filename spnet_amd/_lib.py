@@ -136,6 +136,9 @@ _SIGS = {
     "spnet_warp_affine_fixed": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P]),
     "spnet_fake_espi": (c_int, [P, P, P, c_int, c_int, c_int, c_uint, c_int, P, P, P]),
     "spnet_dropout": (c_int, [P, P, c_long, c_uint, c_float, P, P]),
+    "spnet_bandpass_ws": (c_long, [c_int, c_int, c_int]),
+    "spnet_bandpass_project": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "spnet_bandpass_apply": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, P, P, P]),
 }
 
 EXPORTS = tuple(_SIGS)

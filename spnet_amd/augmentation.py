@@ -7,7 +7,12 @@ the PIXEL work runs in HIP kernels on frames that never leave HBM (csrc/augment.
 
 Offline warps (augment_preproc.py:56-100): flip / rotate / translate = one inverse-affine bilinear
 gather kernel plus the reference's host-side metadata arithmetic.
+
+Band-pass mix-up (augmentation.py:10-62): BandpassPool holds the real frames and their low-frequency windows on the
+device, BandpassMixer draws and applies the mix-up (csrc/bandpass.hip), bandpass_mixup is the reference's function.
 """
+import glob
+import os
 import random
 
 import numpy as np
@@ -75,7 +80,11 @@ def draw_blur_gate(blur_prob_outer=0.4, blur_prob=0.3):
 class DeviceAugmenter:
     """Keeps the pristine frames [N,H,W,1] in HBM and writes augmented batches into a device buffer."""
 
-    def __init__(self, X_orig, real_blur=False):
+    def __init__(self, X_orig, real_blur=False, bandpass_real=None, bpmix_prob=0.3):
+        """bandpass_real (None = off, the reference's default: its bp_mixup call is commented out, callbacks.py:333): a
+        directory of real *.png frames of the frames' size, a BandpassPool or a uint8 device tensor [R,H,W]; after the
+        blur gate, np.random.rand() < bpmix_prob selects the frames that are band-pass mixed (callbacks.py:311-315).
+        bpmix_prob <= 0 switches the stage off entirely (no draw is made)."""
         if not X_orig.is_cuda:
             raise RuntimeError("DeviceAugmenter needs device-resident frames (no CPU fallback)")
         self.X = X_orig.contiguous()
@@ -90,6 +99,14 @@ class DeviceAugmenter:
         self.mm_host = mm.cpu().numpy()     # min/max of the pristine frames: cutout's fill range
         self.n_salt, self.n_pepper = saltpepper_counts(self.shape)
         self._upload = None
+        self.bpmix_prob = float(bpmix_prob)
+        self.bp = None
+        if bandpass_real is not None and self.bpmix_prob > 0:
+            pool = bandpass_real if isinstance(bandpass_real, BandpassPool) else \
+                BandpassPool.get(bandpass_real, self.H, self.W, self.X.device)
+            if (pool.H, pool.W) != (self.H, self.W):
+                raise ValueError("DeviceAugmenter: band-pass pool is %dx%d, the frames are %dx%d" % (pool.H, pool.W, self.H, self.W))
+            self.bp = pool.mixer
 
     def draw(self, indices, seeds=None):
         """Host-side parameter draw for the given frame indices, reference RNG order per frame.  seeds (optional,
@@ -106,13 +123,21 @@ class DeviceAugmenter:
         ksize = np.zeros(B, np.int32)
         saved = (np.random.get_state(), random.getstate()) if seeds is not None else None
         try:
-            return self._draw(indices, seeds, rects, vals, nrect, coords, flag, ksize)
+            p = self._draw(indices, seeds, rects, vals, nrect, coords, flag, ksize)
+            if self.bp is not None:
+                p["bp_n"] = len(p["bp_sel"])
+                for k, dt in (("bp_sel", np.int32), ("bp_row", np.int32), ("bp_s", np.float32)):
+                    a = np.zeros(B, dt)             # fixed length B: one upload shape per batch size
+                    a[:p["bp_n"]] = p[k]
+                    p[k] = a
+            return p
         finally:
             if saved is not None:       # the per-sample streams must not leak into the process-wide RNGs
                 np.random.set_state(saved[0])
                 random.setstate(saved[1])
 
     def _draw(self, indices, seeds, rects, vals, nrect, coords, flag, ksize):
+        bp_sel, bp_row, bp_s = [], [], []
         for j, i in enumerate(indices):
             if seeds is not None:
                 np.random.seed(int(seeds[j]))
@@ -129,8 +154,16 @@ class DeviceAugmenter:
                 coords[j, 0, :self.n_salt], coords[j, 1, :self.n_salt] = sp[0], sp[1]
                 coords[j, 0, self.n_salt:], coords[j, 1, self.n_salt:] = sp[2], sp[3]
             ksize[j] = draw_blur_gate()
-        return dict(index=np.asarray(indices, np.int32), rects=rects, vals=vals, nrect=nrect, coords=coords, flag=flag,
-                    ksize=ksize)
+            if self.bp is not None and np.random.rand() < self.bpmix_prob:       # AugmentOnTheFly.bp_mixup gate
+                i_real, flip, s = draw_bandpass(self.bp.pool.n_real)
+                bp_sel.append(j)
+                bp_row.append(4 * i_real + BP_FLIPS.index(flip))
+                bp_s.append(s)
+        p = dict(index=np.asarray(indices, np.int32), rects=rects, vals=vals, nrect=nrect, coords=coords, flag=flag,
+                 ksize=ksize)
+        if self.bp is not None:
+            p.update(bp_sel=bp_sel, bp_row=bp_row, bp_s=bp_s)
+        return p
 
     def apply(self, params, out):
         """out[j] = augmented copy of frame params['index'][j]; out is a device tensor [B,H,W,1]."""
@@ -141,6 +174,8 @@ class DeviceAugmenter:
         # of idle GPU (rocprofv3 kernel trace: the gap in front of each __amd_rocclr_copyBuffer), so seven small uploads
         # cost a 12.5 ms step 0.4 ms.  All fields are 4-byte types: packed as int32 words, viewed back on the device.
         names = ("index", "rects", "vals", "nrect", "coords", "flag", "ksize")
+        if self.bp is not None:
+            names += ("bp_sel", "bp_row", "bp_s")
         flat = [np.ascontiguousarray(params[k]).reshape(-1).view(np.int32) for k in names]
         packed = self._upload("params", np.concatenate(flat))      # pinned ring + one async copy
         up, off = {}, 0
@@ -162,6 +197,15 @@ class DeviceAugmenter:
             tmp = torch.empty_like(out)
             L.spnet_gaussian_blur(out.data_ptr(), tmp.data_ptr(), B, self.H, self.W, up["ksize"].data_ptr(), _stream())
             out.copy_(tmp)
+        if self.bp is not None and params["bp_n"] > 0:
+            # the gated frames only, in place, in network units: pixel = (x/2 + 1/2) * 255, mixed, back to [-1,1]
+            n = int(params["bp_n"])
+            ws = torch.empty(L.spnet_bandpass_ws(n, self.H, self.W), device=dev)
+            self._bp_ws = ws
+            pool = self.bp.pool
+            L.spnet_bandpass_apply(out.data_ptr(), 2, up["bp_sel"].data_ptr(), B, n, self.H, self.W, pool.table.data_ptr(),
+                                   4 * pool.n_real, up["bp_row"].data_ptr(), up["bp_s"].data_ptr(), out.data_ptr(), 1, None,
+                                   ws.data_ptr(), _stream())
         return out
 
     def augment(self, indices, out):
@@ -342,7 +386,202 @@ def invert_image(img, metadata, file_prefix):
     return 255 - img, list(metadata), file_prefix + "_i"
 
 
-def bandpass_mixup(img_in, path_real=None):
-    """Out of scope: the reference mixes in private real frames from a
-    hard-coded path (augmentation.py:10-62)."""
-    raise NotImplementedError("bandpass_mixup needs the reference author's private real images")
+# ----------------------------------------------------------------------------- band-pass mix-up
+BP_FLIPS = (-1, 0, 1, 2)          # np.random.choice([-1,0,1,2]) of augmentation.py:26; 2 = no flip
+BP_DEFAULT_PATH = '/home/shawley/datasets/parsed_zooniverze_steelpan/'    # the reference's default argument
+BGR2GRAY = (0.114, 0.587, 0.299)  # cv2.cvtColor(COLOR_BGR2GRAY) weights of B, G, R for float images
+
+
+def draw_bandpass(n_real):
+    """The RNG calls of one bandpass_mixup (augmentation.py:24-27, 51), in its order: random.choice over the sorted file
+    list, np.random.choice([-1,0,1,2]), np.random.rand().  Returns (file index, flip code, s = 3 * rand as float32, the
+    precision the reference's float32 spectra are scaled in)."""
+    i = random.choice(range(n_real))          # consumes what random.choice(files) does: one _randbelow(len)
+    flip = int(np.random.choice([-1, 0, 1, 2]))
+    s = np.float32(np.random.rand() * 3)
+    return i, flip, s
+
+
+def draw_bandpass_batch(n_real, n, seeds=None):
+    """n draws of draw_bandpass.  seeds (optional, one per sample): each sample's draws come from numpy / python streams
+    seeded with its own seed; the process-wide RNG states are saved and restored around the draw (DeviceAugmenter.draw).
+    Returns dict(real, flip, s, row), row = 4 * real + BP_FLIPS.index(flip): the row of BandpassPool.table."""
+    real, flip, s = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+    saved = (np.random.get_state(), random.getstate()) if seeds is not None else None
+    try:
+        for j in range(n):
+            if seeds is not None:
+                np.random.seed(int(seeds[j]))
+                random.seed(int(seeds[j]))
+            real[j], flip[j], s[j] = draw_bandpass(n_real)
+    finally:
+        if saved is not None:
+            np.random.set_state(saved[0])
+            random.setstate(saved[1])
+    row = (4 * real + np.searchsorted(BP_FLIPS, flip)).astype(np.int32)
+    return dict(real=real, flip=flip, s=s, row=row)
+
+
+def bandpass_check_dims(H, W):
+    if H < 16 or W < 16:
+        raise ValueError("bandpass_mixup: frames must be at least 16 x 16 (the mixed 16 x 16 window of lowest "
+                         "frequencies), got %d x %d" % (H, W))
+
+
+def read_real_frames(path, H, W):
+    """The sorted *.png files of `path` (the reference's glob order is unspecified) read as greyscale uint8 [R,H,W].
+    FileNotFoundError when there are none, ValueError naming the first file of another size."""
+    from PIL import Image
+    files = sorted(glob.glob(os.path.join(path, '*.png')))
+    if not files:
+        raise FileNotFoundError("bandpass_mixup: no real *.png images in %r" % path)
+    imgs = []
+    for f in files:
+        with Image.open(f) as im:
+            a = np.asarray(im.convert("L"), dtype=np.uint8)
+        if a.shape != (H, W):
+            raise ValueError("bandpass_mixup: real image %s is %dx%d, the frames are %dx%d" % (f, a.shape[0], a.shape[1], H, W))
+        imgs.append(a)
+    return files, np.stack(imgs)
+
+
+class BandpassPool:
+    """The real frames of the mix-up on the device, uint8 [R,H,W], and the low-frequency windows of all four flips of
+    each, table [R,4,16,16,2] fp32 (flip order BP_FLIPS), computed once.  src: a directory of *.png (sorted) or a uint8
+    device tensor [R,H,W].  BandpassPool.get caches directory pools by (realpath, H, W, device)."""
+    _cache = {}
+
+    def __init__(self, src, H, W, device=None):
+        bandpass_check_dims(H, W)
+        self.H, self.W = int(H), int(W)
+        if isinstance(src, torch.Tensor):
+            if src.dtype != torch.uint8 or src.dim() != 3 or tuple(src.shape[1:]) != (H, W) or src.shape[0] < 1:
+                raise ValueError("BandpassPool: expected uint8 [R,%d,%d], got %s %s" % (H, W, src.dtype, tuple(src.shape)))
+            _require_cuda(src)
+            self.files, self.path = None, None
+            self.images = src.contiguous()
+        else:
+            self.path = str(src)
+            self.files, host = read_real_frames(self.path, H, W)
+            if device is None:
+                if not torch.cuda.is_available():
+                    raise RuntimeError("BandpassPool: the band-pass mix-up runs on the GPU (no CPU fallback)")
+                device = torch.device("cuda", torch.cuda.current_device())
+            self.images = torch.from_numpy(host).to(device)
+        self.n_real = int(self.images.shape[0])
+        dev = self.images.device
+        win = torch.empty((len(BP_FLIPS), self.n_real, 16, 16, 2), dtype=torch.float32, device=dev)
+        ws = torch.empty(L.spnet_bandpass_ws(self.n_real, H, W), device=dev)
+        for fi, code in enumerate(BP_FLIPS):
+            flip = torch.full((self.n_real,), code, dtype=torch.int32, device=dev)
+            L.spnet_bandpass_project(self.images.data_ptr(), 0, self.n_real, H, W, flip.data_ptr(), win[fi].data_ptr(),
+                                     ws.data_ptr(), _stream())
+        self.table = win.transpose(0, 1).contiguous()
+        torch.cuda.current_stream(dev).synchronize()       # flip / ws are released on return
+        self.mixer = BandpassMixer(self)
+
+    @classmethod
+    def get(cls, src, H, W, device=None):
+        if isinstance(src, cls):
+            return src
+        if isinstance(src, torch.Tensor):
+            return cls(src, H, W, device)
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+        key = (os.path.realpath(str(src)), int(H), int(W), str(device))
+        pool = cls._cache.get(key)
+        if pool is None:
+            pool = cls._cache[key] = cls(src, H, W, device)
+        return pool
+
+
+class BandpassMixer:
+    """draw(n, seeds=None) -> parameters (host, reference RNG order); apply(params, frames, ...) mixes frames [n,H,W]
+    (or [n,H,W,1]) on the device: one packed upload of the parameters, four launches (csrc/bandpass.hip)."""
+
+    def __init__(self, pool):
+        self.pool = pool
+        self._upload = None
+
+    def draw(self, n, seeds=None):
+        return draw_bandpass_batch(self.pool.n_real, n, seeds)
+
+    def apply(self, params, frames, out_f=None, out_u8=None, units="pixel"):
+        """frames: uint8, or float32 in `units` ("pixel" 0..255 | "network" [-1,1]); out_f (float32, same units) and / or
+        out_u8 (uint8, round half to even) receive the mixed frames (either may be `frames` itself)."""
+        pool = self.pool
+        n = len(params["row"])
+        if frames.shape[0] != n or frames.numel() != n * pool.H * pool.W:
+            raise ValueError("BandpassMixer.apply: frames %s do not hold %d frames of %dx%d" % (tuple(frames.shape), n,
+                                                                                           pool.H, pool.W))
+        if out_f is None and out_u8 is None:
+            raise ValueError("BandpassMixer.apply: no output")
+        for o, dt in ((out_f, torch.float32), (out_u8, torch.uint8)):
+            if o is not None and (o.dtype != dt or o.numel() != frames.numel() or not o.is_contiguous()):
+                raise ValueError("BandpassMixer.apply: output must be contiguous %s of %d elements" % (dt, frames.numel()))
+        if not frames.is_contiguous():
+            raise ValueError("BandpassMixer.apply: frames must be contiguous")
+        if frames.dtype == torch.uint8:
+            kind = 0
+        elif frames.dtype == torch.float32:
+            kind = 2 if units == "network" else 1
+        else:
+            raise ValueError("BandpassMixer.apply: frames must be uint8 or float32, got %s" % frames.dtype)
+        _require_cuda(frames)
+        if n == 0:
+            return
+        dev = frames.device
+        if self._upload is None:
+            self._upload = L.AsyncUploader(dev)
+        packed = self._upload("bp", np.concatenate([np.asarray(params["row"], np.int32),
+                                                    np.asarray(params["s"], np.float32).view(np.int32)]))
+        row, s = packed[:n], packed[n:].view(torch.float32)
+        ws = torch.empty(L.spnet_bandpass_ws(n, pool.H, pool.W), device=dev)
+        self._keep = (packed, ws)
+        L.spnet_bandpass_apply(frames.data_ptr(), kind, None, n, n, pool.H, pool.W, pool.table.data_ptr(), 4 * pool.n_real,
+                               row.data_ptr(), s.data_ptr(), L.ptr(out_f), int(units == "network"), L.ptr(out_u8),
+                               ws.data_ptr(), _stream())
+
+
+def bandpass_mixup(img_in, path_real=BP_DEFAULT_PATH):
+    """Reference signature (augmentation.py:10-62): replace the 16 x 16 lowest spatial frequencies of the fake frame
+    img_in with those of a random, randomly flipped real frame from path_real scaled by 3 * rand, take the magnitude of
+    the inverse transform and min-max normalise it to 0..255 (a constant becomes 0).  Exactly the reference's three RNG
+    calls (draw_bandpass).  img_in: numpy array or device tensor, [H,W], [H,W,1] or [H,W,3] (BGR); returns float32 of the
+    same kind and shape.
+
+    Fixed reference bugs: the real files are SORTED (glob order is unspecified); [H,W,1] (the generator's own frame
+    shape; rows, cols = img_in.shape raised) is accepted and returned as [H,W,1]; [H,W,3] is reduced with cv2's float
+    BGR2GRAY weights and the result replicated to 3 channels (the reference's cvCvtColor is a NameError); an empty or
+    missing directory raises FileNotFoundError naming it (not IndexError); a real image of another size raises ValueError
+    naming the file; frames smaller than 16 x 16 raise ValueError."""
+    is_t = isinstance(img_in, torch.Tensor)
+    shape = tuple(img_in.shape)
+    if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] not in (1, 3)):
+        raise ValueError("bandpass_mixup: expected [H,W], [H,W,1] or [H,W,3], got %s" % (shape,))
+    H, W = shape[0], shape[1]
+    bandpass_check_dims(H, W)
+    if is_t:
+        _require_cuda(img_in)
+        dev = img_in.device
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError("bandpass_mixup runs on the GPU (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    pool = BandpassPool.get(path_real, H, W, dev)
+    params = pool.mixer.draw(1)
+    x = img_in if is_t else torch.from_numpy(np.ascontiguousarray(img_in)).to(dev)
+    if len(shape) == 3 and shape[2] == 3:
+        x = x.to(torch.float32)
+        x = (x[..., 0] * BGR2GRAY[0] + x[..., 1] * BGR2GRAY[1]) + x[..., 2] * BGR2GRAY[2]
+    elif len(shape) == 3:
+        x = x[..., 0]
+    if x.dtype != torch.uint8:
+        x = x.to(torch.float32)
+    x = x.contiguous().reshape(1, H, W)
+    out = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    pool.mixer.apply(params, x, out_f=out)
+    out = out[0]
+    if len(shape) == 3:
+        out = out[..., None].expand(H, W, shape[2]).contiguous()
+    return out if is_t else out.cpu().numpy()

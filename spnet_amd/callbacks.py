@@ -91,9 +91,13 @@ class AugmentOnTheFly(Callback):
     tensor) or already a device tensor.  The augmented set is a second device tensor that the model's
     fit() reads batches from (`model.set_train_frames`)."""
 
-    def __init__(self, X, Y, orig_img_shape=(384, 512), aug_every=1, chunk=256, seed=1, real_blur=False):
+    def __init__(self, X, Y, orig_img_shape=(384, 512), aug_every=1, chunk=256, seed=1, real_blur=False,
+                 bandpass_real=None, bpmix_prob=0.3):
         """real_blur=False reproduces the reference, whose Gaussian blur is a no-op (the result of cv2.GaussianBlur is
-        discarded, augmentation.py:66-70); True applies it (train_spnet.py --augment_blur)."""
+        discarded, augmentation.py:66-70); True applies it (train_spnet.py --augment_blur).
+        bandpass_real: directory of real *.png frames of the training frames' size -- after the blur, a frame is
+        band-pass mixed with probability bpmix_prob (bp_mixup, callbacks.py:311-315, whose call the reference has
+        commented out; train_spnet.py --bp_real / --bpmix_prob).  None (default): off."""
         super().__init__()
         import torch
         from . import parallel
@@ -107,7 +111,8 @@ class AugmentOnTheFly(Callback):
         dev = parallel.local_device()
         self.X_orig = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X)).to(dev)
         self.X_aug = self.X_orig.clone()      # rows no epoch has augmented yet hold the pristine frame, not garbage
-        self.augmenter = DeviceAugmenter(self.X_orig, real_blur=real_blur)
+        self.augmenter = DeviceAugmenter(self.X_orig, real_blur=real_blur, bandpass_real=bandpass_real,
+                                         bpmix_prob=bpmix_prob)
 
     def set_model(self, model):
         super().set_model(model)

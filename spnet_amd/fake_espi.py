@@ -8,6 +8,10 @@ bands (draw_waves :60-80), 1..7 non-overlapping ringed ellipses (draw_antinodes 
 one numpy RandomState per frame: checked against oracle/espi_ref.py, which is pinned to the reference's own
 draws), the pixels are statistically, not bitwise, OpenCV's.  Exactly one PNG per CSV is written (the reference also writes
 a *_bp.png that would trip build_dataset's file-count assertion, utils.py:455-459).
+
+The band-pass mix-up with real frames (gen_fake_espi.py:266-271) is opt-in: generate_device(bandpass_real=...) returns
+the mixed frames, write_dataset(bandpass_real=..., bp_path=...) writes them as a dataset of their own.  Its draws come
+from per-frame streams derived from (not equal to) the frame seeds: deterministic in (n, seed), independent of `chunk`.
 """
 import os
 
@@ -129,15 +133,30 @@ def frame_seeds(n, seed):
     return [seed * 1000003 + i for i in range(n)]
 
 
-def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk=1024, count_range=(1, 7)):
+def bandpass_seeds(n, seed):
+    """Seeds of the per-frame band-pass draws: a hash of the frame seed, not the seed itself (the frame's own streams
+    stay as they are)."""
+    return [((s * 2654435761) ^ 0x5BD1E995) % (2 ** 32) for s in frame_seeds(n, seed)]
+
+
+def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk=1024, count_range=(1, 7),
+                    bandpass_real=None):
     """n frames rasterised directly in HBM (csrc/espi.hip): the SAME per-frame parameters as generate(n, seed)
     (so the labels are identical), pixels from the analytic device rasteriser, sensor noise / dropout from a
-    counter-based RNG.  Returns (float32 device tensor [n,384,512,1] in [-1,1], label rows[, uint8 device tensor])."""
+    counter-based RNG.  Returns (float32 device tensor [n,384,512,1] in [-1,1], label rows[, uint8 device tensor]).
+    bandpass_real (directory of real 512x384 *.png, or a BandpassPool): the frames are band-pass mixed
+    (augmentation.bandpass_mixup) -- the uint8 frame is the mixed one rounded as cv2.imwrite does, X is derived from it
+    exactly as reading that PNG back would give."""
     import torch
     from . import _lib as L
     dev = torch.device(device)
+    mixer = bp = None
+    if bandpass_real is not None:
+        from .augmentation import BandpassPool
+        mixer = BandpassPool.get(bandpass_real, IM_H, IM_W, dev).mixer
+        bp = mixer.draw(n, seeds=bandpass_seeds(n, seed))
     X = torch.empty((n, IM_H, IM_W, 1), dtype=torch.float32, device=dev)
-    U = torch.empty((n, IM_H, IM_W), dtype=torch.uint8, device=dev) if want_u8 else None
+    U = torch.empty((n, IM_H, IM_W), dtype=torch.uint8, device=dev) if (want_u8 or mixer is not None) else None
     labels = []
     st = torch.cuda.current_stream(dev).cuda_stream
     for lo in range(0, n, chunk):
@@ -157,6 +176,9 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
         L.spnet_fake_espi(wd.data_ptr(), ndd.data_ptr(), nnd.data_ptr(), hi - lo, IM_H, IM_W,
                           (seed * 2654435761 + lo * 97 + 12345) & 0xFFFFFFFF, int(bool(noise)), X[lo:hi].data_ptr(),
                           U[lo:hi].data_ptr() if U is not None else None, st)
+        if mixer is not None:
+            mixer.apply({k: v[lo:hi] for k, v in bp.items()}, U[lo:hi], out_u8=U[lo:hi])
+            L.spnet_u8_to_input(U[lo:hi].data_ptr(), X[lo:hi].data_ptr(), (hi - lo) * IM_H * IM_W, st)
         torch.cuda.current_stream(dev).synchronize()       # wd / ndd / nnd are freed on return
     return (X, labels, U) if want_u8 else (X, labels)
 
@@ -216,8 +238,13 @@ def to_network_input(X_u8):
     return x[..., None]
 
 
-def write_dataset(path, n, seed=0, start=0):
-    """steelpan_NNNNNNN.png + .csv pairs under `path` (the layout build_dataset reads)."""
+def write_dataset(path, n, seed=0, start=0, bandpass_real=None, bp_path=None, chunk=256):
+    """steelpan_NNNNNNN.png + .csv pairs under `path` (the layout build_dataset reads).  bandpass_real (directory of real
+    512x384 *.png) with bp_path: also the band-pass mixed frames, steelpan_NNNNNNN_bp.png + steelpan_NNNNNNN_bp.csv
+    (the same labels) under bp_path -- a dataset of its own: the reference writes the _bp.png beside the frame
+    (gen_fake_espi.py:269-271), which build_dataset's PNG / CSV count assertion rejects."""
+    if (bandpass_real is None) != (bp_path is None):
+        raise ValueError("write_dataset: bandpass_real and bp_path go together")
     os.makedirs(path, exist_ok=True)
     X, labels = generate(n, seed)
     for i in range(n):
@@ -225,4 +252,21 @@ def write_dataset(path, n, seed=0, start=0):
         Image.fromarray(X[i]).save(stem + ".png")
         with open(stem + ".csv", "w") as f:
             f.write(rows_to_csv(labels[i]))
+    if bandpass_real is not None:
+        import torch
+        from .augmentation import BandpassPool
+        os.makedirs(bp_path, exist_ok=True)
+        mixer = BandpassPool.get(bandpass_real, IM_H, IM_W).mixer
+        bp = mixer.draw(n, seeds=bandpass_seeds(n, seed))
+        dev = mixer.pool.images.device
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            u = torch.from_numpy(X[lo:hi]).to(dev)
+            mixer.apply({k: v[lo:hi] for k, v in bp.items()}, u, out_u8=u)
+            mixed = u.cpu().numpy()
+            for i in range(lo, hi):
+                stem = os.path.join(bp_path, "steelpan_" + str(start + i).zfill(7) + "_bp")
+                Image.fromarray(mixed[i - lo]).save(stem + ".png")
+                with open(stem + ".csv", "w") as f:
+                    f.write(rows_to_csv(labels[i]))
     return X, labels

@@ -476,6 +476,47 @@ int spnet_bandpass_apply(const void* x, int x_kind, const int* sel, int n_src, i
                          int n_table, const int* row, const float* s, float* out_f, int f_kind, unsigned char* out_u8,
                          float* ws, void* stream);
 
+/* ---- keras DenseNet121 (csrc/densenet.hip, gemm.hip; call site spnet/models.py:357-359 with cf.basemodel = 'DenseNet121') */
+/* Y[M,N] (row stride ldy) = relu(x[:, :K]*scale + shift) W[K,N]: BatchNorm + ReLU of the block's Concatenate buffer (pixels
+ * ldx floats apart) applied while the A tile is staged.  coef = [scale | unused | shift], cld floats each, zero beyond
+ * channel K-1 (spnet_dense_coeffs writes it).  colstats / stat_rows (or NULL / NULL) as spnet_gemm_f32_colstats. */
+int spnet_gemm_f32_bnrelu(const float* x, int ldx, const float* coef, int cld, const float* W, int ldw, float* Y, int ldy,
+                          int M, int N, int K, int tile, float* colstats, int* stat_rows, void* stream);
+/* ZeroPadding2D: backward = 0 pads x [B][H][W][C] into [B][H+pt+pb][W+pl+pr][C]; backward = 1 crops such a tensor back. */
+int spnet_pad_nhwc(const float* in, float* out, int B, int H, int W, int C, int pt, int pb, int pl, int pr, int backward,
+                   void* stream);
+/* ZeroPadding2D(3) + Conv2D(64, 7, strides 2, valid) on the 3-channel stem output (conv1/conv): op 0 fwd (a = x, b = w),
+ * 1 data gradient (a = dy, b = w), 2 weight gradient (a = x, b = dy; workspace >= spnet_dense_conv7_ws floats).  H, W:
+ * the input plane; output (H-1)/2+1 x (W-1)/2+1. */
+long spnet_dense_conv7_ws(int B, int H, int W);
+int spnet_dense_conv7(int op, const float* a, const float* b, float* out, int B, int H, int W, float* workspace,
+                      long ws_floats, void* stream);
+/* Column sums (sum, sum of squares) of x [M][C] (row stride ldx) as partial[spnet_dense_rows(M)][2][C] rows, the input of
+ * spnet_bn_finalize_fwd: the batch statistics of a dense block's input channels. */
+long spnet_dense_rows(long M);
+int spnet_dense_colsums_ld(const float* x, long ldx, long M, int C, float* partial, void* stream);
+/* Affine of one consumer BatchNorm over channels [0, c) as coef = [scale | 0 | shift] (cld floats each, zero from c on):
+ * training = 1 from the shared batch statistics (mean, invstd) + moving update of (mm, mv) towards (bmean, bvar);
+ * training = 0 from (mm, mv). */
+int spnet_dense_coeffs(int c, int cld, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                       const float* bmean, const float* bvar, float* mm, float* mv, float* coef, float eps, float momentum,
+                       int training, void* stream);
+/* y = act(scale*x + shift) over C channels (act 0 none, 1 ReLU), strided input and output. */
+int spnet_dense_apply_ld(const float* x, long ldx, long M, int C, const float* coef, int cld, int relu, float* y, long ldy,
+                         void* stream);
+/* Consumer backward: g = dz * [scale*x + shift > 0] (relu) | dz; G[:, :c] += gamma*g; partial[spnet_dense_rows(M)][2][c]
+ * = (sum g, sum g*x^).  spnet_dense_consumer_fin: dbeta = sum g, dgamma = sum g*x^, u += gamma*dbeta, v += gamma*dgamma. */
+int spnet_dense_consumer_bwd(const float* dz, long ldz, const float* x, long ldx, long M, int c, const float* coef, int cld,
+                             const float* mean, const float* invstd, const float* gamma, int relu, float* G, long ldg,
+                             float* partial, void* stream);
+int spnet_dense_consumer_fin(const float* partial, int P, int c, const float* gamma, float* dgamma, float* dbeta, float* u,
+                             float* v, void* stream);
+/* Producer finalize: out[:, j - c0] = invstd*(G - u/M - x^*v/M) for c0 <= j < c1 (the summed BatchNorm backward of every
+ * consumer of those channels). */
+int spnet_dense_producer_fin(const float* G, long ldg, const float* u, const float* v, const float* x, long ldx,
+                             const float* mean, const float* invstd, long M, int c0, int c1, float* out, long ldo,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

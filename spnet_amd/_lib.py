@@ -139,6 +139,17 @@ _SIGS = {
     "spnet_bandpass_ws": (c_long, [c_int, c_int, c_int]),
     "spnet_bandpass_project": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
     "spnet_bandpass_apply": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, P, P, P]),
+    "spnet_gemm_f32_bnrelu": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "spnet_pad_nhwc": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "spnet_dense_conv7_ws": (c_long, [c_int, c_int, c_int]),
+    "spnet_dense_conv7": (c_int, [c_int, P, P, P, c_int, c_int, c_int, P, c_long, P]),
+    "spnet_dense_rows": (c_long, [c_long]),
+    "spnet_dense_colsums_ld": (c_int, [P, c_long, c_long, c_int, P, P]),
+    "spnet_dense_coeffs": (c_int, [c_int, c_int, P, P, P, P, P, P, P, P, P, c_float, c_float, c_int, P]),
+    "spnet_dense_apply_ld": (c_int, [P, c_long, c_long, c_int, P, c_int, c_int, P, c_long, P]),
+    "spnet_dense_consumer_bwd": (c_int, [P, c_long, P, c_long, c_long, c_int, P, c_int, P, P, P, c_int, P, c_long, P, P]),
+    "spnet_dense_consumer_fin": (c_int, [P, c_int, c_int, P, P, P, P, P, P]),
+    "spnet_dense_producer_fin": (c_int, [P, c_long, P, P, P, c_long, P, P, c_long, c_int, c_int, P, c_long, P]),
 }
 
 EXPORTS = tuple(_SIGS)

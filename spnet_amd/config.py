@@ -17,7 +17,8 @@ loss_type = 'same'
 # 'monolithic' (default): frames resized to 331x331; 'big': native 384x512 frames;
 # 'simple' / 'compound' / 'ss': legacy head variants of the reference (config.py:42-48)
 model_type = 'monolithic'
-# backbone selector (config.py:50-52); this build implements 'Xception'
+# backbone selector (config.py:50-52); this build implements 'Xception', 'MobileNet', 'InceptionResNetV2' and
+# 'DenseNet121'
 basemodel = 'Xception'
 
 

@@ -43,6 +43,8 @@
 // tile t % tiles_n, so the extra stores are spread evenly over the workgroups that stage that row tile.
 // (blended kernels of the small tiles are held to 3 workgroups per CU like their plain counterparts: the middle
 // flow's 768-workgroup launches are exactly one resident wave of 3 per CU)
+// AX = 2: the A operand is relu(a[k]*A_ + c[k]) of ONE tensor (TileStage::xform_relu; X2 unused, coefficient row b
+// unused): BatchNorm + ReLU applied while the tile is staged, the pre-activation 1x1 convolution of keras DenseNet.
 
 
 // N x { one MFMA, PER instructions of class MASK } for the instruction scheduler
@@ -207,13 +209,15 @@ __global__ __launch_bounds__(256, (AX && BM * BN <= 96 * 64) ? 3 : 2) void gemm_
       if (tid < CFT) *reinterpret_cast<float4*>(cfs + slot * CFS + tid * 4) = cfreg;
   };
   auto fetch = [&](auto& stA, auto& stB, int k0, auto& wreg) {      // any tile: predicated
-    if constexpr (AX) stA.load2(A, X2, lda, m0, M, k0, kend, tid, wreg);
+    if constexpr (AX == 1) stA.load2(A, X2, lda, m0, M, k0, kend, tid, wreg);
     else if constexpr (AG) gather_a(stA, k0);
     else stA.load(A, lda, m0, M, k0, kend, tid);
     stB.load(B, ldb, n0, N, k0, kend, tid);
   };
   auto blend = [&](auto& stA, int k0, auto& wreg, const float4 a, const float4 b, const float4 c) {
-    if constexpr (AX) {
+    if constexpr (AX == 2) {
+      stA.xform_relu(a, c);
+    } else if constexpr (AX) {
       stA.xform(a, b, c, wreg);
       if (dy_out && ((k0 - kbeg) / BK) % tiles_n == tn) stA.store_global(dy_out, lda, m0, M, k0, kend, tid);
     }
@@ -255,7 +259,7 @@ __global__ __launch_bounds__(256, (AX && BM * BN <= 96 * 64) ? 3 : 2) void gemm_
   const long boff = (BMAJ == SP_K_MAJOR ? (long)kbeg : (long)kbeg * ldb) + (PIPE ? 4 : 2) * SB::kstep(ldb);
   const float* Ak = A + aoff;
   const float* Bk = B + boff;
-  const float* Xk = AX ? X2 + aoff : nullptr;      // second tensor of the blended operand
+  const float* Xk = (AX == 1) ? X2 + aoff : nullptr;      // second tensor of the blended operand
   // Plain (AX = 0) kernels: the main loop is an explicit software pipeline over the two 16-deep chunks of a K tile.
   // Per step t (LDS buffer cur = t & 1 holds tile t; two register stages, stage t & 1 holds tile t+2):
   //   first half    fragments of chunk 1 (cur) -> set 1  |  MFMAs of chunk 0 on set 0
@@ -353,13 +357,13 @@ __global__ __launch_bounds__(256, (AX && BM * BN <= 96 * 64) ? 3 : 2) void gemm_
       if (FULL || t + 2 < nt) cf_fetch(kbeg + (t + 2) * BK);
     }
     if (FULL) {
-      if constexpr (AX) sa[PAR].load_full2(Ak, Xk, wsh);
+      if constexpr (AX == 1) sa[PAR].load_full2(Ak, Xk, wsh);
       else if constexpr (AG) gather_a(sa[PAR], kbeg + (t + 2) * BK);
       else sa[PAR].load_full(Ak);
       sb[PAR].load_full(Bk);
       Ak += SA::kstep(lda);
       Bk += SB::kstep(ldb);
-      if constexpr (AX) Xk += SA::kstep(lda);
+      if constexpr (AX == 1) Xk += SA::kstep(lda);
     } else if (t + 2 < nt) {
       fetch(sa[PAR], sb[PAR], kbeg + (t + 2) * BK, wsh);
     }
@@ -508,6 +512,9 @@ static int launch_tile(const float* A, int amaj, int lda, const float* B, int bm
   } else if (xf == 1) {
     if (amaj == SP_K_MAJOR && bmaj == SP_OUT_MAJOR) SP_LAUNCH(SP_BK, SP_K_MAJOR, SP_OUT_MAJOR, 1, 0);
     else return (int)hipErrorInvalidValue;
+  } else if (xf == 2) {
+    if (amaj == SP_K_MAJOR && bmaj == SP_OUT_MAJOR) SP_LAUNCH(SP_BK, SP_K_MAJOR, SP_OUT_MAJOR, 2, 0);
+    else return (int)hipErrorInvalidValue;
   } else if (amaj == SP_K_MAJOR && bmaj == SP_OUT_MAJOR) SP_LAUNCH_P(SP_K_MAJOR, SP_OUT_MAJOR);
   else if (amaj == SP_K_MAJOR && bmaj == SP_K_MAJOR) SP_LAUNCH_P(SP_K_MAJOR, SP_K_MAJOR);
   else if (amaj == SP_OUT_MAJOR && bmaj == SP_OUT_MAJOR) SP_LAUNCH_P(SP_OUT_MAJOR, SP_OUT_MAJOR);
@@ -632,7 +639,8 @@ static int gemm_impl(const float* A, int a_major, int lda, const float* B, int b
   if (a_major == SP_OUT_MAJOR && (M & 3)) return (int)hipErrorInvalidValue;
   if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return (int)hipErrorInvalidValue;
   if (xf) {   // blended A operand: second tensor + [a|b|c] coefficients, zero-padded to whole K tiles; no K split
-    if (xf != 1 || batch || !X2 || !coef || (((uintptr_t)X2 | (uintptr_t)coef | (uintptr_t)dy_out) & 15) || (cld & 3))
+    if ((xf != 1 && xf != 2) || batch || (xf == 1 && !X2) || !coef ||
+        (((uintptr_t)X2 | (uintptr_t)coef | (uintptr_t)dy_out) & 15) || (cld & 3) || (xf == 2 && dy_out))
       return (int)hipErrorInvalidValue;
     if (cld < spnet_cdiv(K, SP_BK) * SP_BK) return (int)hipErrorInvalidValue;
     split_k = 1;
@@ -641,7 +649,9 @@ static int gemm_impl(const float* A, int a_major, int lda, const float* B, int b
   const int form = (a_major == SP_OUT_MAJOR) ? 2 : (b_major == SP_K_MAJOR ? 1 : 0);
   if (tile <= 0 || tile > SP_NTILES)
     tile = pick_tile(form, M, N, K, split_k, workspace != nullptr, ws_floats, batch ? nbatch : 1);
-  if (xf && auto_tile && tile == 1) tile = 8;     // the blended 128x128 kernel does not fit the register file
+  // the two-tensor blended 128x128 kernel does not fit the register file (it spills); the one-tensor BN+ReLU form (xf 2:
+  // 248 VGPRs, no scratch) keeps it -- a 128x96 tile would waste a third of every N = 128 problem of DenseNet
+  if (xf == 1 && auto_tile && tile == 1) tile = 8;
   int bm, bn;
   tile_dims(tile, &bm, &bn);
   const long tiles = (long)spnet_cdiv(M, bm) * spnet_cdiv(N, bn);
@@ -761,6 +771,19 @@ extern "C" int spnet_gemm_f32_bnblend(const float* g, const float* yp, const flo
                                       float* dy_out, void* stream) {
   return gemm_impl(g, SP_K_MAJOR, lda, B, SP_OUT_MAJOR, ldb, C, ldc, M, N, K, 1, nullptr, 0, nullptr, tile, nullptr,
                    nullptr, stream, nullptr, 0, 1, yp, coef, cld, dy_out);
+}
+
+// Y[M,N] (row stride ldy) = relu(x[:, :K]*scale + shift) W[K,N] with the BatchNorm + ReLU of every input channel applied
+// while the A tile is staged (AX = 2): the pre-activation 1x1 convolutions of keras DenseNet121 read the first K
+// channels of their block's Concatenate buffer (pixels ldx floats apart) and the BN+ReLU output is never written.
+// coef = [scale | (unused) | shift], cld floats each, zero beyond channel K-1 (cld a multiple of 32 covering K).
+// colstats / stat_rows (or NULL / NULL): BatchNorm column sums of Y as spnet_gemm_f32_colstats.
+extern "C" int spnet_gemm_f32_bnrelu(const float* x, int ldx, const float* coef, int cld, const float* W, int ldw,
+                                     float* Y, int ldy, int M, int N, int K, int tile, float* colstats, int* stat_rows,
+                                     void* stream) {
+  if (!x || !W || !Y || (!colstats) != (!stat_rows) || ldx < K) return (int)hipErrorInvalidValue;
+  return gemm_impl(x, SP_K_MAJOR, ldx, W, SP_OUT_MAJOR, ldw, Y, ldy, M, N, K, 1, nullptr, 0, nullptr, tile, colstats,
+                   stat_rows, stream, nullptr, 0, 2, nullptr, coef, cld, nullptr);
 }
 
 // Forward-form GEMM that also emits BatchNorm column statistics of C: colstats[rows][2][N] holds per

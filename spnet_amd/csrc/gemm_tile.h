@@ -93,6 +93,19 @@ struct TileStage {
       v[i].w = fmaf(a.w, v[i].w, fmaf(b.w, w[i].w, c.w));
     }
   }
+  // v <- relu(a*v + c) (XF = 2: the BatchNorm + ReLU of the operand's producer applied on load -- keras DenseNet's
+  // pre-activation 1x1 convolutions read their Concatenate buffer through it; a = scale, c = shift, zero past the last
+  // channel, so out-of-range reduction steps stay zero).
+  __device__ __forceinline__ void xform_relu(const float4 a, const float4 c) {
+    static_assert(MAJ == SP_K_MAJOR && 256 % (BK / 4) == 0, "K-major operands only");
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      v[i].x = fmaxf(fmaf(a.x, v[i].x, c.x), 0.f);
+      v[i].y = fmaxf(fmaf(a.y, v[i].y, c.y), 0.f);
+      v[i].z = fmaxf(fmaf(a.z, v[i].z, c.z), 0.f);
+      v[i].w = fmaxf(fmaf(a.w, v[i].w, c.w), 0.f);
+    }
+  }
   // The (blended) tile as it stands in v[] -> out[row*ld + k] (K-major operands): only real rows / reduction steps.
   __device__ __forceinline__ void store_global(float* __restrict__ out, int ld, int r0, int R, int k0, int kend,
                                                int tid) const {

@@ -28,6 +28,7 @@ BN_EPS = 1e-3
 BN_MOMENTUM = 0.99
 L2_COEF = 1e-4
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_RELU6 = 0, 1, 2, 3
+BACKBONES = ("Xception", "MobileNet", "InceptionResNetV2", "DenseNet121")      # cf.basemodel values this build implements
 # keras.applications.mobilenet.MobileNet(alpha=1): (pointwise filters, depthwise stride) of conv_dw/pw_1..13
 MOBILENET_BLOCKS = [(64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2), (512, 1), (512, 1), (512, 1), (512, 1),
                     (512, 1), (1024, 2), (1024, 1)]
@@ -303,6 +304,15 @@ def param_specs(H, W, n_out=576, backbone="Xception"):
         if h < 1 or w < 1:
             raise ValueError("frames of %dx%d are too small for InceptionResNetV2 (needs >= 150x150)" % (H, W))
         specs.append(("FinalOutput/kernel", (h * w * 1536, n_out), True, True))
+        specs.append(("FinalOutput/bias", (n_out,), True, False))
+        return specs
+    if backbone == "DenseNet121":
+        from .densenet import densenet_out_hw, densenet_param_specs
+        specs += densenet_param_specs()
+        h, w = densenet_out_hw(H, W)
+        if h < 1 or w < 1:
+            raise ValueError("frames of %dx%d are too small for DenseNet121 (needs >= 64x64)" % (H, W))
+        specs.append(("FinalOutput/kernel", (h * w * 1024, n_out), True, True))
         specs.append(("FinalOutput/bias", (n_out,), True, False))
         return specs
     if backbone == "MobileNet":
@@ -658,9 +668,8 @@ class Engine:
         # (start, step) of the output columns that pass through a sigmoid: the 'compound' head of the reference
         # (models.py:379-386) = one dense layer with sigmoid 'noobj' columns once InterleaveColumns has re-ordered them
         self.sigmoid_cols = sigmoid_cols
-        if backbone not in ("Xception", "MobileNet", "InceptionResNetV2"):
-            raise NotImplementedError("backbone %r: this build implements Xception, MobileNet and InceptionResNetV2"
-                                      % (backbone,))
+        if backbone not in BACKBONES:
+            raise NotImplementedError("backbone %r: this build implements %s" % (backbone, ", ".join(BACKBONES)))
         self.backbone = backbone
         self.dev = torch.device(device)
         self.loss_type = loss_type
@@ -670,6 +679,7 @@ class Engine:
         self._pw_layers = []            # every Pointwise of this plan (their bf16x3 weight planes: WeightSet.need_planes)
         self._bns = []                  # every BN of this plan (their inference coefficients: refresh)
         self._irv2 = None               # the IRv2Backbone node, if any (its gathered group operands: refresh)
+        self._densenet = None           # the DenseNetBackbone node, if any
         self.deferred_wgrads = []       # (x, dy, gw, cin, cout, M) of layers whose dW waits for the batched launch
         self.dw_reduce_jobs = []        # (partials, grad, rows, 9*C) of every depthwise layer
         self._dw_reduce_table = None
@@ -788,6 +798,11 @@ class Engine:
         if self.backbone == "InceptionResNetV2":
             net = IRv2Backbone(self, d.y); n.append(net)
             self._irv2 = net
+            self.backbone_out = net.y
+            return self._build_head(net.y)
+        if self.backbone == "DenseNet121":
+            from .densenet import DenseNetBackbone
+            net = DenseNetBackbone(self, d.y); n.append(net)
             self.backbone_out = net.y
             return self._build_head(net.y)
         # ---- Xception entry flow, block 1
@@ -1591,8 +1606,8 @@ class BN:
     reductions run inside OTHER kernels' epilogues and whose affine is applied by its consumers on load
     (the normalised tensor itself is only written when `apply()` is called)."""
 
-    def __init__(self, eng, C, M, name):
-        self.e, self.C, self.M = eng, C, M
+    def __init__(self, eng, C, M, name, eps=BN_EPS):
+        self.e, self.C, self.M, self.eps = eng, C, M, eps
         self.gamma, self.beta = eng.P(name + "/gamma"), eng.P(name + "/beta")
         self.mm, self.mv = eng.S(name + "/moving_mean"), eng.S(name + "/moving_variance")
         self.ss = eng.new(2 * C)                 # [scale | shift], valid after finalize()/infer()
@@ -1641,12 +1656,12 @@ class BN:
         e = self.e
         L.spnet_bn_finalize_fwd(e.ws_ptr(region), rows, self.M, self.C, L.ptr(self.gamma), L.ptr(self.beta),
                                 L.ptr(self.mm), L.ptr(self.mv), self.mean_ptr, self.invstd_ptr, L.ptr(self.ss),
-                                BN_EPS, BN_MOMENTUM, _stream())
+                                self.eps, BN_MOMENTUM, _stream())
 
     def infer(self):
         """scale|shift from the moving statistics (Engine.refresh, when the weights or statistics moved)"""
         L.spnet_bn_infer_coeffs(self.C, L.ptr(self.gamma), L.ptr(self.beta), L.ptr(self.mm), L.ptr(self.mv),
-                                L.ptr(self.ss), BN_EPS, _stream())
+                                L.ptr(self.ss), self.eps, _stream())
 
     def apply(self, x, y, act, residual=None):
         L.spnet_bn_apply(L.ptr(x), self.M, self.C, L.ptr(self.ss), act, L.ptr(residual), 0, L.ptr(y), _stream())

@@ -25,6 +25,9 @@ import numpy as np
 from . import config as cf
 from . import multi_gpu, utils  # noqa: F401  (same import surface as the reference module)
 
+# cf.basemodel values this build implements (keras.applications class names; spnet/config.py:50-52)
+BACKBONES = ('Xception', 'MobileNet', 'InceptionResNetV2', 'DenseNet121')
+
 lambda_center = 2.0
 lambda_size = 1.0
 lambda_angle = 3.0
@@ -167,6 +170,9 @@ def keras_layer_table(basemodel=None):
             else:
                 t.append((op[0], []))
         return t
+    if (basemodel or cf.basemodel) == 'DenseNet121':     # keras.applications.densenet layer order (Keras 2.1.3)
+        from .densenet import densenet_layers
+        return t + [(name, [prefix] if prefix else []) for name, _, prefix in densenet_layers()]
     if (basemodel or cf.basemodel) == 'MobileNet':       # keras.applications.mobilenet layer order
         t += [("conv1", ["conv1"]), ("conv1_bn", ["conv1_bn"]), ("conv1_relu", [])]
         for i in range(1, len(MOBILENET_BLOCKS) + 1):
@@ -207,9 +213,9 @@ class Model:
         # Select this rank's GPU (and join the torchrun process group) BEFORE anything is allocated: every plan,
         # callback buffer and kernel launch of this process then lives on cuda:LOCAL_RANK.
         self.rank, _, self.world = parallel.init_distributed()
-        if cf.basemodel not in ('Xception', 'MobileNet', 'InceptionResNetV2'):
-            raise NotImplementedError("this build implements the Xception, MobileNet and InceptionResNetV2 backbones "
-                                      "(cf.basemodel=%r)" % cf.basemodel)
+        if cf.basemodel not in BACKBONES:
+            raise NotImplementedError("this build implements the %s backbones (cf.basemodel=%r)"
+                                      % (", ".join(BACKBONES), cf.basemodel))
         self.basemodel = cf.basemodel
         self.input_shape = tuple(int(v) for v in input_shape)
         H, W = self.input_shape[0], self.input_shape[1]
@@ -275,7 +281,7 @@ class Model:
             r = self._root
             mask = torch.ones(r.n_theta, device=r.dev, dtype=torch.float32)
             for name, (off, n, _) in r.p_off.items():
-                if name.split("/")[0] in self._frozen_prefixes:
+                if name.split("/")[0] in self._frozen_prefixes or name.rsplit("/", 1)[0] in self._frozen_prefixes:
                     mask[off:off + n] = 0
             self._mask = mask
 
@@ -614,7 +620,7 @@ def load_model(path, custom_objects=None):
     try:                                   # head variant and backbone are part of the saved model, not of the caller's config
         if saved_type in ("compound", "monolithic", "big"):
             cf.model_type = saved_type
-        if meta.get("basemodel") in ("Xception", "MobileNet", "InceptionResNetV2"):
+        if meta.get("basemodel") in BACKBONES:
             cf.basemodel = meta["basemodel"]
         model = Model(shape, Y0size=int(meta.get("Y0size", 576)), freeze_fac=0.0)
     finally:

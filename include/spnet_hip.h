@@ -419,6 +419,16 @@ int spnet_adam_l2_sum(const float* sq_partial, int count, float l2, float* l2_lo
 /* uint8 grey levels -> float32 network input, dst = (src / 255 - 0.5) * 2 with numpy's float32 roundings (bit-identical
  * to the host conversion); n pixels, pointers 16-byte aligned.  Lets frames cross PCIe as bytes. */
 int spnet_u8_to_input(const unsigned char* src, float* dst, long n, void* stream);
+/* PIL.Image.resize((OW, OH), ANTIALIAS) of N one-channel uint8 frames [N][H][W] (spnet/utils.py:335-337), bit-identical to
+ * Pillow's 8-bit Lanczos resampler: horizontal pass, then vertical over its uint8 result, both in one launch (the
+ * intermediate lives in LDS).  xtab / ytab: int32 device tables [O][2 + taps] = (first input index, tap count, taps ...,
+ * zero padded) of spnet_amd/resize.py lanczos_taps(), |tap| < 2^23; a pass whose size does not change is skipped as Pillow
+ * skips it (its table is ignored and may be NULL).  out_u8 (or NULL): [N][OH][OW]; out_f (or NULL): the same frames as
+ * network input, == spnet_u8_to_input(out_u8); at least one.  Sizes 1 .. 2048, any W / OW, no alignment asked
+ * of src / out_u8 (a slice of frames is fine; out_f as a float).  hipErrorInvalidValue (nothing written) otherwise.
+ * Tables that are not lanczos_taps' of the size pair give wrong or unwritten pixels, never an out-of-range access. */
+int spnet_resize_u8(const unsigned char* src, int N, int H, int W, const int* xtab, int xtaps, const int* ytab, int ytaps,
+                    int OH, int OW, unsigned char* out_u8, float* out_f, void* stream);
 /* Batch assembly: dst[i][0..L) = src[index[i]][0..L), n rows of L floats (16 bytes per lane when L % 4 == 0 and both
  * buffers are 16-byte aligned, 4 otherwise), index int32 | int64 on the device (idx_bytes 4 | 8), clamped to [0, src_rows) -- the minibatch gather Keras' fit does on the host
  * (train_spnet.py:75,81: model.fit(X_train, Y_train, batch_size, shuffle=True)). */

@@ -16,8 +16,9 @@ default_image_dir = '/home/shawley/datasets/zooniverse_steelpan/'
 
 
 def predict_network(weights_file="spnet.model", datapath=default_image_dir, fraction=1.0, log_dir='logs/Predicting/',
-                    batch_size=16, model=None, X_pred='', u8_frames=False):
+                    batch_size=16, model=None, X_pred='', u8_frames=False, device_resize=False):
     img_file_list = []
+    resize = False
     if isinstance(X_pred, str) and X_pred == '':
         print(f"Getting data from {datapath}, fraction = {fraction}.")
         if cf.model_type == 'simple':
@@ -32,15 +33,19 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
         if batch_size is not None:
             total_load = nearest_multiple(total_load, batch_size)
         print("      Total files = ", total_files, ", going to load total_load = ", total_load)
+        # device_resize: the files' own grey levels travel, the GPU resizes them to force_dim (implies u8 frames; the
+        # 'big' layout has nothing to resize)
+        resize = bool(device_resize) and grayscale and force_dim is not None
         X_pred, _ = build_X(total_load, img_file_list, force_dim=force_dim, grayscale=grayscale,
-                            as_uint8=bool(u8_frames) and grayscale)
+                            as_uint8=(bool(u8_frames) or resize) and grayscale, device_resize=resize)
         print("")
 
     if model is None:
         print("Loading model from", weights_file)
         if '.hdf5' in weights_file:
             print("   Defining model, then loading weights")
-            model, _ = setup_model(X_pred, try_checkpoint=True, no_cp_fatal=True, weights_file=weights_file,
+            X_shape = np.empty((1, force_dim, force_dim, 1), np.float32) if resize else X_pred
+            model, _ = setup_model(X_shape, try_checkpoint=True, no_cp_fatal=True, weights_file=weights_file,
                                    parallel=False, freeze_fac=0.0, quick_setup=True)
         else:
             print("   Loading whole model")
@@ -49,7 +54,8 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
     m = X_pred.shape[0]
     print("    Predicting... (m = ", m, " frames in dataset)", sep="")
     start_time = time.time()
-    Y_pred = model.predict(X_pred, batch_size=batch_size)
+    Y_pred = model.predict(X_pred, batch_size=batch_size, resize=True) if resize else \
+        model.predict(X_pred, batch_size=batch_size)
     elapsed = time.time() - start_time
     print("    ...elapsed time to predict = ", elapsed, "s.   FPS = ", m * 1.0 / elapsed)
 
@@ -79,9 +85,12 @@ if __name__ == '__main__':
     p.add_argument('--u8_frames', action='store_true',
                    help="(additive) keep the decoded frames as uint8 and scale them to [-1,1] on the GPU: same "
                         "predictions, a quarter of the host-to-device bytes")
+    p.add_argument('--device_resize', action='store_true',
+                   help="(additive, implies --u8_frames) load the frames at their own size and resize them to the "
+                        "network's on the GPU, bit-identical to the PIL resize of the default path")
     args = p.parse_args()
     for attr, val in (("model_type", args.model_type), ("loss_type", args.loss_type)):
         if val is not None:
             setattr(cf, attr, val)
     predict_network(weights_file=args.weights, datapath=args.datapath, fraction=args.fraction, log_dir=args.logdir,
-                    batch_size=args.batch_size, u8_frames=args.u8_frames)
+                    batch_size=args.batch_size, u8_frames=args.u8_frames, device_resize=args.device_resize)

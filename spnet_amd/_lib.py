@@ -127,6 +127,7 @@ _SIGS = {
     "spnet_adam_part": (c_int, [P, P, P, P, c_long, c_long, c_float, c_float, c_float, c_float, c_float, c_float, P, P, P, P]),
     "spnet_adam_l2_sum": (c_int, [P, c_int, c_float, P, P]),
     "spnet_u8_to_input": (c_int, [P, P, c_long, P]),
+    "spnet_resize_u8": (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, P, P]),
     "spnet_gather_rows": (c_int, [P, c_long, P, c_int, P, c_int, c_long, P]),
     "spnet_minmax": (c_int, [P, c_int, c_long, P, P, P]),
     "spnet_cutout": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P]),

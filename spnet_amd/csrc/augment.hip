@@ -292,9 +292,6 @@ extern "C" int spnet_warp_affine_fixed(const float* src, float* dst, int N, int 
 // byte per pixel instead of four; the pass replaces the device-to-device copy into the plan's input buffer.
 // 16 pixels per thread step: one 16-byte load, four 16-byte stores (+ a scalar tail); both pointers 16-byte aligned.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float u8_to_input(unsigned v) {
-  return __fmul_rn(__fsub_rn(__fdiv_rn((float)v, 255.f), 0.5f), 2.f);
-}
 
 __global__ __launch_bounds__(256) void u8_to_input_kernel(const unsigned char* __restrict__ src8, float* __restrict__ dstf,
                                                           long n) {
@@ -307,11 +304,11 @@ __global__ __launch_bounds__(256) void u8_to_input_kernel(const unsigned char* _
     const unsigned w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      dst[i * 4 + k] = make_float4(u8_to_input(w[k] & 0xffu), u8_to_input((w[k] >> 8) & 0xffu),
-                                   u8_to_input((w[k] >> 16) & 0xffu), u8_to_input(w[k] >> 24));
+      dst[i * 4 + k] = make_float4(spnet_u8_to_input_f(w[k] & 0xffu), spnet_u8_to_input_f((w[k] >> 8) & 0xffu),
+                                   spnet_u8_to_input_f((w[k] >> 16) & 0xffu), spnet_u8_to_input_f(w[k] >> 24));
   }
   const long t = n16 * 16 + gtid;                    // the < 16 pixels past the last whole vector
-  if (t < n) dstf[t] = u8_to_input(src8[t]);
+  if (t < n) dstf[t] = spnet_u8_to_input_f(src8[t]);
 }
 
 extern "C" int spnet_u8_to_input(const unsigned char* src, float* dst, long n, void* stream) {

@@ -38,6 +38,12 @@ __device__ __forceinline__ float wave_min(float v) {
   return v;
 }
 
+// Input codec: uint8 grey level -> the network's float32 input, x = (v / 255 - 0.5) * 2 with every step rounded as numpy
+// rounds it on float32 (spnet/utils.py:340-342), so a pixel converted on the device has the host conversion's bits.
+__device__ __forceinline__ float spnet_u8_to_input_f(unsigned v) {
+  return __fmul_rn(__fsub_rn(__fdiv_rn((float)v, 255.f), 0.5f), 2.f);
+}
+
 // Keras' moving-statistics update, moving*momentum + value*(1 - momentum), with every product and the sum rounded on
 // its own (no fused multiply-add): the same bits from every kernel that performs it.
 __device__ __forceinline__ float bn_moving_update(float moving, float momentum, float value) {

@@ -140,13 +140,16 @@ def bandpass_seeds(n, seed):
 
 
 def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk=1024, count_range=(1, 7),
-                    bandpass_real=None):
+                    bandpass_real=None, size=None):
     """n frames rasterised directly in HBM (csrc/espi.hip): the SAME per-frame parameters as generate(n, seed)
     (so the labels are identical), pixels from the analytic device rasteriser, sensor noise / dropout from a
     counter-based RNG.  Returns (float32 device tensor [n,384,512,1] in [-1,1], label rows[, uint8 device tensor]).
     bandpass_real (directory of real 512x384 *.png, or a BandpassPool): the frames are band-pass mixed
     (augmentation.bandpass_mixup) -- the uint8 frame is the mixed one rounded as cv2.imwrite does, X is derived from it
-    exactly as reading that PNG back would give."""
+    exactly as reading that PNG back would give.
+    size (int or (OH, OW)): the frames are resized on the device as the input codec resizes them (PIL Lanczos, bit for
+    bit: resize.py) -- X is [n,OH,OW,1] and the uint8 frames [n,OH,OW], exactly what writing the PNGs and reading them
+    back through build_dataset at force_dim = size gives.  Labels stay in the 512x384 frame's coordinates."""
     import torch
     from . import _lib as L
     dev = torch.device(device)
@@ -155,8 +158,12 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
         from .augmentation import BandpassPool
         mixer = BandpassPool.get(bandpass_real, IM_H, IM_W, dev).mixer
         bp = mixer.draw(n, seeds=bandpass_seeds(n, seed))
-    X = torch.empty((n, IM_H, IM_W, 1), dtype=torch.float32, device=dev)
-    U = torch.empty((n, IM_H, IM_W), dtype=torch.uint8, device=dev) if (want_u8 or mixer is not None) else None
+    OH, OW = (IM_H, IM_W)
+    if size is not None:
+        from .resize import _size, resize_u8_device
+        OH, OW = _size(size)
+    X = torch.empty((n, OH, OW, 1), dtype=torch.float32, device=dev)
+    U = torch.empty((n, OH, OW), dtype=torch.uint8, device=dev) if (want_u8 or (mixer is not None and size is None)) else None
     labels = []
     st = torch.cuda.current_stream(dev).cuda_stream
     for lo in range(0, n, chunk):
@@ -173,13 +180,19 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
                 nodes[k, j, 7] = 1.0
             labels.append([node[:6] for node in nd])
         wd, ndd, nnd = (torch.from_numpy(a).to(dev) for a in (waves, nodes, nn))
+        if size is None:
+            Xc, Uc = X[lo:hi], (U[lo:hi] if U is not None else None)
+        else:               # the 384x512 uint8 frames of this chunk only; X / U receive them resized
+            Xc, Uc = None, torch.empty((hi - lo, IM_H, IM_W), dtype=torch.uint8, device=dev)
         L.spnet_fake_espi(wd.data_ptr(), ndd.data_ptr(), nnd.data_ptr(), hi - lo, IM_H, IM_W,
-                          (seed * 2654435761 + lo * 97 + 12345) & 0xFFFFFFFF, int(bool(noise)), X[lo:hi].data_ptr(),
-                          U[lo:hi].data_ptr() if U is not None else None, st)
+                          (seed * 2654435761 + lo * 97 + 12345) & 0xFFFFFFFF, int(bool(noise)), L.ptr(Xc), L.ptr(Uc), st)
         if mixer is not None:
-            mixer.apply({k: v[lo:hi] for k, v in bp.items()}, U[lo:hi], out_u8=U[lo:hi])
-            L.spnet_u8_to_input(U[lo:hi].data_ptr(), X[lo:hi].data_ptr(), (hi - lo) * IM_H * IM_W, st)
-        torch.cuda.current_stream(dev).synchronize()       # wd / ndd / nnd are freed on return
+            mixer.apply({k: v[lo:hi] for k, v in bp.items()}, Uc, out_u8=Uc)
+            if size is None:
+                L.spnet_u8_to_input(Uc.data_ptr(), Xc.data_ptr(), (hi - lo) * IM_H * IM_W, st)
+        if size is not None:
+            resize_u8_device(Uc, (OH, OW), out_f=X[lo:hi], out_u8=None if U is None else U[lo:hi])
+        torch.cuda.current_stream(dev).synchronize()       # wd / ndd / nnd (/ Uc) are freed on return
     return (X, labels, U) if want_u8 else (X, labels)
 
 

@@ -373,7 +373,7 @@ class Model:
         return self._uploaded[key][1]
 
     # -- inference --------------------------------------------------------------------------------
-    def predict(self, X, batch_size=32, verbose=0):
+    def predict(self, X, batch_size=32, verbose=0, resize=False):
         """model.predict(X, batch_size) (predict_spnet.py:85, evaluate_spnet.py:66): [N,576] float32.
 
         One static launch plan per batch size, replayed as a hipGraph (Engine.predict_step).  Host frames are STREAMED:
@@ -381,8 +381,21 @@ class Model:
         the whole set nor a second copy of it has to fit anywhere and the PCIe transfer hides behind the forward
         passes; device-resident frames are read in place.  uint8 frames -- host arrays or device tensors alike -- are grey
         levels 0..255 and are scaled to [-1,1] on the device (an addition of this build: Keras would cast them unscaled);
-        float frames are taken as they are."""
+        float frames are taken as they are.
+        resize=True (additive): X holds uint8 grey levels [N,h,w(,1)] of ANY size -- the camera's 384x512 frames -- and
+        each batch is resized to the model's H x W on the device as the input codec resizes on the host (Pillow's
+        Lanczos, bit for bit: spnet_amd/resize.py), straight into the plan's input buffer: the same predictions as
+        predict(build_X(..., force_dim=H)).  Host frames are streamed at their own size."""
         torch = _torch()
+        if resize:
+            if not ((isinstance(X, torch.Tensor) and X.dtype == torch.uint8) or
+                    (isinstance(X, np.ndarray) and X.dtype == np.uint8)):
+                raise TypeError("predict(resize=True) expects uint8 grey-level frames [N,h,w(,1)]")
+            if not (X.ndim == 3 or (X.ndim == 4 and X.shape[-1] == 1)):
+                raise ValueError("predict(resize=True) expects frames [N,h,w(,1)], got %s" % (tuple(X.shape),))
+            fh, fw = int(X.shape[1]), int(X.shape[2])
+        else:
+            fh, fw = self.H, self.W
         N = int(X.shape[0])
         bs = max(1, min(int(batch_size), max(N, 1)))
         eng = self._engine(bs, train=False)
@@ -403,7 +416,12 @@ class Model:
             the device exactly as the input codec scales them on the host (spnet_u8_to_input: utils.py:340-342) --
             the same frames give the same predictions whatever container they arrive in"""
             n = hi - lo
-            if frames.dtype == torch.uint8:
+            if resize:
+                from .resize import resize_u8_device
+                resize_u8_device(frames.reshape(n, fh, fw), (self.H, self.W), out_f=eng.x_in[:n])
+                if n < bs:                           # ragged tail: pad with the last frame, drop the extras
+                    eng.x_in[n:].copy_(eng.x_in[n - 1:n].expand(bs - n, -1, -1, -1))
+            elif frames.dtype == torch.uint8:
                 if frames.data_ptr() & 15:          # a slice of a resident uint8 tensor whose frame size is not a multiple of
                     frames = frames.clone()         # 16 bytes (331 x 331): the kernel wants 16-byte aligned bytes
                 L.spnet_u8_to_input(frames.data_ptr(), eng.x_in.data_ptr(), n * self.H * self.W, L.current_stream())
@@ -429,13 +447,13 @@ class Model:
         # bit-identical to the host conversion) straight into the plan's input buffer.
         u8 = isinstance(X, np.ndarray) and X.dtype == np.uint8
         dt_h = torch.uint8 if u8 else torch.float32
-        Xh = np.ascontiguousarray(X, dtype=np.uint8 if u8 else np.float32).reshape(N, self.H, self.W, 1)
+        Xh = np.ascontiguousarray(X, dtype=np.uint8 if u8 else np.float32).reshape(N, fh, fw, 1)
         depth = 3
-        key = (bs, str(dev), u8)
+        key = (bs, str(dev), u8) if not resize else (bs, str(dev), u8, fh, fw)
         ring = self._rings.get(key)
         if ring is None:
-            ring = [(torch.empty((bs, self.H, self.W, 1), dtype=dt_h).pin_memory(),
-                     torch.empty((bs, self.H, self.W, 1), dtype=dt_h, device=dev),
+            ring = [(torch.empty((bs, fh, fw, 1), dtype=dt_h).pin_memory(),
+                     torch.empty((bs, fh, fw, 1), dtype=dt_h, device=dev),
                      torch.cuda.Event(), torch.cuda.Event()) for _ in range(depth)]
             self._rings[key] = ring
             self._copy_stream = torch.cuda.Stream(device=dev)
@@ -456,13 +474,14 @@ class Model:
             consumed.record(main)
         return out.cpu().numpy()
 
-    def predict_u8(self, X_u8, batch_size=32, verbose=0):
+    def predict_u8(self, X_u8, batch_size=32, verbose=0, resize=False):
         """predict() over uint8 grey-level frames [N,H,W(,1)] (what load_img yields before utils.py:340-342 scales it):
-        same result as predict(to_network_input(X_u8)), a quarter of the bytes over PCIe."""
+        same result as predict(to_network_input(X_u8)), a quarter of the bytes over PCIe.  resize=True: frames of any
+        size, resized to the model's on the device (see predict)."""
         X_u8 = np.asarray(X_u8)
         if X_u8.dtype != np.uint8:
             raise TypeError("predict_u8 expects uint8 frames, got %s" % X_u8.dtype)
-        return self.predict(X_u8, batch_size=batch_size, verbose=verbose)
+        return self.predict(X_u8, batch_size=batch_size, verbose=verbose, resize=resize)
 
     def evaluate(self, X, Y, batch_size=32, verbose=0):
         return custom_loss(Y, self.predict(X, batch_size=batch_size))

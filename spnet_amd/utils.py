@@ -143,13 +143,19 @@ def _load_one(force_dim, grayscale, filename, as_uint8=False):
     return arr[:, :, 0:1] if grayscale else arr
 
 
-def build_X(total_load, img_file_list, force_dim=224, grayscale=False, as_uint8=False):
+def build_X(total_load, img_file_list, force_dim=224, grayscale=False, as_uint8=False, device_resize=False):
     """PNG -> X float32 [N,H,W,C] scaled to [-1,1]; channel 0 only when grayscale (utils.py:325-421).
     as_uint8 (additive, grayscale only): keep the decoded grey levels, uint8 [N,H,W,1]; Model.predict applies the
-    same scaling on the device (bit-identical), and the frames cross PCIe as bytes."""
+    same scaling on the device (bit-identical), and the frames cross PCIe as bytes.
+    device_resize (additive, with as_uint8): the grey levels are kept at the files' own size and force_dim is left to
+    Model.predict(X, resize=True), which resizes on the device exactly as PIL does here (spnet_amd/resize.py)."""
     print("      Reading images and assigning as input X...")
     if as_uint8 and not grayscale:
         raise ValueError("as_uint8 is for grayscale input (model_type 'big' / 'monolithic')")
+    if device_resize:
+        if not as_uint8:
+            raise ValueError("device_resize needs as_uint8=True (the device resizes 8-bit grey levels)")
+        force_dim = None
     first = _load_one(force_dim, grayscale, img_file_list[0], as_uint8)
     img_dims = first.shape
     X = np.zeros((total_load,) + img_dims, dtype=np.uint8 if as_uint8 else cf.dtype)

@@ -7,9 +7,9 @@ Layout of the reference run (its log :62-66,:176,:208): model_type 'monolithic' 
 batch 16, lr_max 4e-5 1-cycle, augmentation on the fly, freeze_fac 0 (`Freezing 0 / 144 layers`), loss_type 'same'.
 Here: the same flow through the product's own API (models.setup_model -> Model.fit with MyProgressCallback,
 OneCycleScheduler, AugmentOnTheFly; evaluate_spnet.py's metrics at the end).  Frames come from the device
-fake-ESPI generator (csrc/espi.hip; labels identical to the host generator's), are resized on the host with the
-codec's own PIL call and never touch the disk.  gpurun allows 20 minutes per call, so the number of epochs is an
-argument (the 1-cycle schedule is built for that many epochs, as train_spnet.py -e would).
+fake-ESPI generator (csrc/espi.hip; labels identical to the host generator's), are resized on the device exactly as the
+codec's own PIL call resizes them (generate_device(size=...), spnet_amd/resize.py) and never touch the disk.  One GPU
+job is limited to 20 minutes, so the number of epochs is an argument (the 1-cycle schedule is built for that many epochs, as train_spnet.py -e would).
 
 Round 4 (like-for-like): --density 0-6 draws the number of antinodes per frame the way the generator did when the
 published dataset was made (gen_fake_espi.py:250-251 dates the change to 1-7 to Nov 2020; 14,965 objects in 4,992
@@ -24,7 +24,6 @@ import json
 import os
 import sys
 import time
-from multiprocessing.pool import ThreadPool
 
 import numpy as np
 
@@ -69,34 +68,23 @@ BANDS = {
 }
 
 
-def make_set(n, seed, dev, size, threads, count_range=(1, 7)):
-    """n fake-ESPI frames: device rasteriser -> uint8 on the host -> the input codec's resize (PIL Lanczos to
-    size x size, utils._load_one) -> float32 [n,size,size,1] in [-1,1]; labels -> normalised grid targets."""
+def make_set(n, seed, dev, size, count_range=(1, 7)):
+    """n fake-ESPI frames: device rasteriser -> the input codec's resize on the device (PIL Lanczos to size x size,
+    utils._load_one, bit for bit: spnet_amd/resize.py) -> float32 [n,size,size,1] in [-1,1]; labels -> normalised grid
+    targets."""
     import torch
-    from PIL import Image
     import bench
     from spnet_amd import fake_espi as F
     X = np.empty((n, size, size, 1), np.float32)
     labels = []
-    pool = ThreadPool(threads)
-
-    def resize(a):
-        return np.asarray(Image.fromarray(a).resize((size, size), Image.LANCZOS), dtype=np.float32)
-
     block = 4096
     for k, lo in enumerate(range(0, n, block)):
         m = min(block, n - lo)
-        _, lab, U = F.generate_device(m, seed=seed + k, device=str(dev), want_u8=True, count_range=count_range)
-        u = U.cpu().numpy()
-        del U
+        Xd, lab = F.generate_device(m, seed=seed + k, device=str(dev), count_range=count_range, size=size)
+        X[lo:lo + m] = Xd.cpu().numpy()
+        del Xd
         torch.cuda.empty_cache()
-        for i, arr in enumerate(pool.imap(resize, list(u), chunksize=16)):
-            X[lo + i, :, :, 0] = arr
         labels += lab
-    pool.close()
-    X /= 255.0
-    X -= 0.5
-    X *= 2.0
     return X, bench.labels_to_Y(labels)
 
 
@@ -288,11 +276,11 @@ def main():
     count_range = (lo, hi)
 
     # (generator seeds: frame seed = seed * 1000003 + i must stay below 2**32; one seed per block of 4,096 frames)
-    X_train, Y_train = make_set(args.train, 100 + 1000 * args.seed, dev, args.size, threads, count_range)
-    X_val, Y_val = make_set(args.val, 300 + 1000 * args.seed, dev, args.size, threads, count_range)
+    X_train, Y_train = make_set(args.train, 100 + 1000 * args.seed, dev, args.size, count_range)
+    X_val, Y_val = make_set(args.val, 300 + 1000 * args.seed, dev, args.size, count_range)
     X_test = Y_test = None
     if args.test:
-        X_test, Y_test = make_set(args.test, 400 + 1000 * args.seed, dev, args.size, threads, count_range)
+        X_test, Y_test = make_set(args.test, 400 + 1000 * args.seed, dev, args.size, count_range)
     t_data = time.time() - t_start
     print("data: %d/%d/%d frames at %dx%d in %.1f s" % (args.train, args.val, args.test, args.size, args.size, t_data),
           flush=True)

@@ -1,0 +1,122 @@
+#! /usr/bin/env python3
+"""Offline geometric augmentation of a directory of PNG + CSV pairs -- the surface of the reference's augment_preproc.py:
+every image is flipped at random, rotated by up to +-20 degrees about its centre and (nine times out of ten) shifted by
+up to +-40 px, n_augs times, and each result is written beside it as a new PNG + CSV with the reference's file-name
+suffixes (_v | _h | _vh, _r{angle:.2f}, _t{xt},{yt}).  The pixels are warped in batches on the GPU (spnet_amd.augmentation.
+DeviceWarper: the whole chain in one launch, bit-identical to flip_image -> rotate_image -> translate_image), the metadata
+with the reference's arithmetic.
+
+Differences from the reference, on purpose: the file lists are sorted; every (file, augmentation) pair draws from its own
+RNG stream seeded by (seed, file index, augmentation index) -- the reference's forked workers all inherit ONE generator
+state and so repeat each other's draws -- which makes a run reproducible whatever the batch size; band-pass mix-up
+(bp_too) is not part of this tool.  train_spnet.py --warp does the same warps afresh every epoch without writing files.
+"""
+import glob
+import os
+
+import numpy as np
+from PIL import Image
+
+meta_extension = ".csv"
+
+
+def caption_from_metadata(metadata):
+    """metadata list-of-lists -> CSV text, one antinode per line (augment_preproc.py:41-53)."""
+    return "\n".join("{0},{1},{2},{3},{4},{5}".format(*row) for row in metadata)
+
+
+def _read_planes(filename):
+    """PNG -> uint8 planes [C,H,W] (1 for L, 3 for RGB, 4 for RGBA); other modes are read as RGB."""
+    with Image.open(filename) as im:
+        if im.mode not in ("L", "RGB", "RGBA"):
+            im = im.convert("RGB")
+        a = np.asarray(im, dtype=np.uint8)
+    return a[None] if a.ndim == 2 else np.ascontiguousarray(np.moveaxis(a, 2, 0))
+
+
+def augment_data(path='Train', n_augs=39, seed=0, chunk=256):
+    """Writes n_augs warped copies of every PNG + CSV pair of `path`; returns [(prefix, params)] of the files written,
+    params = dict(flip, angle, xt, yt) with xt = yt = None where no shift was drawn.  chunk: planes warped per launch."""
+    import torch
+    from spnet_amd import augmentation as A
+    from spnet_amd import parallel, utils
+    print("augment_data: Augmenting data in", path, 'by a factor of', n_augs + 1)
+    path += '/'
+    img_file_list = sorted(glob.glob(path + '*.png'))
+    meta_file_list = sorted(glob.glob(path + '*' + meta_extension))
+    assert len(img_file_list) == len(meta_file_list), \
+        f"{len(img_file_list)} images, {len(meta_file_list)} CSV files. Should be the same number"
+    numfiles = len(img_file_list)
+    print("Found", numfiles, "files in", path)
+    if not torch.cuda.is_available():
+        raise RuntimeError("augment_preproc warps on the GPU (no CPU fallback)")
+    written = []
+    jobs, planes = [], []          # pending (file index, aug index, first plane, plane count), their source planes
+
+    def flush():
+        if not jobs:
+            return
+        X = np.concatenate(planes)
+        warper = A.DeviceWarper(X)
+        index, draws = [], []
+        for i, k, p0, c in jobs:
+            np.random.seed(parallel.sample_seed(seed, k, i))
+            d = A.draw_warp_gated()
+            draws.append(d)
+            index += list(range(p0, p0 + c))
+        params = warper.new_params(index)
+        j = 0
+        for (i, k, p0, c), (flip, angle, xt, yt) in zip(jobs, draws):
+            for _ in range(c):              # the planes of one image share its parameter set
+                A.set_warp(params, j, flip, angle, xt or 0, yt or 0)
+                j += 1
+        out = torch.empty((len(index), warper.H, warper.W), dtype=torch.uint8, device=warper.X.device)
+        warper.apply(params, out_u8=out)
+        out = out.cpu().numpy()
+        j = 0
+        for (i, k, p0, c), (flip, angle, xt, yt) in zip(jobs, draws):
+            md, suffix = A.chain_metadata(utils.read_metadata(meta_file_list[i]), flip, angle, xt, yt, warper.W, warper.H)
+            prefix = os.path.splitext(img_file_list[i])[0] + suffix
+            img = out[j] if c == 1 else np.moveaxis(out[j:j + c], 0, 2)
+            j += c
+            with open(prefix + meta_extension, "w") as f:
+                f.write(caption_from_metadata(md))
+            Image.fromarray(np.ascontiguousarray(img)).save(prefix + '.png')     # 1 / 3 / 4 planes: L / RGB / RGBA, the input's mode
+            written.append((prefix, dict(flip=flip, angle=angle, xt=xt, yt=yt)))
+        jobs.clear()
+        planes.clear()
+
+    saved = np.random.get_state()
+    try:
+        shape, n_planes = None, 0
+        for i in range(numfiles):
+            if 0 == i % 10:
+                print("     Progress: i =", i, "/", numfiles)
+            pl = _read_planes(img_file_list[i])
+            if shape is not None and pl.shape[1:] != shape:
+                flush()                      # a batch holds frames of one size
+                n_planes = 0
+            shape = pl.shape[1:]
+            planes.append(pl)
+            for k in range(n_augs):
+                jobs.append((i, k, n_planes, pl.shape[0]))
+            n_planes += pl.shape[0]
+            if len(jobs) * pl.shape[0] >= chunk:
+                flush()
+                n_planes = 0
+        flush()
+    finally:
+        np.random.set_state(saved)
+    print("Augmented from", numfiles, "files up to", len(sorted(glob.glob(path + '*.png'))))
+    return written
+
+
+if __name__ == "__main__":
+    import argparse
+    parser = argparse.ArgumentParser(description="augments data in path",
+                                     formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument('-d', '--datapath', help='dataset directory in which to augment', default="Train/")
+    parser.add_argument('-n', '--naugs', type=int, help='number of augmentations per image to generate', default=42)
+    parser.add_argument('--seed', type=int, help='seed of the per-(file, augmentation) random streams', default=0)
+    args = parser.parse_args()
+    augment_data(path=args.datapath, n_augs=args.naugs, seed=args.seed)

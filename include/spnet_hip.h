@@ -453,6 +453,19 @@ int spnet_warp_affine(const float* src, float* dst, int N, int H, int W, int C, 
  * column terms of the INVERTED matrix, scaled by 1024 (+ round_delta 16 in X0 / Y0). */
 int spnet_warp_affine_fixed(const float* src, float* dst, int N, int H, int W, int C, const int* xrow, const int* xcol,
                             void* stream);
+/* flip_image -> rotate_image -> translate_image of N one-channel uint8 frames in ONE gather (augment_preproc.py:74-99;
+ * spnet/augmentation.py:82-112, 184-207 and 216-239), bit-identical to the three steps run one after the other: the flip is
+ * a pixel permutation, the rotation cv2.warpAffine's 8-bit fixed-point bilinear (as spnet_warp_affine_fixed computes it, its
+ * row / column terms formed on the device in float64 without contraction), the translation an integer shift with zero fill.
+ * src [n_src][H][W]; sel (or NULL: output n reads source n, N <= n_src): int32 source index per output, clamped to
+ * [0, n_src); params: N records of 64 bytes, 8-byte aligned = { double m[6] (the INVERTED rotation matrix, row major),
+ * int flip (-2 none, 0 vertical, 1 horizontal, -1 both), int xt, int yt, int pad }.  out_u8 (or NULL): [N][H][W]; out_f (or
+ * NULL): the same frames as network input, == spnet_u8_to_input(out_u8); at least one.  Sizes 1 .. 2048, any W, no
+ * alignment asked of src / out_u8.  hipErrorInvalidValue (nothing written) otherwise.  No parameter value causes an
+ * out-of-range access: row / column terms saturate at 2^29 (bit-identity holds below that), shifts past the frame give
+ * zeros, other flip codes mean none. */
+int spnet_warp_chain_u8(const unsigned char* src, int n_src, const int* sel, const void* params, int N, int H, int W,
+                        unsigned char* out_u8, float* out_f, void* stream);
 /* Dropout(0.1) of the stem (spnet/models.py:340); same call with dy regenerates the mask in backward. */
 int spnet_dropout(const float* x, float* y, long n, unsigned seed, float rate, const unsigned* seed_dev,
                   void* stream);   /* seed_dev (or NULL): device uint32 overriding seed (hipGraph replay) */

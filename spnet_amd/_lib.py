@@ -135,6 +135,7 @@ _SIGS = {
     "spnet_gaussian_blur": (c_int, [P, P, c_int, c_int, c_int, P, P]),
     "spnet_warp_affine": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
     "spnet_warp_affine_fixed": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P]),
+    "spnet_warp_chain_u8": (c_int, [P, c_int, P, P, c_int, c_int, c_int, P, P, P]),
     "spnet_fake_espi": (c_int, [P, P, P, c_int, c_int, c_int, c_uint, c_int, P, P, P]),
     "spnet_dropout": (c_int, [P, P, c_long, c_uint, c_float, P, P]),
     "spnet_bandpass_ws": (c_long, [c_int, c_int, c_int]),

@@ -6,7 +6,9 @@ reference's call order (so a seeded run reproduces the reference's augmented fra
 the PIXEL work runs in HIP kernels on frames that never leave HBM (csrc/augment.hip).
 
 Offline warps (augment_preproc.py:56-100): flip / rotate / translate = one inverse-affine bilinear
-gather kernel plus the reference's host-side metadata arithmetic.
+gather kernel plus the reference's host-side metadata arithmetic.  DeviceWarper is the batched, device-resident form: the
+whole flip -> rotate -> translate chain of a batch in one launch (csrc/warp.hip), bit-identical to the three calls, with the
+metadata arithmetic and the target codec vectorised on the host (warp_metadata, warp_targets).
 
 Band-pass mix-up (augmentation.py:10-62): BandpassPool holds the real frames and their low-frequency windows on the
 device, BandpassMixer draws and applies the mix-up (csrc/bandpass.hip), bandpass_mixup is the reference's function.
@@ -108,8 +110,10 @@ class DeviceAugmenter:
                 raise ValueError("DeviceAugmenter: band-pass pool is %dx%d, the frames are %dx%d" % (pool.H, pool.W, self.H, self.W))
             self.bp = pool.mixer
 
-    def draw(self, indices, seeds=None):
-        """Host-side parameter draw for the given frame indices, reference RNG order per frame.  seeds (optional,
+    def draw(self, indices, seeds=None, before=None):
+        """Host-side parameter draw for the given frame indices, reference RNG order per frame.  before (optional):
+        before(j, i) is called for frame i (position j) after its seeding and ahead of its cutout draws -- where
+        AugmentOnTheFly(warp=True) makes the frame's warp draws.  seeds (optional,
         one per frame): each frame's draws come from numpy / python streams seeded with its own seed (data parallel:
         a sample's augmentation then depends on its seed only, not on what was drawn before it); the process-wide
         RNG states are saved and restored around the draw, so later consumers of np.random / random are unaffected."""
@@ -123,7 +127,7 @@ class DeviceAugmenter:
         ksize = np.zeros(B, np.int32)
         saved = (np.random.get_state(), random.getstate()) if seeds is not None else None
         try:
-            p = self._draw(indices, seeds, rects, vals, nrect, coords, flag, ksize)
+            p = self._draw(indices, seeds, rects, vals, nrect, coords, flag, ksize, before)
             if self.bp is not None:
                 p["bp_n"] = len(p["bp_sel"])
                 for k, dt in (("bp_sel", np.int32), ("bp_row", np.int32), ("bp_s", np.float32)):
@@ -136,12 +140,14 @@ class DeviceAugmenter:
                 np.random.set_state(saved[0])
                 random.setstate(saved[1])
 
-    def _draw(self, indices, seeds, rects, vals, nrect, coords, flag, ksize):
+    def _draw(self, indices, seeds, rects, vals, nrect, coords, flag, ksize, before=None):
         bp_sel, bp_row, bp_s = [], [], []
         for j, i in enumerate(indices):
             if seeds is not None:
                 np.random.seed(int(seeds[j]))
                 random.seed(int(seeds[j]))
+            if before is not None:
+                before(j, i)
             lo, hi = self.mm_host[i]
             rs = draw_cutout(self.shape, lo, hi)
             nrect[j] = len(rs)
@@ -165,9 +171,16 @@ class DeviceAugmenter:
             p.update(bp_sel=bp_sel, bp_row=bp_row, bp_s=bp_s)
         return p
 
-    def apply(self, params, out):
-        """out[j] = augmented copy of frame params['index'][j]; out is a device tensor [B,H,W,1]."""
+    def apply(self, params, out, src=None):
+        """out[j] = augmented copy of frame params['index'][j]; out is a device tensor [B,H,W,1].  src (optional, device
+        float32 [B,H,W(,1)], not `out`): the batch's frames are read from src[j] instead (frames that were warped first)."""
         dev = self.X.device
+        X = self.X
+        if src is not None:
+            if src.dtype != torch.float32 or not src.is_contiguous() or src.numel() != len(params["index"]) * self.H * self.W:
+                raise ValueError("DeviceAugmenter.apply: src must be contiguous float32 [%d,%d,%d]" % (len(params["index"]), self.H, self.W))
+            X = src
+            params = dict(params, index=np.arange(len(params["index"]), dtype=np.int32))
         if self._upload is None:
             self._upload = L.AsyncUploader(dev)
         # ONE host -> device copy for the whole parameter set: every async copy from pinned memory is preceded by ~56 us
@@ -186,7 +199,7 @@ class DeviceAugmenter:
         B = len(params["index"])
         self._keep = up                    # keep the upload alive until the kernels have consumed it
         self.index_dev = up["index"]       # int32 frame indices of this batch on the device (label gathers reuse them)
-        L.spnet_cutout(self.X.data_ptr(), up["index"].data_ptr(), out.data_ptr(), B, self.H, self.W,
+        L.spnet_cutout(X.data_ptr(), up["index"].data_ptr(), out.data_ptr(), B, self.H, self.W,
                        up["rects"].data_ptr(), up["vals"].data_ptr(), up["nrect"].data_ptr(), _stream())
         mm = torch.empty(B * (2 + 32), device=dev)   # [B,2] result followed by B*32 floats of reduction scratch
         self._mm = mm
@@ -281,12 +294,9 @@ def _warp(img, minv):
     return out
 
 
-def cv2_fixed_point_terms(M, H, W):
-    """Row / column terms of cv2.warpAffine's fixed-point coordinate computation for a FORWARD 2x3 matrix M (OpenCV 3.4
-    imgwarp.cpp, warpAffine + WarpAffineInvoker): M is inverted in double precision exactly as OpenCV does it, then
-    adelta[x] = cvRound(M00*x*1024), bdelta[x] = cvRound(M10*x*1024), X0[y] = cvRound((M01*y + M02)*1024) + 16,
-    Y0[y] = cvRound((M11*y + M12)*1024) + 16 (cvRound = round-half-even = np.rint).  Returns int32 arrays
-    xrow [H,2] = (X0, Y0), xcol [W,2] = (adelta, bdelta)."""
+def invert_affine_cv2(M):
+    """The inverse of a FORWARD 2x3 matrix as cv2.warpAffine forms it, operation by operation in double precision (OpenCV
+    3.4 imgwarp.cpp, warpAffine)."""
     m = np.asarray(M, np.float64).reshape(2, 3).copy()
     D = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
     D = 1.0 / D if D != 0 else 0.0
@@ -295,6 +305,16 @@ def cv2_fixed_point_terms(M, H, W):
     b1 = -m[0, 0] * m[0, 2] - m[0, 1] * m[1, 2]
     b2 = -m[1, 0] * m[0, 2] - m[1, 1] * m[1, 2]
     m[0, 2], m[1, 2] = b1, b2
+    return m
+
+
+def cv2_fixed_point_terms(M, H, W):
+    """Row / column terms of cv2.warpAffine's fixed-point coordinate computation for a FORWARD 2x3 matrix M (OpenCV 3.4
+    imgwarp.cpp, warpAffine + WarpAffineInvoker): M is inverted in double precision exactly as OpenCV does it, then
+    adelta[x] = cvRound(M00*x*1024), bdelta[x] = cvRound(M10*x*1024), X0[y] = cvRound((M01*y + M02)*1024) + 16,
+    Y0[y] = cvRound((M11*y + M12)*1024) + 16 (cvRound = round-half-even = np.rint).  Returns int32 arrays
+    xrow [H,2] = (X0, Y0), xcol [W,2] = (adelta, bdelta)."""
+    m = invert_affine_cv2(M)
     xs, ys = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
     xcol = np.stack([np.rint(m[0, 0] * xs * 1024.0), np.rint(m[1, 0] * xs * 1024.0)], 1).astype(np.int32)
     xrow = np.stack([np.rint((m[0, 1] * ys + m[0, 2]) * 1024.0) + 16, np.rint((m[1, 1] * ys + m[1, 2]) * 1024.0) + 16],
@@ -329,15 +349,8 @@ def rotation_matrix_2d(center, angle_deg, scale=1.0):
     return np.array([[a, b, (1 - a) * cx - b * cy], [-b, a, b * cx + (1 - a) * cy]], np.float64)
 
 
-def flip_image(img, metadata, file_prefix, flip_param):
-    """flip_param: -2 none, 0 vertical, 1 horizontal, -1 both (augmentation.py:82-112)."""
-    if flip_param == -2:
-        return img.copy(), list(metadata), file_prefix[:]
-    height, width, _ = img.shape
-    sx = -1.0 if flip_param in (1, -1) else 1.0
-    sy = -1.0 if flip_param in (0, -1) else 1.0
-    minv = [[sx, 0, (width - 1) if sx < 0 else 0], [0, sy, (height - 1) if sy < 0 else 0]]
-    out = _warp(img, minv)
+def flip_metadata(metadata, flip_param, width, height):
+    """Metadata half of flip_image (augmentation.py:91-104)."""
     new_md = []
     for cx, cy, a, b, angle, rings in metadata:
         if flip_param in (0, -1):
@@ -347,8 +360,49 @@ def flip_image(img, metadata, file_prefix, flip_param):
             cx, angle = width - cx, 180 - angle
         angle = cleanup_angle(angle)
         new_md.append([cx, cy, a, b, angle, rings])
-    suffix = {0: "_v", 1: "_h"}.get(flip_param, "_vh")
-    return out, new_md, file_prefix + suffix
+    return new_md
+
+
+def flip_suffix(flip_param):
+    return {0: "_v", 1: "_h"}.get(flip_param, "_vh")
+
+
+def rotate_metadata(metadata, rot_angle, M):
+    """Metadata half of rotate_image (augmentation.py:196-204); M: the forward rotation matrix."""
+    new_md = []
+    for cx, cy, a, b, angle, rings in metadata:
+        angle = cleanup_angle(angle + rot_angle)
+        p = M @ np.array([cx, cy, 1.0])
+        new_md.append([int(round(p[0])), int(round(p[1])), a, b, angle, rings])
+    return new_md
+
+
+def chain_metadata(metadata, flip, angle, xt, yt, width, height):
+    """(rows, file-name suffix) of flip_image -> rotate_image -> translate_image for one frame's rows as Python values (the
+    types a CSV written from them shows); translate_image's part applies whenever a shift was drawn, i.e. (xt, yt) is
+    given as None, None when its gate was 0."""
+    md, suffix = list(metadata), ""
+    if flip != -2:
+        md, suffix = flip_metadata(md, flip, width, height), flip_suffix(flip)
+    if angle != 0:
+        md = rotate_metadata(md, angle, rotation_matrix_2d((width / 2, height / 2), angle, 1.0))
+        suffix += "_r{:>.2f}".format(angle)
+    if xt is not None:
+        md = [[cx + xt, cy + yt, a, b, ang, rings] for cx, cy, a, b, ang, rings in md]
+        suffix += "_t" + str(xt) + ',' + str(yt)
+    return md, suffix
+
+
+def flip_image(img, metadata, file_prefix, flip_param):
+    """flip_param: -2 none, 0 vertical, 1 horizontal, -1 both (augmentation.py:82-112)."""
+    if flip_param == -2:
+        return img.copy(), list(metadata), file_prefix[:]
+    height, width, _ = img.shape
+    sx = -1.0 if flip_param in (1, -1) else 1.0
+    sy = -1.0 if flip_param in (0, -1) else 1.0
+    minv = [[sx, 0, (width - 1) if sx < 0 else 0], [0, sy, (height - 1) if sy < 0 else 0]]
+    out = _warp(img, minv)
+    return out, flip_metadata(metadata, flip_param, width, height), file_prefix + flip_suffix(flip_param)
 
 
 def rotate_image(img, metadata, file_prefix, rot_angle, rot_origin=None):
@@ -362,12 +416,7 @@ def rotate_image(img, metadata, file_prefix, rot_angle, rot_origin=None):
     M = rotation_matrix_2d(rot_origin, rot_angle, 1.0)
     # 8-bit images (the offline set, augment_preproc.py) take OpenCV's fixed-point path like the reference's call does
     out = _warp_cv2(img, M) if img.dtype == np.uint8 else _warp(img, _invert_affine(M))
-    new_md = []
-    for cx, cy, a, b, angle, rings in metadata:
-        angle = cleanup_angle(angle + rot_angle)
-        p = M @ np.array([cx, cy, 1.0])
-        new_md.append([int(round(p[0])), int(round(p[1])), a, b, angle, rings])
-    return out, new_md, file_prefix[:] + "_r{:>.2f}".format(rot_angle)
+    return out, rotate_metadata(metadata, rot_angle, M), file_prefix[:] + "_r{:>.2f}".format(rot_angle)
 
 
 def translate_image(img, metadata, file_prefix, trans_index):
@@ -384,6 +433,292 @@ def translate_image(img, metadata, file_prefix, trans_index):
 
 def invert_image(img, metadata, file_prefix):
     return 255 - img, list(metadata), file_prefix + "_i"
+
+
+# ----------------------------------------------------------------------------- batched warp chain
+MAX_OBJECTS = 16                  # ellipses per frame the vectorised metadata path pads to (the data sets hold at most 6)
+WARP_RECORD = np.dtype([("m", "<f8", (6,)), ("flip", "<i4"), ("xt", "<i4"), ("yt", "<i4"), ("pad", "<i4")])   # csrc/warp.hip
+_IDENTITY_MINV = np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0])
+
+
+def draw_warp(H, W):
+    """The RNG calls of one pass of augment_one_file (augment_preproc.py:74-86) in its order: np.random.choice of the
+    flip code, np.random.uniform(-20, 20) for the angle, np.random.randint(10) for translate_image's gate and, only when
+    that is not 0, translate_image's two np.random.random() (spnet/augmentation.py:227-228).  Returns (flip, angle, xt,
+    yt); the draws do not depend on the frame size."""
+    flip, angle, xt, yt = draw_warp_gated()
+    return flip, angle, xt or 0, yt or 0
+
+
+def draw_warp_gated():
+    """draw_warp with xt = yt = None when translate_image's gate was 0 (it then adds no '_t' suffix to the file name)."""
+    flip = int(np.random.choice([-2, -1, 0, 1]))
+    angle = float(np.random.uniform(-20, high=20))
+    xt = yt = None
+    if np.random.randint(10) != 0:
+        trans_max = 40
+        xt = int(round(trans_max * (2 * np.random.random() - 1)))
+        yt = int(round(trans_max * (2 * np.random.random() - 1)))
+    return flip, angle, xt, yt
+
+
+def warp_minv(H, W, angle):
+    """The six entries of the INVERTED matrix of rotate_image(angle) for an H x W frame, as cv2.warpAffine inverts it; the
+    identity for angle == 0 (rotate_image returns the frame as it is)."""
+    if angle == 0:
+        return _IDENTITY_MINV.copy()
+    return invert_affine_cv2(rotation_matrix_2d((W / 2, H / 2), angle, 1.0)).reshape(6)
+
+
+def new_warp_params(indices, H, W):
+    """Identity parameters for the frames `indices`: dict(index, flip, angle, xt, yt, minv [B,6], H, W)."""
+    B = len(indices)
+    return dict(index=np.asarray(indices, np.int32), flip=np.full(B, -2, np.int32), angle=np.zeros(B, np.float64),
+                xt=np.zeros(B, np.int32), yt=np.zeros(B, np.int32), minv=np.tile(_IDENTITY_MINV, (B, 1)), H=int(H), W=int(W))
+
+
+def set_warp(params, j, flip, angle, xt, yt):
+    params["flip"][j], params["angle"][j], params["xt"][j], params["yt"][j] = flip, angle, xt, yt
+    params["minv"][j] = warp_minv(params["H"], params["W"], angle)
+
+
+def warp_chain_host(frames, params):
+    """numpy restatement of spnet_warp_chain_u8 (tests, documentation): uint8 frames [n_src,H,W], output j from frame
+    params['index'][j].  The single gather: destination (x, y) takes the rotated value at (u, v) = (x - xt, y - yt) or 0
+    outside the image, and the four fixed-point bilinear taps of that value read the source through the flip."""
+    frames = np.asarray(frames)
+    H, W = frames.shape[1:3]
+    out = np.zeros((len(params["index"]), H, W), np.uint8)
+    for j, i in enumerate(params["index"]):
+        m = params["minv"][j]
+        flip, xt, yt = int(params["flip"][j]), int(params["xt"][j]), int(params["yt"][j])
+        src = frames[min(max(int(i), 0), len(frames) - 1)].astype(np.int64)
+        u, v = np.arange(W, dtype=np.float64) - xt, np.arange(H, dtype=np.float64) - yt
+        ad, bd = np.rint(m[0] * u * 1024.0).astype(np.int64), np.rint(m[3] * u * 1024.0).astype(np.int64)
+        X0 = np.rint((m[1] * v + m[2]) * 1024.0).astype(np.int64) + 16
+        Y0 = np.rint((m[4] * v + m[5]) * 1024.0).astype(np.int64) + 16
+        X, Y = (X0[:, None] + ad[None, :]) >> 5, (Y0[:, None] + bd[None, :]) >> 5
+        sx, sy, fx, fy = X >> 5, Y >> 5, X & 31, Y & 31
+
+        def at(y, x):
+            ok = (y >= 0) & (y < H) & (x >= 0) & (x < W)
+            yy, xx = np.clip(y, 0, H - 1), np.clip(x, 0, W - 1)
+            if flip in (0, -1):
+                yy = H - 1 - yy
+            if flip in (1, -1):
+                xx = W - 1 - xx
+            return np.where(ok, src[yy, xx], 0)
+        w00 = np.minimum((32 - fy) * (32 - fx) * 32, 32767)
+        val = (at(sy, sx) * w00 + at(sy, sx + 1) * ((32 - fy) * fx * 32) + at(sy + 1, sx) * (fy * (32 - fx) * 32) +
+               at(sy + 1, sx + 1) * (fy * fx * 32) + (1 << 14)) >> 15
+        inside = ((v >= 0) & (v < H))[:, None] & ((u >= 0) & (u < W))[None, :]
+        out[j] = np.where(inside, np.clip(val, 0, 255), 0)
+    return out
+
+
+def pad_metadata(meta, max_objects=MAX_OBJECTS):
+    """List (one entry per frame) of [cx,cy,a,b,angle,rings] row lists -> (rows float64 [B,max_objects,6] zero padded,
+    count int32 [B]).  ValueError when a frame holds more objects."""
+    if isinstance(meta, tuple):
+        return meta
+    B = len(meta)
+    rows, count = np.zeros((B, max_objects, 6), np.float64), np.zeros(B, np.int32)
+    for j, md in enumerate(meta):
+        if len(md) > max_objects:
+            raise ValueError("warp metadata: frame %d holds %d objects, at most %d are supported" % (j, len(md), max_objects))
+        count[j] = len(md)
+        if len(md):
+            rows[j, :len(md)] = np.asarray(md, np.float64).reshape(len(md), 6)
+    return rows, count
+
+
+def _cleanup_angle_where(angle, mask):
+    """cleanup_angle on the entries `mask` selects, in its add / subtract 180 form (the same roundings as the scalar loop)."""
+    angle = angle.copy()
+    while True:
+        m = mask & (angle < 0)
+        if not m.any():
+            break
+        angle[m] += 180
+    while True:
+        m = mask & (angle >= 180)
+        if not m.any():
+            break
+        angle[m] -= 180
+    return angle
+
+
+def warp_metadata(meta, params):
+    """The metadata arithmetic of flip_image -> rotate_image -> translate_image for a chunk of frames, in float64 with the
+    reference's roundings: height - cy / width - cx and the angle reflections with cleanup_angle after each (flip code -2
+    leaves the rows alone), angle + rot_angle, centres through the FORWARD rotation matrix and int(round()) (angle 0
+    leaves the rows alone), then the integer shift.  meta: a list of row lists or pad_metadata's result for the frames of
+    params, in their order.  Returns (rows [B,MAX_OBJECTS,6], count [B]).  The rotated centres are summed as
+    (m00 cx + m01 cy) + m02; numpy's own M @ [cx, cy, 1] can differ from that in the last bit, which changes
+    a centre only where it falls within one ulp of a half-integer."""
+    rows, count = pad_metadata(meta)
+    rows = rows.copy()
+    H, W = params["H"], params["W"]
+    B = rows.shape[0]
+    if len(params["flip"]) != B:
+        raise ValueError("warp_metadata: %d metadata entries for %d parameter sets" % (B, len(params["flip"])))
+    flip = np.asarray(params["flip"])[:, None]
+    rot = np.asarray(params["angle"], np.float64)[:, None]
+    cx, cy, ang = rows[..., 0], rows[..., 1], rows[..., 4]
+    every = np.ones(cx.shape, bool)
+    fy, fx, fany = every & ((flip == 0) | (flip == -1)), every & ((flip == 1) | (flip == -1)), every & (flip != -2)
+    cy[fy] = (H - cy)[fy]
+    ang[fy] = -ang[fy]
+    ang[...] = _cleanup_angle_where(ang, fany)
+    cx[fx] = (W - cx)[fx]
+    ang[fx] = (180 - ang)[fx]
+    ang[...] = _cleanup_angle_where(ang, fany)
+    rmask = every & (rot != 0)
+    if rmask.any():
+        M = np.stack([rotation_matrix_2d((W / 2, H / 2), a, 1.0) if a != 0 else np.eye(2, 3) for a in rot[:, 0]])
+        ang[...] = _cleanup_angle_where(np.where(rmask, ang + rot, ang), rmask)
+        px = M[:, 0, 0, None] * cx + M[:, 0, 1, None] * cy + M[:, 0, 2, None]
+        py = M[:, 1, 0, None] * cx + M[:, 1, 1, None] * cy + M[:, 1, 2, None]
+        cx[rmask] = np.rint(px)[rmask]
+        cy[rmask] = np.rint(py)[rmask]
+    cx += np.asarray(params["xt"], np.float64)[:, None]
+    cy += np.asarray(params["yt"], np.float64)[:, None]
+    rows[np.arange(rows.shape[1])[None, :] >= count[:, None]] = 0.0
+    return rows, count
+
+
+def _encode_targets(rows, count, pred_grid=(6, 6, 2)):
+    """parse_meta_file's row processing -> true_to_pred_grid -> norm_Y (spnet/utils.py:260-286, 191-244, 181-184) for a
+    chunk, bit-identical to the per-sample path.  Returns (Y float32 [B, prod(grid) * 8], overflow bool [B]): overflow
+    marks the frames where a cell would receive more ellipses than it has slots (the reference's AssertionError); their
+    rows of Y hold the ellipses that did fit."""
+    from . import config as cf
+    from . import utils
+    pred_shape = np.array([pred_grid[0], pred_grid[1], pred_grid[2], cf.vars_per_pred], dtype=int)
+    cx_min, cy_min, _, _, xbin, ybin, gridYi = utils.setup_means_and_ranges(pred_shape)
+    nx, ny, ns = int(pred_shape[0]), int(pred_shape[1]), int(pred_shape[2])
+    B, K = rows.shape[0], rows.shape[1]
+    cx, cy, a, b, ang, rings = (rows[..., k] for k in range(6))
+    swap = b > a
+    a, b, ang = np.where(swap, b, a), np.where(swap, a, b), np.where(swap, ang + 90, ang)
+    keep = (np.arange(K)[None, :] < count[:, None]) & (rings > 0.0)
+    t = 2 * np.deg2rad(ang)
+    obj = np.stack([cx, cy, a, b, np.cos(t), np.sin(t), np.zeros_like(cx), rings], -1)       # [B,K,8] float64
+    order = np.lexsort((cy, cx, ~keep), axis=-1)                   # kept rows first, by (cx, cy), stable
+    obj = np.take_along_axis(obj, order[..., None], 1)
+    keep = np.take_along_axis(keep, order, 1)
+    ix = np.clip(np.trunc((obj[..., 0] - cx_min) / xbin), 0, nx - 1).astype(np.int64)
+    iy = np.clip(np.trunc((obj[..., 1] - cy_min) / ybin), 0, ny - 1).astype(np.int64)
+    cell = ix * ny + iy
+    same = (cell[:, :, None] == cell[:, None, :]) & keep[:, None, :] & (np.arange(K)[None, :] < np.arange(K)[:, None])[None]
+    slot = same.sum(-1)                                            # earlier kept ellipses in the same cell
+    overflow = (keep & (slot >= ns)).any(1)
+    G = np.broadcast_to(gridYi, (B,) + gridYi.shape).copy()
+    put = keep & (slot < ns)
+    bi = np.broadcast_to(np.arange(B)[:, None], put.shape)
+    G[bi[put], ix[put], iy[put], slot[put]] = obj[put].astype(G.dtype)
+    return utils.norm_Y(G.reshape(B, -1)), overflow
+
+
+def warp_targets(meta, params, pred_grid=(6, 6, 2)):
+    """Network targets of warped frames: (Y float32 [B,576], rejected bool [B]) = warp_metadata, then the target codec
+    vectorised over the chunk and bit-identical to writing the warped rows to a CSV and loading it (parse_meta_file's row
+    processing -> true_to_pred_grid -> norm_Y).  On the host in numpy: a few hundred values per frame.
+
+    Where the warp moves a third ellipse into a grid cell -- the reference's codec asserts -- the frame is REJECTED for this
+    draw: its entries of `params` are reset to the identity IN PLACE and its row of Y holds its unwarped targets.  No
+    redraw is made, so the RNG order is undisturbed.  Centres that the warp moves out of the image are KEPT: the codec
+    clips them into the edge cells, exactly as the reference's true_to_pred_grid does (and 4-6 % of the frames have one)."""
+    meta = pad_metadata(meta)
+    rows, count = warp_metadata(meta, params)
+    Y, rejected = _encode_targets(rows, count, pred_grid)
+    if rejected.any():
+        Y0, bad = _encode_targets(meta[0][rejected], meta[1][rejected], pred_grid)
+        assert not bad.any(), "the unwarped metadata itself puts more ellipses into a grid cell than it has slots"
+        Y[rejected] = Y0
+        for j in np.nonzero(rejected)[0]:
+            set_warp(params, j, -2, 0.0, 0, 0)
+    return Y, rejected
+
+
+class DeviceWarper:
+    """Keeps pristine full-size uint8 frames [N,H,W] in HBM and their metadata rows on the host; warps batches of them
+    with one launch (csrc/warp.hip) and computes the matching targets on the host.
+      draw(indices, seeds=None) -> params (draw_warp per frame; per-frame seeding as DeviceAugmenter.draw)
+      targets(params)           -> (Y, rejected), see warp_targets (resets rejected frames' parameters to the identity)
+      apply(params, out_u8=None, out_f=None)   out[j] = warp of frame params['index'][j]"""
+
+    def __init__(self, X_u8, meta=None, pred_grid=(6, 6, 2)):
+        if isinstance(X_u8, np.ndarray):
+            if not torch.cuda.is_available():
+                raise RuntimeError("DeviceWarper runs on the GPU (no CPU fallback)")
+            X_u8 = torch.from_numpy(np.ascontiguousarray(X_u8)).cuda()
+        _require_cuda(X_u8)
+        if X_u8.dim() == 4 and X_u8.shape[-1] == 1:
+            X_u8 = X_u8[..., 0]
+        if X_u8.dtype != torch.uint8 or X_u8.dim() != 3:
+            raise ValueError("DeviceWarper expects uint8 frames [N,H,W(,1)], got %s %s" % (X_u8.dtype, tuple(X_u8.shape)))
+        self.X = X_u8.contiguous()
+        self.N, self.H, self.W = (int(v) for v in self.X.shape)
+        if not (1 <= self.H <= 2048 and 1 <= self.W <= 2048):
+            raise ValueError("DeviceWarper: frames of %d x %d (sizes 1 .. 2048)" % (self.H, self.W))
+        self.pred_grid = tuple(pred_grid)
+        self.meta = None
+        if meta is not None:
+            self.meta = pad_metadata(meta)
+            if self.meta[0].shape[0] != self.N:
+                raise ValueError("DeviceWarper: %d metadata entries for %d frames" % (self.meta[0].shape[0], self.N))
+        self._upload = None
+
+    def new_params(self, indices):
+        return new_warp_params(indices, self.H, self.W)
+
+    def draw_into(self, params, j):
+        set_warp(params, j, *draw_warp(self.H, self.W))
+
+    def draw(self, indices, seeds=None):
+        params = self.new_params(indices)
+        saved = (np.random.get_state(), random.getstate()) if seeds is not None else None
+        try:
+            for j in range(len(indices)):
+                if seeds is not None:
+                    np.random.seed(int(seeds[j]))
+                    random.seed(int(seeds[j]))
+                self.draw_into(params, j)
+        finally:
+            if saved is not None:
+                np.random.set_state(saved[0])
+                random.setstate(saved[1])
+        return params
+
+    def targets(self, params):
+        if self.meta is None:
+            raise ValueError("DeviceWarper.targets: no metadata was given")
+        idx = np.asarray(params["index"], np.int64)
+        return warp_targets((self.meta[0][idx], self.meta[1][idx]), params, self.pred_grid)
+
+    def apply(self, params, out_u8=None, out_f=None):
+        B = len(params["index"])
+        if out_u8 is None and out_f is None:
+            raise ValueError("DeviceWarper.apply: no output")
+        for o, dt in ((out_u8, torch.uint8), (out_f, torch.float32)):
+            if o is not None and (o.dtype != dt or o.device != self.X.device or not o.is_contiguous() or
+                                  o.numel() != B * self.H * self.W):
+                raise ValueError("DeviceWarper.apply: output must be a contiguous %s device tensor of %d x %d x %d elements"
+                                 % (dt, B, self.H, self.W))
+        if B == 0:
+            return out_u8, out_f
+        rec = np.zeros(B, WARP_RECORD)
+        rec["m"], rec["flip"], rec["xt"], rec["yt"] = params["minv"], params["flip"], params["xt"], params["yt"]
+        if self._upload is None:
+            self._upload = L.AsyncUploader(self.X.device)
+        # one host -> device copy: the records (8-byte aligned at the front), then the source indices
+        packed = self._upload("warp", np.concatenate([rec.view(np.int32).reshape(-1), np.asarray(params["index"], np.int32)]))
+        self._keep = packed
+        with torch.cuda.device(self.X.device):
+            L.spnet_warp_chain_u8(self.X.data_ptr(), self.N, packed[16 * B:].data_ptr(), packed.data_ptr(), B, self.H, self.W,
+                                  L.ptr(out_u8), L.ptr(out_f), _stream())
+        return out_u8, out_f
 
 
 # ----------------------------------------------------------------------------- band-pass mix-up

@@ -92,12 +92,21 @@ class AugmentOnTheFly(Callback):
     fit() reads batches from (`model.set_train_frames`)."""
 
     def __init__(self, X, Y, orig_img_shape=(384, 512), aug_every=1, chunk=256, seed=1, real_blur=False,
-                 bandpass_real=None, bpmix_prob=0.3):
+                 bandpass_real=None, bpmix_prob=0.3, warp=False, warp_files=None, pred_grid=(6, 6, 2)):
         """real_blur=False reproduces the reference, whose Gaussian blur is a no-op (the result of cv2.GaussianBlur is
         discarded, augmentation.py:66-70); True applies it (train_spnet.py --augment_blur).
         bandpass_real: directory of real *.png frames of the training frames' size -- after the blur, a frame is
         band-pass mixed with probability bpmix_prob (bp_mixup, callbacks.py:311-315, whose call the reference has
-        commented out; train_spnet.py --bp_real / --bpmix_prob).  None (default): off."""
+        commented out; train_spnet.py --bp_real / --bpmix_prob).  None (default): off.
+        warp (train_spnet.py --warp; needs warp_files, the PNG of every row of X in X's order, each with its same-stem
+        CSV): every epoch each frame is first flipped / rotated / shifted as augment_preproc.py does offline -- a fresh
+        draw per frame and epoch, the frame's warp draws ahead of its cutout draws -- at the files' own size
+        (spnet_warp_chain_u8), resized to X's frame size as the input codec resizes (spnet_resize_u8; 'big' frames need
+        none) and then augmented as before; its targets are recomputed from the warped metadata (augmentation.
+        warp_targets) into Y_aug, which fit() trains on (Model.set_train_targets).  A frame whose warp would put a third
+        ellipse into a grid cell keeps its unwarped pixels and targets for that epoch (counted, printed once per epoch).
+        The cutout fill range stays that of the unwarped frame.  warp=False (default): nothing of this exists, the RNG
+        stream and the frames are what they were."""
         super().__init__()
         import torch
         from . import parallel
@@ -113,11 +122,68 @@ class AugmentOnTheFly(Callback):
         self.X_aug = self.X_orig.clone()      # rows no epoch has augmented yet hold the pristine frame, not garbage
         self.augmenter = DeviceAugmenter(self.X_orig, real_blur=real_blur, bandpass_real=bandpass_real,
                                          bpmix_prob=bpmix_prob)
+        self.warper = None
+        self.rejected = 0                     # frames of the last augmented epoch whose warp was rejected
+        if warp:
+            self._setup_warp(warp_files, pred_grid, dev)
+
+    def _setup_warp(self, warp_files, pred_grid, dev):
+        import torch
+        from .augmentation import DeviceWarper
+        n = int(self.X_orig.shape[0])
+        if warp_files is None or len(warp_files) != n:
+            raise ValueError("AugmentOnTheFly(warp=True) needs warp_files: the PNG file of each of the %d training frames" % n)
+        if self.X_orig.dim() != 4 or self.X_orig.shape[-1] != 1:
+            raise ValueError("AugmentOnTheFly(warp=True) is for one-channel frames [N,H,W,1]")
+        files = list(warp_files)
+        X_full, _ = utils.build_X(n, files, grayscale=True, as_uint8=True, device_resize=True)
+        meta = [utils.read_metadata(os.path.splitext(f)[0] + cf.meta_extension) for f in files]
+        self.warper = DeviceWarper(torch.from_numpy(X_full[..., 0]).to(dev), meta, pred_grid=pred_grid)
+        Yh = self.Y.detach().cpu().numpy() if isinstance(self.Y, torch.Tensor) else np.asarray(self.Y)
+        self.Y_aug = torch.from_numpy(np.ascontiguousarray(Yh, dtype=np.float32)).to(dev)
+        self._y_upload = None
+        self.label_seconds = 0.0              # host time of the last epoch's draws' targets (tools/warp_time.py)
+
+    def _augment_chunk(self, idx, seeds, out):
+        """out[j] = augmented frame idx[j] (device [B,h,w,1]); with warp: warped first, and -> (Y [B,576] device, number
+        of rejected frames), else None."""
+        import torch
+        from . import _lib as L
+        aug, wr = self.augmenter, self.warper
+        if wr is None:
+            aug.apply(aug.draw(idx, seeds=seeds), out)
+            return None
+        wp = wr.new_params(idx)
+        p = aug.draw(idx, seeds=seeds, before=lambda j, i: wr.draw_into(wp, j))
+        t0 = time.time()
+        Y, rejected = wr.targets(wp)
+        self.label_seconds += time.time() - t0
+        B, dev = len(idx), self.X_aug.device
+        warped = torch.empty((B, aug.H, aug.W), dtype=torch.float32, device=dev)
+        if (wr.H, wr.W) == (aug.H, aug.W):
+            wr.apply(wp, out_f=warped)
+        else:
+            from .resize import resize_u8_device
+            full = torch.empty((B, wr.H, wr.W), dtype=torch.uint8, device=dev)
+            wr.apply(wp, out_u8=full)
+            resize_u8_device(full, (aug.H, aug.W), out_f=warped)
+        aug.apply(p, out, src=warped)
+        if self._y_upload is None:
+            self._y_upload = L.AsyncUploader(dev)
+        self.last_warp = wp
+        return self._y_upload("Y", Y), int(rejected.sum())
+
+    def _report_rejected(self):
+        if self.warper is not None:
+            print("   Augmenting on the fly: %d warps rejected (a third ellipse in one grid cell): those frames keep their "
+                  "unwarped targets this epoch" % self.rejected)
 
     def set_model(self, model):
         super().set_model(model)
         if hasattr(model, "set_train_frames"):
             model.set_train_frames(self.X, self.X_aug)
+        if self.warper is not None and hasattr(model, "set_train_targets"):
+            model.set_train_targets(self.Y, self.Y_aug)
 
     def on_epoch_begin(self, epoch, logs=None):
         if 0 != epoch % self.aug_every:
@@ -126,12 +192,17 @@ class AugmentOnTheFly(Callback):
         if shard is not None:
             return self._augment_shard(np.asarray(shard), getattr(self.model, "_epochs_seen", epoch))
         n = self.X_orig.shape[0]
+        self.rejected, self.label_seconds = 0, 0.0
         for lo in range(0, n, self.chunk):
             hi = min(n, lo + self.chunk)
             if (lo // self.chunk) % 16 == 0 or hi == n:
                 print("   Augmenting on the fly: ", hi, "/", n, "\r", sep="", end="")
-            self.augmenter.augment(list(range(lo, hi)), self.X_aug[lo:hi])
+            res = self._augment_chunk(list(range(lo, hi)), None, self.X_aug[lo:hi])
+            if res is not None:
+                self.Y_aug[lo:hi].copy_(res[0])
+                self.rejected += res[1]
         print("")
+        self._report_rejected()
 
 
     def _augment_shard(self, shard, epoch):
@@ -141,13 +212,19 @@ class AugmentOnTheFly(Callback):
         import torch
         from . import parallel
         tmp = None
+        self.rejected, self.label_seconds = 0, 0.0
         for lo in range(0, len(shard), self.chunk):
             idx = shard[lo:lo + self.chunk]
             if tmp is None or tmp.shape[0] != len(idx):
                 tmp = torch.empty((len(idx),) + tuple(self.X_aug.shape[1:]), device=self.X_aug.device)
             seeds = [parallel.sample_seed(self.seed, epoch, i) for i in idx]
-            self.augmenter.apply(self.augmenter.draw(list(idx), seeds=seeds), tmp)
-            self.X_aug.index_copy_(0, torch.as_tensor(idx, dtype=torch.int64, device=self.X_aug.device), tmp)
+            res = self._augment_chunk(list(idx), seeds, tmp)
+            where = torch.as_tensor(idx, dtype=torch.int64, device=self.X_aug.device)
+            self.X_aug.index_copy_(0, where, tmp)
+            if res is not None:
+                self.Y_aug.index_copy_(0, where, res[0])
+                self.rejected += res[1]
+        self._report_rejected()
 
 
 # ----------------------------------------------------------------------------- checkpoints

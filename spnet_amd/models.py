@@ -243,6 +243,7 @@ class Model:
         self._engines = {}
         self._root = None
         self._train_frames = None          # (id of host array, device tensor) registered by AugmentOnTheFly
+        self._train_targets = None         # likewise for the targets (AugmentOnTheFly(warp=True) rewrites them per epoch)
         self._uploaded = {}
         self._rings = {}                   # predict(): pinned staging rings per (batch size, device)
         self._epochs_seen = 0              # epochs trained so far (over all fit() calls): the shard permutation's index
@@ -354,6 +355,11 @@ class Model:
     def set_train_frames(self, host_array, device_tensor):
         """AugmentOnTheFly registers the device tensor that shadows the host training array."""
         self._train_frames = (id(host_array), device_tensor)
+
+    def set_train_targets(self, host_Y, device_tensor):
+        """AugmentOnTheFly(warp=True) registers the device tensor [N, Y0size] float32 that shadows the host targets:
+        fit(X, host_Y) reads its batches' targets from it (looked up by id(host_Y) after the epoch-begin callbacks)."""
+        self._train_targets = (id(host_Y), device_tensor)
 
     def _device_frames(self, X):
         torch = _torch()
@@ -521,6 +527,10 @@ class Model:
             for cb in callbacks:
                 cb.on_epoch_begin(epoch, {})
             Xd = self._device_frames(X)
+            if self._train_targets is not None and self._train_targets[0] == id(Y):
+                Yd = self._train_targets[1]
+                if Yd.dtype != torch.float32 or not Yd.is_contiguous() or tuple(Yd.shape) != (N, self.Y0size):
+                    raise ValueError("fit(): the registered training targets must be contiguous float32 [%d, %d]" % (N, self.Y0size))
             if Xd.dtype == torch.uint8:
                 # grey levels: the same scaling predict() applies to uint8 frames (utils.py:340-342) -- a container must
                 # not change what the network sees

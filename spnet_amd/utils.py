@@ -2,6 +2,7 @@
 
   grid codec      setup_means_and_ranges, true_to_pred_grid, norm_Y, denorm_Y   (utils.py:144-244)
   metadata        parse_meta_file, build_Y                                      (utils.py:260-320)
+                  read_metadata (raw rows for the warps)                        (augment_preproc.py:25-38)
   frames          build_X (PNG -> float32 [N,H,W,1] in [-1,1]), build_dataset   (utils.py:325-482)
   outputs         cleanup_antinode_vars, show_pred_ellipses (overlay PNGs + hawley_spnet.csv)
                                                                                 (utils.py:56-137)
@@ -115,6 +116,20 @@ def parse_meta_file(meta_filename):
             t = 2 * np.deg2rad(angle)
             out.append([cx, cy, a, b, np.cos(t), np.sin(t), 0, rings])
     return sorted(out, key=itemgetter(0, 1))
+
+
+def read_metadata(meta_filename):
+    """CSV rows cx,cy,a,b,angle,rings as augment_preproc.py:25-38 reads them for warping: duplicates dropped, angle as
+    float, sorted by (cx, cy); no a/b swap and no ring filter (parse_meta_file applies those when the file is loaded)."""
+    try:
+        df = pd.read_csv(meta_filename, header=None, names=['cx', 'cy', 'a', 'b', 'angle', 'rings'])
+    except pd.errors.EmptyDataError:
+        return []
+    df.drop_duplicates(inplace=True)
+    arrs = []
+    for _, row in df.iterrows():        # (iterrows: a row's values share one dtype, as in the reference)
+        arrs.append([row['cx'], row['cy'], row['a'], row['b'], float(row['angle']), row['rings']])
+    return sorted(arrs, key=itemgetter(0, 1))
 
 
 def build_Y(total_load, meta_file_list, img_file_list, pred_grid=[6, 6, 2], set_means_ranges=False):

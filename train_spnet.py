@@ -22,7 +22,7 @@ from predict_spnet import default_image_dir, predict_network
 
 def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch_size=32, epochs=30, pred_grid=[6, 6, 2],
                   noaugment=False, log_dir=".", lr_max=4e-5, freeze_fac=0.7, frozen_epochs=4, random_seed=1,
-                  augment_blur=False, bp_real=None, bpmix_prob=0.3):
+                  augment_blur=False, bp_real=None, bpmix_prob=0.3, warp=False):
     np.random.seed(random_seed)
     # Data parallel (launched by torch.distributed.run): choose this rank's GPU and join the process group before
     # anything touches the device; rank 0 alone logs, validates and writes checkpoints.
@@ -51,7 +51,8 @@ def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch
         print("Adding callback for augment on the fly")
         callback_list.append(callbacks.AugmentOnTheFly(X_train, Y_train, aug_every=1, seed=random_seed,
                                                        real_blur=augment_blur, bandpass_real=bp_real,
-                                                       bpmix_prob=bpmix_prob))
+                                                       bpmix_prob=bpmix_prob, warp=warp, pred_grid=pred_grid,
+                                                       warp_files=list(train_file_list[:X_train.shape[0]]) if warp else None))
 
     fit_args = dict(batch_size=batch_size, shuffle=True, verbose=1, validation_data=(X_val, Y_val), callbacks=callback_list)
     if frozen_epochs > 0 and freeze_fac > 0.0:        # warm-up phase with the first layers frozen
@@ -96,6 +97,11 @@ if __name__ == '__main__':
     p.add_argument('--bp_real', default=None,
                    help="directory of real ESPI *.png frames (the training frames' size): band-pass mix-up on the fly")
     p.add_argument('--bpmix_prob', type=float, default=0.3, help="probability of the band-pass mix-up per frame")
+    p.add_argument('--warp', action='store_true',
+                   help="warp every training frame afresh each epoch (random flip, rotation of +-20 degrees, shift of up to "
+                        "+-40 px: what augment_preproc.py writes offline) and recompute its targets.  NEEDS the PNG + CSV "
+                        "files of Train/ on disk: the frames are warped at their full size and the targets come from the "
+                        "CSV rows.  Ignored with --noaugment")
     args = p.parse_args()
     print("Command line ~= \n", ' '.join(sys.argv))
     print("args = ", args)
@@ -113,7 +119,7 @@ if __name__ == '__main__':
                           batch_size=args.batch_size, epochs=args.epochs, pred_grid=pred_grid, noaugment=args.noaugment,
                           log_dir=log_dir, lr_max=args.lrmax, freeze_fac=args.freeze_fac,
                           frozen_epochs=args.frozen_epochs, random_seed=args.random_seed,
-                          augment_blur=args.augment_blur, bp_real=args.bp_real, bpmix_prob=args.bpmix_prob)
+                          augment_blur=args.augment_blur, bp_real=args.bp_real, bpmix_prob=args.bpmix_prob, warp=args.warp)
 
     if int(os.environ.get("RANK", "0")) == 0:
         print("\n----------------------------\nStarting model evaluation...")

@@ -143,6 +143,71 @@ def test_device_map_matches_host_metric():
     assert D.calc_map(Yt, Yt, device=True) == 1.0
 
 
+def test_device_iou_at_the_canvas_borders():
+    """spnet_ellipse_iou on a 64 x 48 canvas, where its bounding-box clipping works: ellipses cut by each border and by
+    a corner, entirely outside, wider than the canvas, and the noobj thresholds from both sides -- against the host raster
+    of diagnostics.create_ellipse_image at the same canvas size.  Same bound as on the 512 x 384 canvas; the same pairs are
+    kept (IoU >= 0) and dropped (-1)."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from spnet_amd import _lib as L
+    from spnet_amd import diagnostics as D
+    nx, ny = 64, 48
+
+    def tup(cx, cy, a_, b_, ang, noobj=0.0):
+        return [cx, cy, a_, b_, np.cos(2 * np.deg2rad(ang)), np.sin(2 * np.deg2rad(ang)), noobj, 1.0]
+
+    inside = tup(30.4, 22.7, 14.3, 8.2, 35.5)
+    pairs = [
+        (tup(3.3, 24.6, 12.4, 6.3, 20.5), tup(5.1, 23.2, 11.7, 7.2, 31.2)),          # cut by the left border
+        (tup(60.7, 20.3, 10.2, 7.4, 160.5), tup(62.2, 22.1, 11.3, 6.1, 150.2)),       # right
+        (tup(30.2, 2.4, 9.3, 6.2, 70.3), tup(28.6, 1.1, 10.4, 5.3, 80.1)),            # top
+        (tup(33.6, 45.8, 12.1, 5.2, 100.4), tup(35.2, 47.3, 11.2, 6.4, 95.3)),        # bottom
+        (tup(61.3, 46.2, 9.4, 8.1, 45.2), tup(63.8, 47.9, 10.3, 7.2, 50.6)),          # the bottom-right corner
+        (tup(-2.4, -1.3, 8.2, 6.1, 130.2), tup(-4.1, 1.2, 9.3, 5.4, 120.7)),          # centres outside, past the top-left corner
+        (tup(200.5, 24.2, 10.1, 5.3, 10.2), inside),                                  # prediction entirely outside: IoU 0
+        (inside, tup(31.2, -40.6, 10.3, 5.1, 15.4)),                                  # truth entirely outside: IoU 0
+        (tup(200.5, 24.2, 10.1, 5.3, 10.2), tup(31.2, 90.6, 10.3, 5.1, 15.4)),        # both outside: both rasters empty, -1
+        (tup(29.1, 23.4, 13.2, 9.1, 30.2, noobj=0.49), inside),                       # predicted noobj just below 0.5: drawn
+        (tup(29.1, 23.4, 13.2, 9.1, 30.2, noobj=0.51), inside),                       # just above: empty raster, IoU 0
+        (tup(29.1, 23.4, 13.2, 9.1, 30.2, noobj=0.51), tup(200.5, 24.2, 10.1, 5.3, 10.2)),   # empty and outside: -1
+        (inside, tup(29.1, 23.4, 13.2, 9.1, 30.2, noobj=0.99)),                       # true noobj 0.99: not "> 0.99", kept
+        (inside, tup(29.1, 23.4, 13.2, 9.1, 30.2, noobj=0.995)),                      # 0.995: nothing there, -1
+        (tup(30.5, 20.2, 90.3, 70.1, 40.3), tup(32.4, 24.1, 80.2, 15.3, 10.6)),       # a (and b) larger than the canvas
+        (tup(10.2, 40.3, 70.4, 3.2, 60.7), inside),                                   # a long sliver across the canvas
+    ]
+    rs = np.random.RandomState(21)
+    for _ in range(24):
+        t = tup(rs.uniform(-6, 70), rs.uniform(-6, 54), rs.uniform(3, 30), rs.uniform(2, 20), rs.uniform(0, 180))
+        p = list(t)
+        p[0] += rs.randn() * 3
+        p[1] += rs.randn() * 3
+        p[2] *= 1 + rs.randn() * 0.1
+        pairs.append((p, t))
+    Yp, Yt = (np.array([pr[k] for pr in pairs], np.float32) for k in (0, 1))
+
+    def host_iou(args_p, args_t):                    # diagnostics.compute_iou at this canvas size
+        if args_t[-2] > 0.99:
+            return -1
+        img_p, img_t = D.create_ellipse_image(args_p, nx, ny), D.create_ellipse_image(args_t, nx, ny)
+        num_i, num_u = int(np.count_nonzero(img_p & img_t)), int(np.count_nonzero(img_p | img_t))
+        return -1 if num_i == 0 and num_u == 0 else num_i / num_u
+
+    host = np.array([host_iou(p, t) for p, t in zip(Yp, Yt)], np.float64)
+    yp, yt = torch.from_numpy(Yp).cuda(), torch.from_numpy(Yt).cuda()
+    iou = torch.full((len(pairs),), float("nan"), dtype=torch.float64, device="cuda")
+    L.spnet_ellipse_iou(yp.data_ptr(), yt.data_ptr(), len(pairs), nx, ny, iou.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    dev = iou.cpu().numpy()
+    print("host IoU", np.round(host, 4).tolist())
+    print("device - host", (dev - host).tolist())
+    assert host[:6].min() > 0.3 and host[14] > 0.1                       # the border cases overlap for real
+    assert host[[6, 7, 10, 12]].tolist() == [0, 0, 0, 0] and host[[8, 11, 13]].tolist() == [-1, -1, -1] and host[9] > 0.5
+    assert np.array_equal(np.nonzero(dev >= 0)[0], np.nonzero(host >= 0)[0])      # the same pairs kept, the same dropped
+    assert (dev[host < 0] == -1).all()
+    assert np.abs(dev - host).max() < 2e-3, np.abs(dev - host).max()
+
+
 def test_setup_model_checkpoint_semantics_and_whole_model_file(data, tmp_path, monkeypatch):
     """setup_model (models.py:461-507 of the reference): missing checkpoint -> fresh start or plain Exception
     with no_cp_fatal; present -> loaded.  Model.save / load_model round trip of the 'whole model' file."""

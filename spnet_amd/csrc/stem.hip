@@ -462,7 +462,10 @@ __global__ __launch_bounds__(256) void conv1_bwd_data_kernel(const float* __rest
       const int h = 2 * i + ph;
       if (h >= H) continue;
       float* dp = dx + (((long)b * H + h) * W + 2 * j) * 3;
-      if (2 * j + 1 < W) {       // 6 consecutive floats, 8-byte aligned
+      // 6 consecutive floats from float offset ((b*H + h)*W + 2j)*3: even, so 8-byte aligned, when W is even; with W odd
+      // the offset is odd on every row with b*H + h odd and the three 8-byte stores are only 4-byte aligned there, which
+      // global stores of this hardware serve (tests/test_small_kernels_gpu.py, test_block1_conv1, pins those rows)
+      if (2 * j + 1 < W) {
         reinterpret_cast<float2*>(dp)[0] = make_float2(acc[ph][0][0], acc[ph][0][1]);
         reinterpret_cast<float2*>(dp)[1] = make_float2(acc[ph][0][2], acc[ph][1][0]);
         reinterpret_cast<float2*>(dp)[2] = make_float2(acc[ph][1][1], acc[ph][1][2]);

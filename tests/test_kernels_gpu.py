@@ -1,6 +1,7 @@
 """Per-kernel parity: every HIP kernel, called through the C ABI, against the CPU oracle on the same
 seeded inputs.  fp32 tolerances are written next to each check (the kernels and the oracle sum in
-different orders, so agreement is to rounding, not bitwise, except where noted)."""
+different orders, so agreement is to rounding, not bitwise, except where noted).
+The stem head, loss / head and augmentation kernels are pinned one by one in tests/test_small_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch

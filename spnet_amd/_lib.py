@@ -1,19 +1,27 @@
-"""ctypes binding of libspnet_hip.so (C ABI declared in include/spnet_hip.h).
+"""ctypes binding of libspnet_hip.so (C ABI declared in include/spnet_hip.h, which is also the table of signatures:
+the kernels are compiled against it and the bindings below are derived from it by _abi.parse_header).
 
 The product path has NO CPU fallback: importing this module without the built library raises, and
 every wrapper raises on a non-zero HIP status.
 """
 import ctypes
 import os
-from ctypes import POINTER, byref, c_float, c_int, c_long, c_uint, c_void_p
+from ctypes import c_int
+
+from . import _abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPNET_HIP_LIB") or os.path.join(_HERE, "lib", "libspnet_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "spnet_hip.h")
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         "spnet_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
         "or `make -C spnet_amd/csrc` (hipcc, gfx950).  There is no CPU fallback." % LIB_PATH)
+if not os.path.exists(HEADER_PATH):
+    raise ImportError(
+        "spnet_amd: %s is missing -- it declares the C ABI of the library, and the bindings are derived from it.  "
+        "There is no second table of signatures." % HEADER_PATH)
 
 # torch first: libspnet_hip.so must bind to the SAME HIP runtime (libamdhip64) that torch has loaded, or
 # the two runtimes would not share devices / streams (kernels then fail with hipErrorNoDevice).
@@ -22,137 +30,8 @@ import torch  # noqa: E402,F401
 
 _lib = ctypes.CDLL(LIB_PATH)
 
-P = c_void_p  # device pointers travel as integers
-
-_SIGS = {
-    "spnet_gemm_f32": (c_int, [P, c_int, c_int, P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_int, P]),
-    "spnet_bf16x3_kp": (c_long, [c_int]),
-    "spnet_bf16x3_plane_elems": (c_long, [c_long, c_int]),
-    "spnet_split_bf16x3": (c_int, [P, P, c_int, c_int, P]),
-    "spnet_split_rows_bf16x3": (c_int, [P, c_long, P, c_long, c_int, P]),
-    "spnet_gemm_bf16x3_pp": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P]),
-    "spnet_gemm_bf16x3_wgrad_ksplit": (c_long, [c_int, c_int, c_int, c_int]),
-    "spnet_gemm_bf16x3_dwbwd_rows": (c_long, [c_long]),
-    "spnet_gemm_bf16x3_dwbwd_ok": (c_long, [c_int, c_int, c_int]),
-    "spnet_gemm_bf16x3_pp_dwbwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, P, P, P, P, P, P]),
-    "spnet_gemm_bf16x3_pp_dwfwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P]),
-    "spnet_gemm_bf16x3_wgrad_batched": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_split_bf16x3_batched": (c_int, [P, c_int, c_long, P]),
-    "spnet_gemm_bf16x3_fwd": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
-    "spnet_gemm_bf16x3_fwd_colstats": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P, P, P]),
-    "spnet_gemm_f32_accumulate": (c_int, [P, c_int, c_int, P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_conv3x3_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_conv3x3_dgrad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_conv3x3_wgrad_ws": (c_long, [c_int, c_int, c_int, c_int, c_int]),
-    "spnet_conv3x3_wgrad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_long, P]),
-    "spnet_reduce_slabs": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
-    "spnet_transpose_batched": (c_int, [P, c_int, c_int, c_int, P]),
-    "spnet_gather_s2": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
-    "spnet_scatter_add_s2": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
-    "spnet_dwconv3x3_strided_ws": (c_long, [c_int, c_int, c_int, c_int, c_int]),
-    "spnet_dwconv3x3_strided": (c_int, [c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "spnet_reduce_rows": (c_int, [P, c_int, c_int, P, P]),
-    "spnet_reduce_rows_ws": (c_int, [P, c_int, c_int, P, P, c_long, P]),
-    "spnet_reduce_rows_batched": (c_int, [P, c_int, c_int, P]),
-    "spnet_dwconv3x3_tiled_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
-    "spnet_dwconv3x3_tiled_fwd_bnfin": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_long, P, P, P, P, P, P, P,
-                                                c_float, c_float, P]),
-    "spnet_dwconv3x3_tiled_fwd_x3": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
-    "spnet_dwconv3x3_tiled_fwd_bnfin_x3": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_long, P, P, P, P, P, P, P,
-                                                   c_float, c_float, P]),
-    "spnet_dwconv3x3_stream_fwd_x3": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P]),
-    "spnet_dwconv3x3_tiled_bwd_ws": (c_long, [c_int, c_int, c_int, c_int]),
-    "spnet_dwconv3x3_tiled_rows": (c_long, [c_int, c_int, c_int, c_int]),
-    "spnet_dwconv3x3_tiled_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P]),
-    "spnet_dwconv3x3_prefers_stream": (c_long, [c_int, c_int, c_int, c_int, c_int]),
-    "spnet_dwconv3x3_stream_rows": (c_long, [c_int, c_int, c_int, c_int, c_int]),
-    "spnet_dwconv3x3_stream_bwd_ws": (c_long, [c_int, c_int, c_int, c_int, c_int]),
-    "spnet_dwconv3x3_stream_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P]),
-    "spnet_dwconv3x3_stream_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P]),
-    "spnet_bn_finalize_fwd": (c_int, [P, c_int, c_long, c_int, P, P, P, P, P, P, P, c_float, c_float, P]),
-    "spnet_bn_infer_coeffs": (c_int, [c_int, P, P, P, P, P, c_float, P]),
-    "spnet_bn_apply": (c_int, [P, c_long, c_int, P, c_int, P, c_int, P, P]),
-    "spnet_bn_finalize_apply": (c_int, [P, c_int, P, c_long, c_int, P, P, P, P, P, P, P, c_int, P, P, c_float, c_float, P]),
-    "spnet_bn_finalize_apply_ld": (c_int, [P, c_int, P, c_long, c_int, P, P, P, P, P, P, P, c_int, P, P, c_long, c_float, c_float, P]),
-    "spnet_bn_bwd_from_partials": (c_int, [P, P, c_long, c_int, P, P, P, P, c_int, P, P, P, P, P, P]),
-    "spnet_bn_bwd_from_partials_x3": (c_int, [P, P, c_long, c_int, P, P, P, P, c_int, P, P, P, P, P, P]),
-    "spnet_bn_bwd_x3": (c_int, [P, P, c_long, c_int, P, P, P, P, c_int, P, P, P, P, P, P]),
-    "spnet_gemm_f32_colstats": (c_int, [P, c_int, c_int, P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
-    "spnet_gemm_f32_bnblend": (c_int, [P, P, P, c_int, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "spnet_bn_bwd_coeffs_from_partials": (c_int, [c_int, P, c_long, c_int, P, P, P, P, P, P, c_int, P]),
-    "spnet_bn_bwd_coeffs": (c_int, [P, P, c_long, c_int, P, P, P, P, P, P, P, c_int, P, P]),
-    "spnet_gemm_f32_batched": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_gemm_batched_ksplit": (c_long, [c_int, c_int, c_int, c_int, P]),
-    "spnet_gemm_f32_batched_splitk": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                              c_int, P, c_long, P]),
-    "spnet_bn_ws": (c_long, [c_long, c_int]),
-    "spnet_bn_fwd_train": (c_int, [P, c_long, c_int, P, P, P, P, P, P, P, c_int, P, c_int, P, c_float, c_float, P, P]),
-    "spnet_bn_fwd_infer": (c_int, [P, c_long, c_int, P, P, P, P, P, c_int, P, c_int, P, c_float, P]),
-    "spnet_bn_fwd_train_ld": (c_int, [P, c_long, c_int, P, P, P, P, P, P, P, c_int, P, c_int, P, c_long, c_float, c_float, P, P]),
-    "spnet_bn_fwd_infer_ld": (c_int, [P, c_long, c_int, P, P, P, P, P, c_int, P, c_int, P, c_long, c_float, P]),
-    "spnet_bn_bwd": (c_int, [P, P, c_long, c_int, P, P, P, P, c_int, P, P, P, P, P, P]),
-    "spnet_maxpool3x3s2_add_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P]),
-    "spnet_maxpool3x3s2_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
-    "spnet_maxpool3x3s2_bwd_rows": (c_long, [c_int, c_int, c_int, c_int, c_int]),
-    "spnet_maxpool3x3s2_bwd_bnsums": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P]),
-    "spnet_maxpool3x3s2_valid_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
-    "spnet_maxpool3x3s2_valid_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
-    "spnet_avgpool3x3s1_same": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_patches": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_patches_ld": (c_int, [P, c_long, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_conv_gemm_f32": (c_int, [P, c_long, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P]),
-    "spnet_grad_bnsums_rows": (c_long, [c_long, c_int]),
-    "spnet_patches_bwd_bnsums": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P,
-                                         c_int, P]),
-    "spnet_copy_cols_bnsums": (c_int, [P, c_int, P, c_long, c_int, P, c_long, P, P, P, c_int, P, c_int, P]),
-    "spnet_patches_bwd_bnsums_ld": (c_int, [P, P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P,
-                                            c_long, P, P, c_int, P, c_long, c_int, P]),
-    "spnet_copy_cols_bnsums_ld": (c_int, [P, c_int, P, c_long, c_long, c_int, P, c_long, P, c_long, P, P, c_int, P, c_long,
-                                          c_int, P]),
-    "spnet_copy_cols_batched": (c_int, [P, c_int, c_long, P]),
-    "spnet_resadd": (c_int, [P, P, P, c_long, c_float, c_int, P]),
-    "spnet_resadd_bwd": (c_int, [P, P, P, P, c_long, c_float, c_int, P]),
-    "spnet_copy_cols": (c_int, [P, c_int, P, c_int, c_long, c_int, c_int, P]),
-    "spnet_avgpool2_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
-    "spnet_avgpool2_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
-    "spnet_conv3x3_small": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, c_long, P]),
-    "spnet_stem_head": (c_int, [c_int, P, P, P, P, c_int, c_int, c_int, P, c_long, P]),
-    "spnet_ellipse_loss": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
-    "spnet_selective_sigmoid": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_decode": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
-    "spnet_ellipse_iou": (c_int, [P, P, c_long, c_int, c_int, P, P]),
-    "spnet_calc_errors": (c_int, [P, P, c_long, c_int, P, P, P]),
-    "spnet_adam_step": (c_int, [P, P, P, P, c_long, c_long, c_float, c_float, c_float, c_float, c_float, c_float, P, P, P, P, P]),
-    "spnet_adam_parts": (c_long, [c_long]),
-    "spnet_adam_part": (c_int, [P, P, P, P, c_long, c_long, c_float, c_float, c_float, c_float, c_float, c_float, P, P, P, P]),
-    "spnet_adam_l2_sum": (c_int, [P, c_int, c_float, P, P]),
-    "spnet_u8_to_input": (c_int, [P, P, c_long, P]),
-    "spnet_resize_u8": (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, P, P]),
-    "spnet_gather_rows": (c_int, [P, c_long, P, c_int, P, c_int, c_long, P]),
-    "spnet_minmax": (c_int, [P, c_int, c_long, P, P, P]),
-    "spnet_cutout": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P]),
-    "spnet_saltpepper": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
-    "spnet_gaussian_blur": (c_int, [P, P, c_int, c_int, c_int, P, P]),
-    "spnet_warp_affine": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
-    "spnet_warp_affine_fixed": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P]),
-    "spnet_warp_chain_u8": (c_int, [P, c_int, P, P, c_int, c_int, c_int, P, P, P]),
-    "spnet_fake_espi": (c_int, [P, P, P, c_int, c_int, c_int, c_uint, c_int, P, P, P]),
-    "spnet_dropout": (c_int, [P, P, c_long, c_uint, c_float, P, P]),
-    "spnet_bandpass_ws": (c_long, [c_int, c_int, c_int]),
-    "spnet_bandpass_project": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
-    "spnet_bandpass_apply": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_int, P, P, P]),
-    "spnet_gemm_f32_bnrelu": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
-    "spnet_pad_nhwc": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
-    "spnet_dense_conv7_ws": (c_long, [c_int, c_int, c_int]),
-    "spnet_dense_conv7": (c_int, [c_int, P, P, P, c_int, c_int, c_int, P, c_long, P]),
-    "spnet_dense_rows": (c_long, [c_long]),
-    "spnet_dense_colsums_ld": (c_int, [P, c_long, c_long, c_int, P, P]),
-    "spnet_dense_coeffs": (c_int, [c_int, c_int, P, P, P, P, P, P, P, P, P, c_float, c_float, c_int, P]),
-    "spnet_dense_apply_ld": (c_int, [P, c_long, c_long, c_int, P, c_int, c_int, P, c_long, P]),
-    "spnet_dense_consumer_bwd": (c_int, [P, c_long, P, c_long, c_long, c_int, P, c_int, P, P, P, c_int, P, c_long, P, P]),
-    "spnet_dense_consumer_fin": (c_int, [P, c_int, c_int, P, P, P, P, P, P]),
-    "spnet_dense_producer_fin": (c_int, [P, c_long, P, P, P, c_long, P, P, c_long, c_int, c_int, P, c_long, P]),
-}
+with open(HEADER_PATH) as _f:
+    _SIGS = _abi.parse_header(_f.read())
 
 EXPORTS = tuple(_SIGS)
 

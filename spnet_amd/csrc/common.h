@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// The C ABI: every extern "C" definition is compiled against its prototype, so a definition that drifts from the header
+// (a type, the order or the number of arguments) is a `conflicting types` error, not a wrong pointer at run time.
+#include "spnet_hip.h"
 
 #define SPNET_WAVE 64
 

@@ -15,6 +15,7 @@ Data layout in HBM
                pointwise [Cin,Cout], dense [in,out]) so checkpoints map 1:1 onto Keras weight names
   BN moving statistics in a second flat buffer (non-trainable, not touched by the optimizer)
 """
+import ctypes
 import math
 import os
 from collections import OrderedDict
@@ -1230,7 +1231,7 @@ def _gemm(A, a_major, lda, Bm, b_major, ldb, C, ldc, M, N, K, eng, bias=None, sp
         prof.keys[len(prof.records) - 1] = (a_major, b_major, 0, M, N, K)
 
 
-_stat_rows = __import__("ctypes").c_int(0)
+_stat_rows = ctypes.c_int(0)
 
 
 def _gemm_colstats(A, lda, Bm, ldb, C, ldc, M, N, K, eng, region=WS_BNP):
@@ -1243,7 +1244,7 @@ def _gemm_colstats(A, lda, Bm, ldb, C, ldc, M, N, K, eng, region=WS_BNP):
         t0 = prof.start()
     L.spnet_gemm_f32_colstats(L.ptr(A), K_MAJOR, lda, L.ptr(Bm), OUT_MAJOR, ldb, L.ptr(C), ldc, M, N, K,
                               _tile_for(K_MAJOR, OUT_MAJOR, 1, M, N, K, 0),
-                              eng.ws_ptr(region), __import__("ctypes").addressof(_stat_rows), _stream())
+                              eng.ws_ptr(region), ctypes.addressof(_stat_rows), _stream())
     if prof is not None:
         prof.stop("gemm", t0, 2.0 * M * N * K, ("aB+stats", M, N, K))
         prof.keys[len(prof.records) - 1] = (K_MAJOR, OUT_MAJOR, 1, M, N, K)
@@ -1445,7 +1446,7 @@ class Pointwise:
             if (self.M + 95) // 96 * 2 * N > colstats_region[1]:
                 raise RuntimeError("BatchNorm partial region too small for M=%d N=%d" % (self.M, N))
             L.spnet_gemm_bf16x3_fwd_colstats(L.ptr(A), lda, L.ptr(planes), L.ptr(C), ldc, self.M, N, K,
-                                             e.ws_ptr(colstats_region), __import__("ctypes").addressof(_stat_rows), _stream())
+                                             e.ws_ptr(colstats_region), ctypes.addressof(_stat_rows), _stream())
             rows = _stat_rows.value
         if prof is not None:
             prof.stop("gemm", t0, 2.0 * self.M * N * K, (tag, self.M, N, K))
@@ -1464,7 +1465,7 @@ class Pointwise:
             if (self.M + 95) // 96 * 2 * N > colstats_region[1]:
                 raise RuntimeError("BatchNorm partial region too small for M=%d N=%d" % (self.M, N))
             L.spnet_gemm_bf16x3_pp(L.ptr(a_planes), L.ptr(b_planes), L.ptr(C), N, self.M, N, K, e.ws_ptr(colstats_region),
-                                   __import__("ctypes").addressof(_stat_rows), _stream())
+                                   ctypes.addressof(_stat_rows), _stream())
             rows = _stat_rows.value
         if prof is not None:
             prof.stop("gemm", t0, 2.0 * self.M * N * K, (tag, self.M, N, K))
@@ -2184,8 +2185,8 @@ class IRv2Backbone(Node):
             for (K, C, M, ldb), members in by_shape.items():
                 if len(members) < 2:
                     continue
-                tile = __import__("ctypes").c_int(0)
-                ksl = int(L.spnet_gemm_batched_ksplit(K, C, M, len(members), __import__("ctypes").addressof(tile)))
+                tile = ctypes.c_int(0)
+                ksl = int(L.spnet_gemm_batched_ksplit(K, C, M, len(members), ctypes.addressof(tile)))
                 for o in members:
                     o.deferred_wgrad = True
                 self.wg_groups.append(dict(members=members, K=K, C=C, M=M, ldb=ldb, ksl=ksl, tile=tile.value, table=None,
@@ -2474,7 +2475,7 @@ class _IRConv:
                                   L.ptr(self.b) if self.bias else None,
                                   _tile_for(K_MAJOR, OUT_MAJOR, 1 if stats else 0, self.M, C, self.K, 0),
                                   e.ws_ptr(WS_BNP) if stats else None,
-                                  __import__("ctypes").addressof(_stat_rows) if stats else None, _stream())
+                                  ctypes.addressof(_stat_rows) if stats else None, _stream())
             if prof is not None:
                 prof.stop("gemm", t0, 2.0 * self.M * C * self.K, ("conv gathered", self.M, C, self.K))
                 prof.keys[len(prof.records) - 1] = (K_MAJOR, OUT_MAJOR, 1 if stats else 0, self.M, C, self.K)

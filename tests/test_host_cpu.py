@@ -32,6 +32,71 @@ def test_library_exports_every_declared_symbol():
     assert set(declared) <= exported
 
 
+def test_abi_parser_types():
+    """The bindings are derived from the header (spnet_amd/_abi.py): every form of parameter and return type the header
+    uses, pinned on one entry each, as the hand-written table had them."""
+    from ctypes import c_float as F, c_int as I, c_long as Lg, c_uint as U, c_void_p as P
+    from spnet_amd import _abi
+    sigs = _abi.parse_header(open(os.path.join(ROOT, "include", "spnet_hip.h")).read())
+    # c_long and six c_float by value
+    assert sigs["spnet_adam_step"] == (I, [P, P, P, P, Lg, Lg, F, F, F, F, F, F, P, P, P, P, P])
+    # `unsigned seed` by value, `const unsigned* seed_dev` a pointer
+    assert sigs["spnet_dropout"] == (I, [P, P, Lg, U, F, P, P])
+    assert sigs["spnet_bn_ws"] == (Lg, [Lg, I])                                   # long return: a query, not a status
+    assert sigs["spnet_gemm_batched_ksplit"] == (Lg, [I, I, I, I, P])             # host `int* tile_out`
+    assert sigs["spnet_gemm_f32_batched"] == (I, [P, P, P, P] + [I] * 10 + [P])   # `const long long* offsets`
+    assert sigs["spnet_maxpool3x3s2_add_fwd"] == (I, [P, P, P, P, I, I, I, I, P, P, P])     # `uint32_t* idx4`
+    assert sigs["spnet_gemm_bf16x3_pp_dwbwd"] == (I, [P, P, I, I, I, I, I, P, P, P, I] + [P] * 9)
+    assert len(sigs["spnet_gemm_bf16x3_pp_dwbwd"][1]) == 20
+    for name, (restype, argtypes) in sigs.items():      # nothing but the five ctypes the table ever held
+        assert restype in (I, Lg) and all(any(a is t for t in (P, I, Lg, F, U)) for a in argtypes), name
+
+
+def test_abi_parser_fails_closed():
+    """A prototype the reader does not understand is an error, never skipped or guessed."""
+    from ctypes import c_float, c_int, c_long, c_void_p
+    from spnet_amd._abi import parse_header
+    ok = '''/* spnet_foo(int a); a comment; with spnet_bar( and stray ; inside */
+#ifndef X
+#include <stdint.h>
+extern "C" {
+// int spnet_gone(int a);
+int spnet_a(const float* x, long n,   /* mid; comment */ float eps, void* stream);
+long spnet_b(int n);
+}
+#endif
+'''
+    assert parse_header(ok) == {"spnet_a": (c_int, [c_void_p, c_long, c_float, c_void_p]), "spnet_b": (c_long, [c_int])}
+    assert list(parse_header(ok)) == ["spnet_a", "spnet_b"]
+    for bad in ("int spnet_a(double x);",                         # by-value type the header does not use
+                "int spnet_a(long long n);",
+                "int spnet_a(struct dim3 g);",                    # by-value struct
+                "int spnet_a(dim3_t g);",
+                "void spnet_a(int n);",                           # return type
+                "float* spnet_a(int n);",
+                "int spnet_a(void (*cb)(int), int n);",           # function pointer
+                "int spnet_a(int v[4]);",                         # array
+                "int spnet_a(float* v[4]);",
+                "int spnet_a(n);",                                # no type
+                "int spnet_a(int);",                              # no name: `unsigned int` / `long long` would be misread
+                "int spnet_a(int n); typedef int t;",             # not a prototype
+                "int spnet_a(int n); int x;",
+                "int spnet_a(int n); struct s { int a; };",
+                "int other_a(int n);",
+                "int spnet_a(int n); int spnet_a(long n);",       # declared twice
+                "int spnet_a(int n) int spnet_b(int n);"):        # missing `;`
+        with pytest.raises(ValueError):
+            parse_header(bad)
+
+
+def test_abi_module_is_standalone(tmp_path):
+    """spnet_amd._abi reads a header: no torch, no built library (an external binder, a build step)."""
+    env = dict(os.environ, SPNET_HIP_LIB=str(tmp_path / "no_such_lib.so"))
+    r = subprocess.run([sys.executable, "-c", "import spnet_amd._abi, sys; assert 'torch' not in sys.modules"],
+                       capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
 def test_product_has_no_oracle_imports():
     for dirpath, _, files in os.walk(os.path.join(ROOT, "spnet_amd")):
         for f in files:

@@ -478,6 +478,31 @@ int spnet_dropout(const float* x, float* y, long n, unsigned seed, float rate, c
  * the uint8 frame. */
 int spnet_fake_espi(const float* waves, const float* nodes, const int* nnode, int N, int H, int W, unsigned seed,
                     int noise, float* out_f, unsigned char* out_u8, void* stream);
+/* The parameters themselves, drawn on the device (csrc/espi_params.hip): writes waves [N][5], nodes [N][7][8] (every
+ * element; unused slots are zeros, valid = column 7) and nnode [N] for the global frames first_frame .. first_frame + N - 1,
+ * in the layout spnet_fake_espi reads.  Same logic as the host's draw_params (draw_waves, gen_fake_espi.py:60-80;
+ * draw_antinodes :145-206), its own random stream.  tries (or NULL) [N][7]: per antinode DRAWN, the try that was accepted,
+ * -1 = dropped after 2000 tries, -2 = not drawn (index >= the frame's count).  trig2 [181][2] = (cos^2, sin^2) of the whole
+ * degrees 0..180, computed in float64 and rounded to float.  N == 0: nothing to do, success.  hipErrorInvalidValue (nothing
+ * launched): N < 0, first_frame < 0, H or W outside 64 .. 2048, count_lo < 0, count_lo > count_hi, count_hi > 7, a NULL
+ * trig2 / waves / nodes / nnode.
+ * The stream, stateless and counter based -- frame g's parameters depend on (seed, g) only:
+ *   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16      (uint32)
+ *   fkey(g) = mix(mix(mix(seed ^ 0x9e3779b9) + low32(g)) ^ high32(g))
+ *   key(slot, t) = mix(fkey + (slot << 12 | t)): slot 0 = the frame's draws (t = 0), slot j + 1 = antinode j, try t
+ *   u(key, k) = mix(key ^ (k * 0x85ebca6b + 0xc2b2ae35)), draw index k
+ *   randint(u, lo, hi) = lo + ((uint64)u * max(hi - lo + 1, 1) >> 32)              (an empty range gives lo)
+ *   frame (slot 0): k 0 amp [10, 200]; 1 wavelength [100, W/2]; 2 thick [15, 40]; 3 U = (u >> 8) * 2^-24, slope =
+ *     3 * (U - 0.5) in float; 4 spacing [thick + thick * int(|1.5 * slope|), H/3]; 5 count [count_lo, count_hi]
+ *   antinode j, try t (0 .. 1999): k 0, 1 the axes, [15, 2W/7] and [15, 2H/7] at t = 0, [25, W/3] and [25, H/3] at t > 0 (integer
+ *     divisions), a = the larger, b = the smaller; k 2 (t = 0 only) rings [1, min(b/8, 11)]; k 3 cx [a, W - a]; k 4 cy
+ *     [b, H - b]; k 5 angle [1, 179] at t = 0, [1, 180] at t > 0; k 6 of t = 0: start = u >> 31
+ *   box of a try: dx = sqrt(a^2 cos^2 + b^2 sin^2), dy = sqrt(a^2 sin^2 + b^2 cos^2) in float, each product and sum rounded
+ *     on its own, the root correctly rounded; x0 = cx - dx, x1 = cx + dx, y0, y1 likewise.  The try passes when
+ *     x0 >= 0, x1 <= W, y0 >= 0, y1 <= H and no accepted box q of the frame has NOT (x1 < q.x0 | x0 > q.x1 | y1 < q.y0 | y0 > q.y1).
+ *   The first passing try is accepted; its ring count is min(rings drawn at t = 0, b_s / 4 of every try s <= t). */
+int spnet_fake_espi_params(long first_frame, int N, int H, int W, unsigned seed, int count_lo, int count_hi,
+                           const float* trig2, float* waves, float* nodes, int* nnode, int* tries, void* stream);
 
 /* ---- band-pass mix-up (spnet/augmentation.py:10-62; csrc/bandpass.hip) ------------------------------------------- */
 /* Frames x [*][H][W], one channel, 16 <= H, W <= 2048; x_kind 0 = uint8, 1 = fp32 pixel units (0..255), 2 = fp32 network

@@ -9,6 +9,7 @@
   OneCycleScheduler           callbacks.py:346-406 -- per-batch learning-rate table
   MyProgressCallback          callbacks.py:58-265 -- validation predict, per-term losses.dat, count
                               metrics, progress.png, overlay drawings
+  FreshFakeESPI               (additive) a fresh synthetic training set every epoch, generated in HBM
   ParallelCheckpointCallback  callbacks.py:20-41 -- weights + full-model checkpoints every N epochs
 """
 import os
@@ -225,6 +226,48 @@ class AugmentOnTheFly(Callback):
                 self.Y_aug.index_copy_(0, where, res[0])
                 self.rejected += res[1]
         self._report_rejected()
+
+
+class FreshFakeESPI(Callback):
+    """Each epoch: a FRESH set of synthetic training frames and targets from a fake_espi.FakeStream -- no files, and no
+    frame is ever seen twice.  fit(X, Y) is called with this callback's X and Y (placeholders that only identify the
+    training set: with X=None, cb.X is the device frame tensor itself -- no host copy of the frames is ever made -- and with
+    Y=None, cb.Y is a host copy of the first targets); the frames fit() reads are cb.X_dev [n,H,W,1] and the targets cb.Y_dev
+    [n, n_targets], registered through Model.set_train_frames / set_train_targets and refilled by stream.epoch() at every
+    epoch begin.  The stream epoch is first_epoch + the number of epochs this callback has begun so far (it keeps counting
+    over several fit() calls and over a change of model, as train_spnet.py's unfreeze makes).  Until the first epoch begins
+    the tensors hold epoch first_epoch's frames, never garbage.
+
+    Data parallel: every rank generates the same n frames (same seed, same epoch) into its own tensors and fit()'s
+    sharding picks this rank's samples; no collective is added.
+
+    With AugmentOnTheFly: build it on the DEVICE tensor, AugmentOnTheFly(cb.X_dev, cb.Y, ...), call fit(cb.X_dev, cb.Y, ...)
+    and list this callback BEFORE it.  Order within an epoch: this callback writes the fresh frames into cb.X_dev, which is
+    the augmenter's pristine set (it keeps a device tensor as it is); AugmentOnTheFly then writes cutout / salt and pepper
+    / blur / band-pass mix-up of them into its X_aug, which is what fit() reads (it registers last).  The cutout fill
+    range is the min / max of the frames AugmentOnTheFly was built on (epoch first_epoch's; a noisy fake-ESPI frame spans
+    the whole range).  warp=True is not meant for streamed frames (it needs files)."""
+
+    def __init__(self, X, Y, stream, first_epoch=0, verbose=True):
+        super().__init__()
+        self.stream, self.first_epoch, self.verbose = stream, int(first_epoch), verbose
+        self.X_dev, self.Y_dev = stream.epoch(self.first_epoch, verbose=False)
+        self.X = self.X_dev if X is None else X
+        self.Y = self.Y_dev.cpu().numpy() if Y is None else Y
+        if tuple(self.X.shape) != tuple(self.X_dev.shape) or tuple(self.Y.shape) != tuple(self.Y_dev.shape):
+            raise ValueError("FreshFakeESPI: X / Y are %s / %s, the stream yields %s / %s"
+                             % (tuple(self.X.shape), tuple(self.Y.shape), tuple(self.X_dev.shape), tuple(self.Y_dev.shape)))
+        self.epochs_filled = []             # the stream epochs generated so far (first_epoch's initial fill not counted)
+
+    def set_model(self, model):
+        super().set_model(model)
+        model.set_train_frames(self.X, self.X_dev)
+        model.set_train_targets(self.Y, self.Y_dev)
+
+    def on_epoch_begin(self, epoch, logs=None):
+        e = self.first_epoch + len(self.epochs_filled)
+        self.stream.epoch(e, self.X_dev, self.Y_dev, verbose=self.verbose and getattr(self.model, "rank", 0) == 0)
+        self.epochs_filled.append(e)
 
 
 # ----------------------------------------------------------------------------- checkpoints

@@ -129,18 +129,69 @@ def gen_frame(seed):
     return a.astype(np.uint8), [n[:6] for n in nodes]
 
 
-def frame_seeds(n, seed):
-    return [seed * 1000003 + i for i in range(n)]
+def frame_seeds(n, seed, first=0):
+    return [seed * 1000003 + i for i in range(first, first + n)]
 
 
-def bandpass_seeds(n, seed):
+def bandpass_seeds(n, seed, first=0):
     """Seeds of the per-frame band-pass draws: a hash of the frame seed, not the seed itself (the frame's own streams
     stay as they are)."""
-    return [((s * 2654435761) ^ 0x5BD1E995) % (2 ** 32) for s in frame_seeds(n, seed)]
+    return [((s * 2654435761) ^ 0x5BD1E995) % (2 ** 32) for s in frame_seeds(n, seed, first)]
+
+
+_TRIG2 = {}
+
+
+def trig2_table(device=None):
+    """(cos^2, sin^2) of the whole degrees 0..180 as float32 [181,2], computed in float64: the table the device sampler's
+    box test reads (spnet_fake_espi_params; no sinf / cosf on the device, so a host restatement has the same bits).
+    device: a cached device tensor instead of the numpy array."""
+    if "host" not in _TRIG2:
+        rad = np.radians(np.arange(181, dtype=np.float64))
+        _TRIG2["host"] = np.stack([np.cos(rad) ** 2, np.sin(rad) ** 2], 1).astype(np.float32)
+    if device is None:
+        return _TRIG2["host"]
+    import torch
+    key = str(torch.device(device))
+    if key not in _TRIG2:
+        _TRIG2[key] = torch.from_numpy(_TRIG2["host"]).to(device)
+    return _TRIG2[key]
+
+
+def draw_params_device(n, seed=0, device="cuda:0", count_range=(1, 7), first_frame=0, want_tries=False):
+    """The parameters of the global frames first_frame .. first_frame + n - 1 drawn by spnet_fake_espi_params (csrc/
+    espi_params.hip): (waves [n,5], nodes [n,7,8], nnode [n]) device tensors in the layout spnet_fake_espi reads
+    [, tries [n,7] int32: the accepted try per antinode drawn, -1 dropped, -2 not drawn].  Same logic and distributions as
+    draw_params, a stream of its own (counter based: a frame's parameters depend on (seed, its global index) only -- not on
+    n, nor on how a range of frames is split into calls).  Enqueued on the current stream; nothing is copied to the host."""
+    import torch
+    from . import _lib as L
+    dev = torch.device(device)
+    waves = torch.empty((n, 5), dtype=torch.float32, device=dev)
+    nodes = torch.empty((n, 7, 8), dtype=torch.float32, device=dev)
+    nnode = torch.empty((n,), dtype=torch.int32, device=dev)
+    tries = torch.empty((n, 7), dtype=torch.int32, device=dev) if want_tries else None
+    with torch.cuda.device(dev):
+        L.spnet_fake_espi_params(int(first_frame), n, IM_H, IM_W, int(seed) & 0xFFFFFFFF, int(count_range[0]),
+                                 int(count_range[1]), trig2_table(dev).data_ptr(), waves.data_ptr(), nodes.data_ptr(),
+                                 nnode.data_ptr(), L.ptr(tries), torch.cuda.current_stream(dev).cuda_stream)
+    return (waves, nodes, nnode, tries) if want_tries else (waves, nodes, nnode)
+
+
+def labels_from_params(nodes, nnode):
+    """Label rows [[(cx, cy, a, b, angle, rings), ...], ...] (Python ints, what generate_device returns) of device (or
+    host) parameter arrays nodes [n,7,8], nnode [n]; device tensors cross to the host in ONE copy."""
+    if hasattr(nodes, "is_cuda"):
+        import torch
+        n = int(nnode.shape[0])
+        packed = torch.cat([nodes.reshape(n, 56), nnode.reshape(n, 1).to(torch.float32)], 1).cpu().numpy()
+        nodes, nnode = packed[:, :56].reshape(n, 7, 8), packed[:, 56]
+    rows = np.asarray(nodes)[:, :, :6].astype(np.int64).tolist()
+    return [[tuple(r) for r in fr[:int(k)]] for fr, k in zip(rows, np.asarray(nnode))]
 
 
 def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk=1024, count_range=(1, 7),
-                    bandpass_real=None, size=None):
+                    bandpass_real=None, size=None, params="host", first_frame=0):
     """n frames rasterised directly in HBM (csrc/espi.hip): the SAME per-frame parameters as generate(n, seed)
     (so the labels are identical), pixels from the analytic device rasteriser, sensor noise / dropout from a
     counter-based RNG.  Returns (float32 device tensor [n,384,512,1] in [-1,1], label rows[, uint8 device tensor]).
@@ -149,15 +200,24 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
     exactly as reading that PNG back would give.
     size (int or (OH, OW)): the frames are resized on the device as the input codec resizes them (PIL Lanczos, bit for
     bit: resize.py) -- X is [n,OH,OW,1] and the uint8 frames [n,OH,OW], exactly what writing the PNGs and reading them
-    back through build_dataset at force_dim = size gives.  Labels stay in the 512x384 frame's coordinates."""
+    back through build_dataset at force_dim = size gives.  Labels stay in the 512x384 frame's coordinates.
+    params: "host" (default) = the per-frame parameters of draw_params, the reference-ordered stream, drawn on the host
+    frame by frame; "device" = drawn by draw_params_device for the GLOBAL frames first_frame .. first_frame + n - 1, chunk
+    by chunk, the labels read back in one copy per chunk: the same distributions, other frames, and parameters / labels /
+    noise-free pixels that do not depend on `chunk`.  The sensor noise keeps its seed of (seed, chunk start) as before
+    (first_frame shifts the chunk start, so that another range of frames gets other noise); first_frame needs "device"."""
     import torch
     from . import _lib as L
+    if params not in ("host", "device"):
+        raise ValueError("generate_device: params must be 'host' or 'device', got %r" % (params,))
+    if first_frame and params != "device":
+        raise ValueError("generate_device: first_frame needs params='device' (the host stream is keyed by (n, seed))")
     dev = torch.device(device)
     mixer = bp = None
     if bandpass_real is not None:
         from .augmentation import BandpassPool
         mixer = BandpassPool.get(bandpass_real, IM_H, IM_W, dev).mixer
-        bp = mixer.draw(n, seeds=bandpass_seeds(n, seed))
+        bp = mixer.draw(n, seeds=bandpass_seeds(n, seed, first_frame))
     OH, OW = (IM_H, IM_W)
     if size is not None:
         from .resize import _size, resize_u8_device
@@ -168,24 +228,29 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
     st = torch.cuda.current_stream(dev).cuda_stream
     for lo in range(0, n, chunk):
         hi = min(n, lo + chunk)
-        waves = np.zeros((hi - lo, 5), np.float32)
-        nodes = np.zeros((hi - lo, 7, 8), np.float32)
-        nn = np.zeros(hi - lo, np.int32)
-        for k, s in enumerate(frame_seeds(n, seed)[lo:hi]):
-            w, nd, _ = draw_params(s, count_range)
-            waves[k] = w
-            nn[k] = len(nd)
-            for j, node in enumerate(nd):
-                nodes[k, j, :7] = node
-                nodes[k, j, 7] = 1.0
-            labels.append([node[:6] for node in nd])
-        wd, ndd, nnd = (torch.from_numpy(a).to(dev) for a in (waves, nodes, nn))
+        if params == "device":
+            wd, ndd, nnd = draw_params_device(hi - lo, seed, dev, count_range, first_frame + lo)
+            labels += labels_from_params(ndd, nnd)
+        else:
+            waves = np.zeros((hi - lo, 5), np.float32)
+            nodes = np.zeros((hi - lo, 7, 8), np.float32)
+            nn = np.zeros(hi - lo, np.int32)
+            for k, s in enumerate(frame_seeds(n, seed)[lo:hi]):
+                w, nd, _ = draw_params(s, count_range)
+                waves[k] = w
+                nn[k] = len(nd)
+                for j, node in enumerate(nd):
+                    nodes[k, j, :7] = node
+                    nodes[k, j, 7] = 1.0
+                labels.append([node[:6] for node in nd])
+            wd, ndd, nnd = (torch.from_numpy(a).to(dev) for a in (waves, nodes, nn))
         if size is None:
             Xc, Uc = X[lo:hi], (U[lo:hi] if U is not None else None)
         else:               # the 384x512 uint8 frames of this chunk only; X / U receive them resized
             Xc, Uc = None, torch.empty((hi - lo, IM_H, IM_W), dtype=torch.uint8, device=dev)
         L.spnet_fake_espi(wd.data_ptr(), ndd.data_ptr(), nnd.data_ptr(), hi - lo, IM_H, IM_W,
-                          (seed * 2654435761 + lo * 97 + 12345) & 0xFFFFFFFF, int(bool(noise)), L.ptr(Xc), L.ptr(Uc), st)
+                          (seed * 2654435761 + (first_frame + lo) * 97 + 12345) & 0xFFFFFFFF, int(bool(noise)), L.ptr(Xc),
+                          L.ptr(Uc), st)
         if mixer is not None:
             mixer.apply({k: v[lo:hi] for k, v in bp.items()}, Uc, out_u8=Uc)
             if size is None:
@@ -194,6 +259,64 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
             resize_u8_device(Uc, (OH, OW), out_f=X[lo:hi], out_u8=None if U is None else U[lo:hi])
         torch.cuda.current_stream(dev).synchronize()       # wd / ndd / nnd (/ Uc) are freed on return
     return (X, labels, U) if want_u8 else (X, labels)
+
+
+def targets_from_labels(labels, pred_grid=(6, 6, 2)):
+    """Label rows of a chunk of frames -> (Y float32 [B, prod(pred_grid) * 8], overflow bool [B]): the file path's row
+    processing (a/b swap with +90 degrees, rings > 0, sort by (cx, cy)), true_to_pred_grid and norm_Y, vectorised
+    (augmentation._encode_targets) and bit-identical to writing the rows with rows_to_csv and loading the CSV.  overflow
+    marks the frames where a third ellipse falls into one grid cell; their targets hold the two that fit."""
+    from .augmentation import _encode_targets, pad_metadata
+    rows, count = pad_metadata(list(labels))
+    Y, overflow = _encode_targets(rows, count, tuple(pred_grid))
+    return np.ascontiguousarray(Y, dtype=np.float32), overflow
+
+
+class FakeStream:
+    """An endless supply of fake-ESPI training frames: epoch e is the n global frames e*n .. e*n + n - 1 of the device
+    parameter stream (generate_device(params="device")), with their normalised grid targets.  Nothing is read from or
+    written to disk.  size: None = native 384x512 frames (model_type 'big'), 331 = the default layout (resized on the device
+    as the input codec resizes)."""
+
+    def __init__(self, n, seed=0, device="cuda:0", size=None, count_range=(1, 7), pred_grid=(6, 6, 2), bandpass_real=None,
+                 chunk=1024):
+        self.n, self.seed, self.device, self.size = int(n), int(seed), device, size
+        self.count_range, self.pred_grid, self.bandpass_real, self.chunk = tuple(count_range), tuple(pred_grid), bandpass_real, chunk
+        if size is None:
+            self.frame_shape = (IM_H, IM_W, 1)
+        else:
+            from .resize import _size
+            self.frame_shape = tuple(_size(size)) + (1,)
+        from . import config as cf
+        self.n_targets = int(np.prod(self.pred_grid)) * cf.vars_per_pred
+        self.overflowed = 0                 # frames of the last epoch() with a third ellipse in one grid cell
+
+    def frames(self, first_frame, n, want_u8=False):
+        """generate_device for the global frames first_frame .. first_frame + n - 1 of this stream."""
+        return generate_device(n, self.seed, self.device, count_range=self.count_range, bandpass_real=self.bandpass_real,
+                               size=self.size, chunk=self.chunk, params="device", first_frame=first_frame, want_u8=want_u8)
+
+    def epoch(self, e, out_X=None, out_Y=None, verbose=True):
+        """Fills out_X [n,H,W,1] float32 and out_Y [n, n_targets] float32 (device tensors; allocated when None) with the
+        frames and targets of epoch e; returns (out_X, out_Y).  A frame with a third ellipse in one grid cell keeps the two
+        that fit (the file path would assert); their number is kept in self.overflowed and printed."""
+        import torch
+        X, labels = self.frames(int(e) * self.n, self.n)
+        Y, overflow = targets_from_labels(labels, self.pred_grid)
+        self.overflowed = int(overflow.sum())
+        if verbose:
+            print("   Fresh fake-ESPI frames: epoch %d = frames %d .. %d; %d frames with a third ellipse in one grid cell keep "
+                  "the two that fit" % (e, int(e) * self.n, int(e) * self.n + self.n - 1, self.overflowed))
+        Yd = torch.from_numpy(Y).to(X.device)
+        if out_X is None:
+            out_X = X
+        else:
+            out_X.copy_(X.reshape(out_X.shape))
+        if out_Y is None:
+            out_Y = Yd
+        else:
+            out_Y.copy_(Yd)
+        return out_X, out_Y
 
 
 def rows_to_csv(rows):

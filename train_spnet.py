@@ -3,7 +3,8 @@
 reference's train_spnet.py, running on the MI355X engine.
 
 Additive flags (not in the reference): --model_type / --loss_type / --backbone override the
-spnet.config globals; multi-GPU = launch with `python -m torch.distributed.run --nproc-per-node N`.
+spnet.config globals; multi-GPU = launch with `python -m torch.distributed.run --nproc-per-node N`;
+--fake_stream N trains on N fresh synthetic frames per epoch generated on the GPU (no Train/ or Val/ directory).
 """
 import argparse
 import os
@@ -20,22 +21,62 @@ from evaluate_spnet import evaluate_network
 from predict_spnet import default_image_dir, predict_network
 
 
+VAL_STREAM_TOP = 2 ** 40      # the validation frames of --fake_stream are the LAST M global frame indices below this
+
+
+def fake_stream_data(n_train, n_val, global_batch, pred_grid, seed):
+    """--fake_stream: (X_train, Y_train, X_val, Y_val, FreshFakeESPI callback, pred_shape).  The training set is n_train
+    (rounded down to a multiple of the global batch) fresh frames per epoch: epoch e = the global frames e*n .. e*n + n - 1
+    of the device parameter stream.  The validation set, n_val frames (default n_train // 4), is generated once from the
+    frame indices VAL_STREAM_TOP - n_val .. VAL_STREAM_TOP - 1: the top of the index space this script uses, which training
+    would reach only after 2^40 / n frames' worth of epochs.  The layout follows cf.model_type: 331 x 331 frames, or the
+    native 384 x 512 for 'big'.  X_train / Y_train are the callback's device tensors (fit() reads them in place)."""
+    from spnet_amd import fake_espi
+    n = utils.nearest_multiple(int(n_train), global_batch)
+    if n < 1:
+        raise ValueError("--fake_stream %d is less than one global batch (%d)" % (n_train, global_batch))
+    m = int(n_train) // 4 if n_val is None else int(n_val)
+    if m < 1:
+        raise ValueError("--fake_val: the validation set is empty")
+    if cf.model_type == 'simple':
+        raise ValueError("--fake_stream generates one-channel frames (model_type 'monolithic' | 'big' | 'compound')")
+    size = None if cf.model_type == 'big' else 331
+    device = str(multi_gpu.parallel.local_device())
+    pred_shape = np.array([pred_grid[0], pred_grid[1], pred_grid[2], cf.vars_per_pred], dtype=int)
+    print("Fresh fake-ESPI frames: %d per epoch, %d validation frames (global frames %d .. %d), frame size %s"
+          % (n, m, VAL_STREAM_TOP - m, VAL_STREAM_TOP - 1, "384x512" if size is None else "331x331"))
+    val = fake_espi.FakeStream(m, seed=seed, device=device, size=size, pred_grid=pred_grid)
+    Xv, labels = val.frames(VAL_STREAM_TOP - m, m)
+    Yv, _ = fake_espi.targets_from_labels(labels, pred_grid)
+    fresh = callbacks.FreshFakeESPI(None, None, fake_espi.FakeStream(n, seed=seed, device=device, size=size,
+                                                                     pred_grid=pred_grid))
+    return fresh.X, fresh.Y, Xv.cpu().numpy(), Yv, fresh, pred_shape
+
+
 def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch_size=32, epochs=30, pred_grid=[6, 6, 2],
                   noaugment=False, log_dir=".", lr_max=4e-5, freeze_fac=0.7, frozen_epochs=4, random_seed=1,
-                  augment_blur=False, bp_real=None, bpmix_prob=0.3, warp=False):
+                  augment_blur=False, bp_real=None, bpmix_prob=0.3, warp=False, fake_stream=None, fake_val=None):
     np.random.seed(random_seed)
     # Data parallel (launched by torch.distributed.run): choose this rank's GPU and join the process group before
     # anything touches the device; rank 0 alone logs, validates and writes checkpoints.
     rank, _, world = multi_gpu.parallel.init_distributed()
     print("pred_grid = ", pred_grid)
-    X_train, Y_train, train_file_list, pred_shape = utils.build_dataset(
-        path=datapath + "/Train/", load_frac=fraction, set_means_ranges=True, batch_size=batch_size, pred_grid=pred_grid)
-    X_val, Y_val, val_file_list, pred_shape = utils.build_dataset(
-        path=datapath + "/Val/", load_frac=1.0, set_means_ranges=False, batch_size=batch_size, pred_grid=pred_grid)
+    fresh = None
+    if fake_stream:
+        X_train, Y_train, X_val, Y_val, fresh, pred_shape = fake_stream_data(fake_stream, fake_val, batch_size * world,
+                                                                             pred_grid, random_seed)
+        train_file_list, val_file_list = None, None          # no files: MyProgressCallback draws no overlays
+        if warp:
+            raise ValueError("--warp needs the PNG + CSV files of Train/; --fake_stream has none")
+    else:
+        X_train, Y_train, train_file_list, pred_shape = utils.build_dataset(
+            path=datapath + "/Train/", load_frac=fraction, set_means_ranges=True, batch_size=batch_size, pred_grid=pred_grid)
+        X_val, Y_val, val_file_list, pred_shape = utils.build_dataset(
+            path=datapath + "/Val/", load_frac=1.0, set_means_ranges=False, batch_size=batch_size, pred_grid=pred_grid)
 
     print("Seting up NN model.  model_type = ", cf.model_type)
     parallel = world > 1
-    model, serial_model = models.setup_model(X_train, Y_train[0].size, no_cp_fatal=False, weights_file=weights_file,
+    model, serial_model = models.setup_model(X_train, int(Y_train[0].size), no_cp_fatal=False, weights_file=weights_file,
                                              parallel=parallel, freeze_fac=freeze_fac)
 
     callback_list = []
@@ -47,6 +88,8 @@ def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch
     # one optimizer iteration consumes batch_size frames on EVERY rank
     callback_list.append(callbacks.OneCycleScheduler(lr_max=lr_max, n_data_points=X_train.shape[0], epochs=epochs,
                                                      batch_size=batch_size * world, verbose=int(rank == 0)))
+    if fresh is not None:       # ahead of AugmentOnTheFly: the fresh frames are what it augments
+        callback_list.append(fresh)
     if not noaugment:
         print("Adding callback for augment on the fly")
         callback_list.append(callbacks.AugmentOnTheFly(X_train, Y_train, aug_every=1, seed=random_seed,
@@ -102,6 +145,11 @@ if __name__ == '__main__':
                         "+-40 px: what augment_preproc.py writes offline) and recompute its targets.  NEEDS the PNG + CSV "
                         "files of Train/ on disk: the frames are warped at their full size and the targets come from the "
                         "CSV rows.  Ignored with --noaugment")
+    p.add_argument('--fake_stream', type=int, default=None, metavar='N',
+                   help="train on N fresh fake-ESPI frames per epoch, generated on the GPU (rounded down to a multiple of "
+                        "the global batch); no Train/ or Val/ directory is read")
+    p.add_argument('--fake_val', type=int, default=None, metavar='M',
+                   help="with --fake_stream: size of the validation set, generated once (default N // 4)")
     args = p.parse_args()
     print("Command line ~= \n", ' '.join(sys.argv))
     print("args = ", args)
@@ -119,15 +167,19 @@ if __name__ == '__main__':
                           batch_size=args.batch_size, epochs=args.epochs, pred_grid=pred_grid, noaugment=args.noaugment,
                           log_dir=log_dir, lr_max=args.lrmax, freeze_fac=args.freeze_fac,
                           frozen_epochs=args.frozen_epochs, random_seed=args.random_seed,
-                          augment_blur=args.augment_blur, bp_real=args.bp_real, bpmix_prob=args.bpmix_prob, warp=args.warp)
+                          augment_blur=args.augment_blur, bp_real=args.bp_real, bpmix_prob=args.bpmix_prob, warp=args.warp,
+                          fake_stream=args.fake_stream, fake_val=args.fake_val)
 
     if int(os.environ.get("RANK", "0")) == 0:
         print("\n----------------------------\nStarting model evaluation...")
         testpath = args.datapath + '/Test/'
         if not os.path.isdir(testpath):
             testpath = args.datapath + '/Val/'
-        evaluate_network(model=model, weights_file="", datapath=testpath, fraction=1.0, log_dir="logs/Evaluation/",
-                         batch_size=args.batch_size, pred_grid=pred_grid, set_means_ranges=False)
+        if args.fake_stream and not os.path.isdir(testpath):
+            print("(--fake_stream: no Test/ or Val/ directory under", args.datapath, "-- evaluation on files skipped)")
+        else:
+            evaluate_network(model=model, weights_file="", datapath=testpath, fraction=1.0, log_dir="logs/Evaluation/",
+                             batch_size=args.batch_size, pred_grid=pred_grid, set_means_ranges=False)
         if os.path.isdir(default_image_dir):      # the reference predicts on the author's unlabeled set here
             print("\n----------------------------\nStarting Zooniverse predictions...")
             predict_network(weights_file="", fraction=args.fraction, log_dir='logs/Predicting/',

@@ -218,8 +218,8 @@ int spnet_dwconv3x3_stream_bwd(const float* dy, const float* x_fwd, const float*
 
 /* ---- BatchNormalization(axis=-1, momentum .99, eps 1e-3) (spnet/models.py:326-336 + 40 in Xception) --- */
 /* act: 0 none, 1 ReLU, 2 LeakyReLU(0.1), 3 ReLU6 (MobileNet) fused behind the affine; residual (or NULL) added last;
- * res_bcast=1 (C<=4 only): residual holds one value per pixel, broadcast over the channels (the
- * stem's skip connection from the 1-channel input, spnet/models.py:337). */
+ * res_bcast=1 (C in {1, 2, 3} only; hipErrorInvalidValue at C % 4 == 0): residual holds one value per pixel, broadcast
+ * over the channels (the stem's skip connection from the 1-channel input, spnet/models.py:337). */
 long spnet_bn_ws(long M, int C);
 int spnet_bn_fwd_train(const float* x, long M, int C, const float* gamma, const float* beta,
                        float* moving_mean, float* moving_var, float* save_mean, float* save_invstd,
@@ -242,7 +242,8 @@ int spnet_bn_infer_coeffs(int C, const float* gamma, const float* beta, const fl
                           const float* moving_var, float* scale_shift, float eps, void* stream);
 int spnet_bn_apply(const float* x, long M, int C, const float* scale_shift, int act, const float* residual,
                    int res_bcast, float* y, void* stream);
-/* spnet_bn_finalize_fwd + spnet_bn_apply (no broadcast residual) as ONE launch while P <= 128 partial rows -- the closing
+/* spnet_bn_finalize_fwd + spnet_bn_apply (no broadcast residual) as ONE launch while P <= 128 partial rows (P <= 512
+ * while M*C <= 4 Mi; more rows: the two launches, and `partial` is consumed from P = 1024 as above) -- the closing
  * BatchNormalization + Add of a keras Xception middle block in training (spnet/models.py:357-359); results identical. */
 int spnet_bn_finalize_apply(float* partial, int P, const float* x, long M, int C, const float* gamma,
                             const float* beta, float* moving_mean, float* moving_var, float* save_mean,

@@ -48,27 +48,32 @@ __device__ __forceinline__ float spnet_u8_to_input_f(unsigned v) {
 }
 
 // Keras' moving-statistics update, moving*momentum + value*(1 - momentum), with every product and the sum rounded on
-// its own (no fused multiply-add): the same bits from every kernel that performs it.
+// its own (no fused multiply-add): the same bits from every kernel that performs it.  (__fmul_rn / __fadd_rn are plain
+// operators in this toolchain's headers; the pragma is what keeps the compiler from contracting them.)
 __device__ __forceinline__ float bn_moving_update(float moving, float momentum, float value) {
+#pragma clang fp contract(off)
   return __fadd_rn(__fmul_rn(momentum, moving), __fmul_rn(1.f - momentum, value));
 }
 
-// shift = beta - mean*scale of the BatchNorm affine, likewise without contraction.
+// shift = beta - mean*scale of the BatchNorm affine as ONE fused multiply-add, written out: __fmul_rn / __fsub_rn are
+// plain operators in this toolchain's headers and the compiler contracted the pair wherever it liked (it did, in every
+// kernel -- tests/test_batchnorm_gpu.py found the bits); an explicit fmaf is the same in every kernel by construction.
 __device__ __forceinline__ float bn_shift(float beta, float mean, float scale) {
-  return __fsub_rn(beta, __fmul_rn(mean, scale));
+  return fmaf(-mean, scale, beta);
 }
 
 // Batch statistics of one channel from its column sums (sum, sum of squares over M values) and everything the BatchNorm
 // forward derives from them.  Three kernels perform this step (bn_fwd_finalize_kernel, and the consumers it is folded
-// into: bn_fwd_fused_vec_kernel, dw3x3_tile_fwd_kernel); every rounding is pinned (no contraction left to the
-// compiler) so that they produce the same bits.
+// into: bn_fwd_fused_vec_kernel, dw3x3_tile_fwd_kernel) and must produce the same bits: the variance is ONE double
+// fma, q/M - mean*mean rounded once (as above: written out, not left to contraction); tests/helpers/bn_ref.py's
+// finalize_bits restates the whole step rounding by rounding.
 struct BnChannelStats {
   float mean, invstd, scale, shift, unbiased_var;
 };
 __device__ __forceinline__ BnChannelStats bn_channel_stats(double s, double q, long M, float gamma, float beta, float eps) {
   BnChannelStats r;
   const double mean = s / (double)M;
-  double var = __dsub_rn(q / (double)M, __dmul_rn(mean, mean));
+  double var = fma(-mean, mean, q / (double)M);
   if (var < 0.0) var = 0.0;
   r.mean = (float)mean;
   r.invstd = (float)(1.0 / sqrt(__dadd_rn(var, (double)eps)));

@@ -245,7 +245,6 @@ class DenseNetBackbone:
     def fwd(self, training):
         from .engine import ACT_RELU, K_MAJOR, OUT_MAJOR, WS_BNP, WS_MISC, _tile_for
         e, B, st = self.e, self.B, L.current_stream()
-        prof = e.prof
         L.spnet_dense_conv7(0, L.ptr(self.x), L.ptr(self.wc), L.ptr(self.y0), B, self.H2, self.W2, None, 0, st)
         if training:
             L.spnet_dense_colsums_ld(L.ptr(self.y0), 64, self.M1, 64, e.ws_ptr(WS_MISC), st)
@@ -262,35 +261,27 @@ class DenseNetBackbone:
             for lay in blk.layers:
                 c, cons, bn1 = lay["c"], lay["cons"], lay["bn1"]
                 cons.coeffs(blk, training)
-                t0 = prof.start() if prof is not None else None
-                L.spnet_gemm_f32_bnrelu(L.ptr(blk.X), blk.Cb, L.ptr(cons.coef), cons.cld, L.ptr(lay["w1"]), DN_BOTTLENECK,
-                                        L.ptr(lay["y1"]), DN_BOTTLENECK, blk.M, DN_BOTTLENECK, c, 0,
-                                        e.ws_ptr(WS_BNP) if training else None,
-                                        ctypes.addressof(_rows) if training else None, st)
-                if prof is not None:
-                    prof.stop("dense_bnrelu_gemm", t0, 2.0 * blk.M * DN_BOTTLENECK * c, ("bnrelu", blk.M, DN_BOTTLENECK, c))
+                e.timed("dense_bnrelu_gemm", 2.0 * blk.M * DN_BOTTLENECK * c, ("bnrelu", blk.M, DN_BOTTLENECK, c),
+                        L.spnet_gemm_f32_bnrelu, L.ptr(blk.X), blk.Cb, L.ptr(cons.coef), cons.cld, L.ptr(lay["w1"]),
+                        DN_BOTTLENECK, L.ptr(lay["y1"]), DN_BOTTLENECK, blk.M, DN_BOTTLENECK, c, 0,
+                        e.ws_ptr(WS_BNP) if training else None, ctypes.addressof(_rows) if training else None, st)
                 if training:
                     bn1.finalize(_rows.value)
                 bn1.apply(lay["y1"], lay["z1"], ACT_RELU)
                 K = 9 * DN_BOTTLENECK
-                t0 = prof.start() if prof is not None else None
-                L.spnet_conv_gemm_f32(L.ptr(lay["z1"]), DN_BOTTLENECK, L.ptr(lay["w2"]), blk.X.data_ptr() + 4 * c, blk.Cb,
-                                      B, blk.h, blk.w, DN_BOTTLENECK, DN_GROWTH, 3, 3, 1, 1, None,
-                                      _tile_for(K_MAJOR, OUT_MAJOR, 1 if training else 0, blk.M, DN_GROWTH, K, 0),
-                                      e.ws_ptr(WS_BNP) if training else None,
-                                      ctypes.addressof(_rows) if training else None, st)
-                if prof is not None:
-                    prof.stop("gemm", t0, 2.0 * blk.M * DN_GROWTH * K, ("conv gathered", blk.M, DN_GROWTH, K))
+                e.timed("gemm", 2.0 * blk.M * DN_GROWTH * K, ("conv gathered", blk.M, DN_GROWTH, K),
+                        L.spnet_conv_gemm_f32, L.ptr(lay["z1"]), DN_BOTTLENECK, L.ptr(lay["w2"]), blk.X.data_ptr() + 4 * c,
+                        blk.Cb, B, blk.h, blk.w, DN_BOTTLENECK, DN_GROWTH, 3, 3, 1, 1, None,
+                        _tile_for(K_MAJOR, OUT_MAJOR, 1 if training else 0, blk.M, DN_GROWTH, K, 0),
+                        e.ws_ptr(WS_BNP) if training else None, ctypes.addressof(_rows) if training else None, st)
                 if training:
                     blk.finalize_stats(e.ws_ptr(WS_BNP), _rows.value, c, DN_GROWTH)
             if blk.trans:
                 tc = blk.tcons
                 tc.coeffs(blk, training)
-                t0 = prof.start() if prof is not None else None
-                L.spnet_gemm_f32_bnrelu(L.ptr(blk.X), blk.Cb, L.ptr(tc.coef), tc.cld, L.ptr(blk.tw), blk.Cb // 2,
-                                        L.ptr(blk.ty), blk.Cb // 2, blk.M, blk.Cb // 2, blk.Cb, 0, None, None, st)
-                if prof is not None:
-                    prof.stop("dense_bnrelu_gemm", t0, 2.0 * blk.M * blk.Cb * blk.Cb // 2, ("bnrelu", blk.M, blk.Cb // 2, blk.Cb))
+                e.timed("dense_bnrelu_gemm", 2.0 * blk.M * blk.Cb * blk.Cb // 2, ("bnrelu", blk.M, blk.Cb // 2, blk.Cb),
+                        L.spnet_gemm_f32_bnrelu, L.ptr(blk.X), blk.Cb, L.ptr(tc.coef), tc.cld, L.ptr(blk.tw), blk.Cb // 2,
+                        L.ptr(blk.ty), blk.Cb // 2, blk.M, blk.Cb // 2, blk.Cb, 0, None, None, st)
                 nxt = self.blocks[self.blocks.index(blk) + 1]
                 pooled = (self.din if e.train_capable else self.pool_scr)[:nxt.M * nxt.c0]
                 L.spnet_avgpool2_fwd(L.ptr(blk.ty), L.ptr(pooled), B, blk.h, blk.w, blk.Cb // 2, st)

@@ -18,7 +18,7 @@ Data layout in HBM
 import ctypes
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -106,6 +106,11 @@ class KernelTimer:
             n, ms, tw = out.get(fam, (0, 0.0, 0.0))
             out[fam] = (n + 1, ms + s.elapsed_time(e), tw + w)
         return out
+
+
+# One layer's deferred weight gradient gw[cin][cout] = a^T dy over M rows (Engine.flush_deferred_wgrads); planes: a and dy
+# are bf16x3 plane sets (csrc/x3t.h) instead of fp32 tensors
+_WgradJob = namedtuple("_WgradJob", "a dy gw cin cout M planes")
 
 
 def xception_plan():
@@ -681,10 +686,9 @@ class Engine:
         self._bns = []                  # every BN of this plan (their inference coefficients: refresh)
         self._irv2 = None               # the IRv2Backbone node, if any (its gathered group operands: refresh)
         self._densenet = None           # the DenseNetBackbone node, if any
-        self.deferred_wgrads = []       # (x, dy, gw, cin, cout, M) of layers whose dW waits for the batched launch
+        self.deferred_wgrads = []       # _WgradJob of every layer whose dW waits for the batched launch
         self.dw_reduce_jobs = []        # (partials, grad, rows, 9*C) of every depthwise layer
-        self._dw_reduce_table = None
-        self._wgrad_table = None
+        self._job_tables = {}           # device tables of the batched launches (_job_table)
         self._first_middle = None
         # The two run-time switches of the engine (DESIGN.md section 2 lists them with the tests that run the non-default
         # branch): SPNET_OVERLAP_WGRAD=0 -- weight gradients on the main stream instead of a side stream joined before
@@ -942,6 +946,46 @@ class Engine:
         if self.wgrad_stream is not None:      # every weight gradient must have landed before the optimizer
             torch.cuda.current_stream().wait_stream(self.wgrad_stream)
 
+    # ------------------------------------------------------------------ launch idioms, written once
+    def on_wgrad_stream(self, call, main_region=None, side_region=None):
+        """call(region) off the data-gradient chain.  A plan without a weight-gradient stream (SPNET_OVERLAP_WGRAD=0, or
+        wgrad_stream set to None by a tool) runs it in line with `main_region`; otherwise it runs on the weight-gradient
+        stream, behind everything the current stream holds so far, with `side_region` -- a launch that takes a workspace
+        must take the one that belongs to the stream it runs on (WS_GEMM / WS_MISC against WS_GEMM2).  Engine.backward
+        joins the stream in front of the optimizer; what call() reads must not be rewritten before that join.
+        The other stream shapes of the plan stay where they are, because they are other shapes: StridedBlock.fwd
+        (set_stream onto the side stream and back, joined later), adam_head_early (a third stream that waits for two) and
+        that final join."""
+        side = self.wgrad_stream
+        if side is None:
+            return call(main_region)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            return call(side_region)
+
+    def timed(self, family, work, tag, call, *args, key=None):
+        """call(*args) -- between two events on the launch stream, recorded as (family, work, tag), when a KernelTimer is
+        set (self.prof); key: the (a_major, b_major, stats, M, N, K) of a plain GEMM launch, for the autotuner.
+        (The arguments travel beside the callable: a closure per launch costs the host more, and a step is some 600
+        launches.)"""
+        prof = self.prof
+        if prof is None:
+            return call(*args)
+        t0 = prof.start()
+        out = call(*args)
+        prof.stop(family, t0, work, tag)
+        if key is not None:
+            prof.keys[len(prof.records) - 1] = key
+        return out
+
+    def _job_table(self, key, words):
+        """The int64 device table of a batched launch, built from words() the first time `key` -- the addresses it was
+        made of -- comes up (every step after the first finds it: the plan's buffers are static)."""
+        table = self._job_tables.get(key)
+        if table is None:
+            table = self._job_tables[key] = torch.tensor(words(), dtype=torch.int64, device=self.dev)
+        return table
+
     def reduce_depthwise_wgrads(self):
         """Fold the partial sums every fused depthwise backward left behind into the 34 depthwise weight
         gradients: one launch (weight-gradient stream) instead of one small kernel per layer on the
@@ -949,104 +993,58 @@ class Engine:
         jobs = self.dw_reduce_jobs
         if not jobs:
             return
-        if self._dw_reduce_table is None:
-            flat = [v for (part, grad, rows, Lr) in jobs for v in (part.data_ptr(), grad.data_ptr(), rows, Lr)]
-            self._dw_reduce_table = torch.tensor(flat, dtype=torch.int64, device=self.dev)
+        table = self._job_table("dw reduce", lambda: [v for (part, grad, rows, Lr) in jobs
+                                                      for v in (part.data_ptr(), grad.data_ptr(), rows, Lr)])
         max_L = max(j[3] for j in jobs)
-        side = self.wgrad_stream
-        if side is None:
-            L.spnet_reduce_rows_batched(self._dw_reduce_table.data_ptr(), len(jobs), max_L, _stream())
-        else:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                L.spnet_reduce_rows_batched(self._dw_reduce_table.data_ptr(), len(jobs), max_L, _stream())
+        self.on_wgrad_stream(lambda _: L.spnet_reduce_rows_batched(table.data_ptr(), len(jobs), max_L, _stream()))
 
     def flush_deferred_wgrads(self):
-        """dW of every deferred pointwise layer in one batched launch (weight-gradient stream).  The operand
-        table lives in device memory and is rebuilt only if a buffer address changed (never, in practice:
-        the plan's buffers are static)."""
-        todo = self.deferred_wgrads
-        if not todo:
-            return
-        self.deferred_wgrads = []
-        x3 = [t for t in todo if t[0] == "x3"]
-        if x3:
-            self._flush_x3_wgrads(x3)
-            todo = [t for t in todo if t[0] != "x3"]
-            if not todo:
-                return
-        x0, dy0, gw0, cin, cout, M = todo[0]
-        if any((t[3], t[4], t[5]) != (cin, cout, M) for t in todo):
-            raise RuntimeError("deferred weight gradients must share one shape")
+        """dW of every deferred pointwise layer in one batched launch per operand form (weight-gradient stream).  The
+        operand tables live in device memory (_job_table)."""
+        todo, self.deferred_wgrads = self.deferred_wgrads, []
+        for planes, flush in ((True, self._flush_x3_wgrads), (False, self._flush_f32_wgrads)):
+            jobs = [t for t in todo if t.planes == planes]
+            if jobs:
+                if any((t.cin, t.cout, t.M) != jobs[0][3:6] for t in jobs):
+                    raise RuntimeError("deferred weight gradients must share one shape")
+                flush(jobs)
+
+    def _flush_f32_wgrads(self, todo):
+        """dW of the deferred layers with fp32 operands: ONE launch of spnet_gemm_f32_batched."""
+        cin, cout, M, nb = todo[0].cin, todo[0].cout, todo[0].M, len(todo)
         # element offsets of every problem's operands from problem 0's (kernel-argument base pointers keep the
         # operand fetches in the global address space)
-        a0, b0, c0 = x0.data_ptr(), dy0.data_ptr(), gw0.data_ptr()
-        offs = [v for (x, dy, gw, _, _, _) in todo
-                for v in ((x.data_ptr() - a0) // 4, (dy.data_ptr() - b0) // 4, (gw.data_ptr() - c0) // 4)]
-        if self._wgrad_table is None:
-            self._wgrad_table = {}
-        key = (a0, b0, c0) + tuple(offs)
-        if key not in self._wgrad_table:
-            self._wgrad_table[key] = torch.tensor(offs, dtype=torch.int64, device=self.dev)
-        table = self._wgrad_table[key]
-        nb = len(todo)
-
-        def launch():
-            prof = self.prof
-            t0 = prof.start() if prof is not None else None
-            L.spnet_gemm_f32_batched(a0, b0, c0, table.data_ptr(), nb, OUT_MAJOR, cin, OUT_MAJOR, cout, cout, cin, cout, M,
-                                     5, _stream())
-            if prof is not None:
-                prof.stop("gemm", t0, 2.0 * nb * cin * cout * M, ("AB x%d batched" % nb, cin, cout, M))
-
-        side = self.wgrad_stream
-        if side is None:
-            launch()
-        else:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                launch()
+        a0, b0, c0 = todo[0].a.data_ptr(), todo[0].dy.data_ptr(), todo[0].gw.data_ptr()
+        offs = [v for t in todo for v in ((t.a.data_ptr() - a0) // 4, (t.dy.data_ptr() - b0) // 4, (t.gw.data_ptr() - c0) // 4)]
+        table = self._job_table((a0, b0, c0) + tuple(offs), lambda: offs)
+        self.on_wgrad_stream(lambda _: self.timed(
+            "gemm", 2.0 * nb * cin * cout * M, ("AB x%d batched" % nb, cin, cout, M), L.spnet_gemm_f32_batched,
+            a0, b0, c0, table.data_ptr(), nb, OUT_MAJOR, cin, OUT_MAJOR, cout, cout, cin, cout, M, 5, _stream()))
 
     def _flush_x3_wgrads(self, todo):
         """dW of the deferred layers whose operands are bf16x3 planes: ONE launch of spnet_gemm_bf16x3_wgrad_batched
-        (weight-gradient stream); a K split (slabs in the weight-gradient stream's workspace + one ordered sum per layer)
-        only if the batch alone does not fill the chip."""
-        _, _, _, _, cin, cout, M = todo[0]
-        if any((t[4], t[5], t[6]) != (cin, cout, M) for t in todo):
-            raise RuntimeError("deferred weight gradients must share one shape")
-        nb = len(todo)
-        side = self.wgrad_stream
-        region = WS_GEMM2 if side is not None else WS_GEMM
-        ks = int(L.spnet_gemm_bf16x3_wgrad_ksplit(cin, cout, M, nb))
-        if ks > 1 and nb * ks * cin * cout > region[1]:
-            ks = max(1, region[1] // (nb * cin * cout))
-        key = ("x3", ks) + tuple(v for t in todo for v in (t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr()))
-        if self._wgrad_table is None:
-            self._wgrad_table = {}
-        if key not in self._wgrad_table:
+        (weight-gradient stream); a K split (slabs in that stream's workspace + one ordered sum per layer) only if the
+        batch alone does not fill the chip."""
+        cin, cout, M, nb = todo[0].cin, todo[0].cout, todo[0].M, len(todo)
+
+        def run(region):
+            ks = int(L.spnet_gemm_bf16x3_wgrad_ksplit(cin, cout, M, nb))
+            if ks > 1 and nb * ks * cin * cout > region[1]:
+                ks = max(1, region[1] // (nb * cin * cout))
             ws = self.ws_ptr(region)
-            flat = [v for b, t in enumerate(todo)
-                    for v in (t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr() if ks == 1 else ws + 4 * b * ks * cin * cout)]
-            self._wgrad_table[key] = torch.tensor(flat, dtype=torch.int64, device=self.dev)
-        table = self._wgrad_table[key]
+            ptrs = tuple(v for t in todo for v in (t.a.data_ptr(), t.dy.data_ptr(), t.gw.data_ptr()))
+            table = self._job_table(("x3", ks) + ptrs, lambda: [
+                v for b, t in enumerate(todo)
+                for v in (t.a.data_ptr(), t.dy.data_ptr(), t.gw.data_ptr() if ks == 1 else ws + 4 * b * ks * cin * cout)])
 
-        def launch():
-            prof = self.prof
-            t0 = prof.start() if prof is not None else None
-            L.spnet_gemm_bf16x3_wgrad_batched(table.data_ptr(), nb, cin, cout, M, ks, _stream())
-            if ks > 1:
-                ws = self.ws_ptr(region)
-                for b, t in enumerate(todo):
-                    L.spnet_reduce_slabs(ws + 4 * b * ks * cin * cout, ks, cin, cout, t[3].data_ptr(), cout, _stream())
-            if prof is not None:
-                prof.stop("gemm", t0, 2.0 * nb * cin * cout * M, ("x3w AB x%d batched" % nb, cin, cout, M))
+            def launch():
+                L.spnet_gemm_bf16x3_wgrad_batched(table.data_ptr(), nb, cin, cout, M, ks, _stream())
+                if ks > 1:
+                    for b, t in enumerate(todo):
+                        L.spnet_reduce_slabs(ws + 4 * b * ks * cin * cout, ks, cin, cout, t.gw.data_ptr(), cout, _stream())
+            self.timed("gemm", 2.0 * nb * cin * cout * M, ("x3w AB x%d batched" % nb, cin, cout, M), launch)
 
-        if side is None:
-            launch()
-        else:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                launch()
+        self.on_wgrad_stream(run, WS_GEMM, WS_GEMM2)
 
     def loss(self, Y=None, with_grad=True):
         if Y is not None:
@@ -1221,34 +1219,30 @@ def _tile_for(a_major, b_major, stats, M, N, K, tile):
 
 def _gemm(A, a_major, lda, Bm, b_major, ldb, C, ldc, M, N, K, eng, bias=None, split_k=0, tile=0, region=WS_GEMM):
     tile = _tile_for(a_major, b_major, 0, M, N, K, tile)
-    prof = eng.prof
-    if prof is not None:
-        t0 = prof.start()
-    L.spnet_gemm_f32(L.ptr(A), a_major, lda, L.ptr(Bm), b_major, ldb, L.ptr(C), ldc, M, N, K, split_k,
-                     eng.ws_ptr(region), region[1], L.ptr(bias), tile, _stream())
-    if prof is not None:
-        prof.stop("gemm", t0, 2.0 * M * N * K, ("aA"[a_major] + "bB"[b_major], M, N, K))
-        prof.keys[len(prof.records) - 1] = (a_major, b_major, 0, M, N, K)
+    eng.timed("gemm", 2.0 * M * N * K, ("aA"[a_major] + "bB"[b_major], M, N, K), L.spnet_gemm_f32,
+              L.ptr(A), a_major, lda, L.ptr(Bm), b_major, ldb, L.ptr(C), ldc, M, N, K, split_k, eng.ws_ptr(region), region[1],
+              L.ptr(bias), tile, _stream(), key=(a_major, b_major, 0, M, N, K))
 
 
 _stat_rows = ctypes.c_int(0)
 
 
+def _partial_rows(eng, region, M, N, tile_rows, entry, *args):
+    """entry(*args, partials, row count out-parameter, stream): a GEMM whose epilogue leaves the BatchNorm column sums of
+    its [M][N] result in `region`, one pair of partial rows per `tile_rows` rows of the result at the most (32: the fp32
+    GEMM's smallest tile, 96: the bf16x3 kernels'); returns the number of partial rows it left."""
+    if (M + tile_rows - 1) // tile_rows * 2 * N > region[1]:
+        raise RuntimeError("BatchNorm partial region too small for M=%d N=%d" % (M, N))
+    entry(*args, eng.ws_ptr(region), ctypes.addressof(_stat_rows), _stream())
+    return _stat_rows.value
+
+
 def _gemm_colstats(A, lda, Bm, ldb, C, ldc, M, N, K, eng, region=WS_BNP):
     """Forward-form GEMM whose epilogue also leaves the BatchNorm column sums of C in the WS_BNP region;
     returns the number of partial rows."""
-    if (M + 31) // 32 * 2 * N > region[1]:
-        raise RuntimeError("BatchNorm partial region too small for M=%d N=%d" % (M, N))
-    prof = eng.prof
-    if prof is not None:
-        t0 = prof.start()
-    L.spnet_gemm_f32_colstats(L.ptr(A), K_MAJOR, lda, L.ptr(Bm), OUT_MAJOR, ldb, L.ptr(C), ldc, M, N, K,
-                              _tile_for(K_MAJOR, OUT_MAJOR, 1, M, N, K, 0),
-                              eng.ws_ptr(region), ctypes.addressof(_stat_rows), _stream())
-    if prof is not None:
-        prof.stop("gemm", t0, 2.0 * M * N * K, ("aB+stats", M, N, K))
-        prof.keys[len(prof.records) - 1] = (K_MAJOR, OUT_MAJOR, 1, M, N, K)
-    return _stat_rows.value
+    return eng.timed("gemm", 2.0 * M * N * K, ("aB+stats", M, N, K), _partial_rows, eng, region, M, N, 32,
+                     L.spnet_gemm_f32_colstats, L.ptr(A), K_MAJOR, lda, L.ptr(Bm), OUT_MAJOR, ldb, L.ptr(C), ldc, M, N, K,
+                     _tile_for(K_MAJOR, OUT_MAJOR, 1, M, N, K, 0), key=(K_MAJOR, OUT_MAJOR, 1, M, N, K))
 
 
 class SmallConv(Node):
@@ -1277,13 +1271,8 @@ class SmallConv(Node):
         self._call(0, self.x, self.w, self.y)
 
     def bwd(self, g):
-        side = self.e.wgrad_stream
-        if side is None:
-            self._call(2, self.x, g, self.gw)
-        else:           # weight gradient off the data-gradient chain (see Pointwise.bwd)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._call(2, self.x, g, self.gw, region=WS_GEMM2)
+        # weight gradient off the data-gradient chain (see Pointwise._wgrad)
+        self.e.on_wgrad_stream(lambda region: self._call(2, self.x, g, self.gw, region=region), WS_MISC, WS_GEMM2)
         if self.need_dx:
             self._call(1, g, self.w, self.dx)
             return self.dx
@@ -1311,18 +1300,9 @@ class StemHead(Node):
 
     def bwd(self, g):
         e = self.e
-        side = e.wgrad_stream
-        region = WS_MISC if side is None else WS_GEMM2
-
-        def call():
-            L.spnet_stem_head(2, L.ptr(self.x), L.ptr(g), L.ptr(self.gw), None, e.B, self.H, self.W, e.ws_ptr(region),
-                              region[1], _stream())
-        if side is None:
-            call()
-        else:           # weight gradient off the data-gradient chain (see Pointwise.bwd)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                call()
+        # weight gradient off the data-gradient chain (see Pointwise._wgrad)
+        e.on_wgrad_stream(lambda region: L.spnet_stem_head(2, L.ptr(self.x), L.ptr(g), L.ptr(self.gw), None, e.B, self.H, self.W,
+                                                           e.ws_ptr(region), region[1], _stream()), WS_MISC, WS_GEMM2)
         return None
 
 
@@ -1434,117 +1414,83 @@ class Pointwise:
         """bf16x3 planes of the kernel (WeightSet.need_planes): form 0 the forward operand, 1 the data-gradient one"""
         return self.e.weights.planes[self.wname][form]
 
-    def _x3(self, tag, A, lda, planes, C, ldc, N, K, colstats_region=None):
-        """One bf16x3 launch: C[M][N] = A[M][K] x planes (+ BatchNorm column sums of C); returns the partial row count."""
-        e = self.e
-        prof = e.prof
-        t0 = prof.start() if prof is not None else None
-        rows = 0
-        if colstats_region is None:
-            L.spnet_gemm_bf16x3_fwd(L.ptr(A), lda, L.ptr(planes), L.ptr(C), ldc, self.M, N, K, _stream())
+    def _x3(self, tag, A, b_planes, C, N, K, a_planes=False, colstats_region=None):
+        """One bf16x3 launch: C[M][N] = A x B planes^T (+ the BatchNorm column sums of C in `colstats_region`), A being
+        [M][K] fp32 that the kernel splits itself or, with a_planes, the planes its producer wrote; returns the partial
+        row count (0 without column sums)."""
+        e, M = self.e, self.M
+        if a_planes:
+            entry, args = L.spnet_gemm_bf16x3_pp, (L.ptr(A), L.ptr(b_planes), L.ptr(C), N, M, N, K)
         else:
-            if (self.M + 95) // 96 * 2 * N > colstats_region[1]:
-                raise RuntimeError("BatchNorm partial region too small for M=%d N=%d" % (self.M, N))
-            L.spnet_gemm_bf16x3_fwd_colstats(L.ptr(A), lda, L.ptr(planes), L.ptr(C), ldc, self.M, N, K,
-                                             e.ws_ptr(colstats_region), ctypes.addressof(_stat_rows), _stream())
-            rows = _stat_rows.value
-        if prof is not None:
-            prof.stop("gemm", t0, 2.0 * self.M * N * K, (tag, self.M, N, K))
-        return rows
-
-    def _x3p(self, tag, a_planes, b_planes, C, N, K, colstats_region=None):
-        """One planes x planes launch: C[M][N] = A planes x B planes^T (+ BatchNorm column sums); returns the partial row
-        count."""
-        e = self.e
-        prof = e.prof
-        t0 = prof.start() if prof is not None else None
-        rows = 0
-        if colstats_region is None:
-            L.spnet_gemm_bf16x3_pp(L.ptr(a_planes), L.ptr(b_planes), L.ptr(C), N, self.M, N, K, None, None, _stream())
-        else:
-            if (self.M + 95) // 96 * 2 * N > colstats_region[1]:
-                raise RuntimeError("BatchNorm partial region too small for M=%d N=%d" % (self.M, N))
-            L.spnet_gemm_bf16x3_pp(L.ptr(a_planes), L.ptr(b_planes), L.ptr(C), N, self.M, N, K, e.ws_ptr(colstats_region),
-                                   ctypes.addressof(_stat_rows), _stream())
-            rows = _stat_rows.value
-        if prof is not None:
-            prof.stop("gemm", t0, 2.0 * self.M * N * K, (tag, self.M, N, K))
-        return rows
+            entry = L.spnet_gemm_bf16x3_fwd if colstats_region is None else L.spnet_gemm_bf16x3_fwd_colstats
+            args = (L.ptr(A), K, L.ptr(b_planes), L.ptr(C), N, M, N, K)
+        if colstats_region is not None:
+            return e.timed("gemm", 2.0 * M * N * K, (tag, M, N, K), _partial_rows, e, colstats_region, M, N, 96, entry, *args)
+        if a_planes:
+            args += (None, None)        # (no column sums)
+        e.timed("gemm", 2.0 * M * N * K, (tag, M, N, K), entry, *args, _stream())
+        return 0
 
     def fwd_p(self, zp, y, colstats_region=None):
         """Forward from the planes of x (written by the producing depthwise kernel); with colstats_region the BatchNorm
         column sums of y are left there and the partial row count is returned."""
         tag = "x3p aB" if colstats_region is None else "x3p aB+stats"
-        return self._x3p(tag, zp, self.planes(0), y, self.cout, self.cin, colstats_region)
+        return self._x3(tag, zp, self.planes(0), y, self.cout, self.cin, a_planes=True, colstats_region=colstats_region)
 
     def bwd_p(self, zp, dyp, dx):
         """Backward from planes: dW = z^T dy by spnet_gemm_bf16x3_wgrad_batched (deferred into the engine's batched launch,
         or alone on the weight-gradient stream with a deterministic K split), dx = dy W^T by the planes x planes kernel."""
         e = self.e
+        job = _WgradJob(zp, dyp, self.gw, self.cin, self.cout, self.M, True)
         if self.defer_wgrad:
-            e.deferred_wgrads.append(("x3", zp, dyp, self.gw, self.cin, self.cout, self.M))
+            e.deferred_wgrads.append(job)
         else:
-            e._flush_x3_wgrads([("x3", zp, dyp, self.gw, self.cin, self.cout, self.M)])
+            e._flush_x3_wgrads([job])
         if dx is not None:
-            self._x3p("x3p ab", dyp, self.planes(1), dx, self.cin, self.cout)
+            self._x3("x3p ab", dyp, self.planes(1), dx, self.cin, self.cout, a_planes=True)
 
     def fwd(self, x, y):
         if self.x3_fwd and self.e.pointwise == "bf16x3":
-            self._x3("x3 aB", x, self.cin, self.planes(0), y, self.cout, self.cout, self.cin)
+            self._x3("x3 aB", x, self.planes(0), y, self.cout, self.cin)
             return
         _gemm(x, K_MAJOR, self.cin, self.w, OUT_MAJOR, self.cout, y, self.cout, self.M, self.cout, self.cin, self.e)
 
     def fwd_colstats(self, x, y, region=WS_BNP):
         """Forward + BatchNorm column sums of y left in `region`; returns the partial row count."""
         if self.x3_fwd and self.e.pointwise == "bf16x3":
-            return self._x3("x3 aB+stats", x, self.cin, self.planes(0), y, self.cout, self.cout, self.cin,
-                            colstats_region=region)
+            return self._x3("x3 aB+stats", x, self.planes(0), y, self.cout, self.cin, colstats_region=region)
         return _gemm_colstats(x, self.cin, self.w, self.cout, y, self.cout, self.M, self.cout, self.cin, self.e,
                               region=region)
 
-    def bwd(self, x, dy, dx):
-        """dW[cin,cout] = x^T dy ; dx[M,cin] = dy W^T.  The two products are independent: dW goes to the
-        engine's weight-gradient stream (own split-K workspace) and overlaps everything that follows on
-        the main stream until Engine.backward() joins the streams in front of the optimizer.  x and dy
-        are not rewritten before that join (they are only produced once per step)."""
+    def _wgrad(self, x, dy):
+        """dW[cin,cout] = x^T dy, independent of the data gradient: left to the engine's batched launch (defer_wgrad), or
+        one GEMM on the engine's weight-gradient stream (own split-K workspace) that overlaps everything that follows on
+        the main stream until Engine.backward() joins the streams in front of the optimizer.  x and dy are not
+        rewritten before that join (they are only produced once per step); dy has just been produced on the main stream."""
         e = self.e
-        side = e.wgrad_stream
         if self.defer_wgrad:
-            e.deferred_wgrads.append((x, dy, self.gw, self.cin, self.cout, self.M))
-        elif side is None:
-            _gemm(x, OUT_MAJOR, self.cin, dy, OUT_MAJOR, self.cout, self.gw, self.cout, self.cin, self.cout, self.M, e)
+            e.deferred_wgrads.append(_WgradJob(x, dy, self.gw, self.cin, self.cout, self.M, False))
         else:
-            side.wait_stream(torch.cuda.current_stream())      # dy has just been produced on the main stream
-            with torch.cuda.stream(side):
-                _gemm(x, OUT_MAJOR, self.cin, dy, OUT_MAJOR, self.cout, self.gw, self.cout, self.cin, self.cout,
-                      self.M, e, region=WS_GEMM2)
+            e.on_wgrad_stream(lambda region: _gemm(x, OUT_MAJOR, self.cin, dy, OUT_MAJOR, self.cout, self.gw, self.cout,
+                                                   self.cin, self.cout, self.M, e, region=region), WS_GEMM, WS_GEMM2)
+
+    def bwd(self, x, dy, dx):
+        """dW[cin,cout] = x^T dy (_wgrad) ; dx[M,cin] = dy W^T."""
+        e = self.e
+        self._wgrad(x, dy)
         if dx is not None and self.x3_dgrad and e.pointwise == "bf16x3":
-            self._x3("x3 ab", dy, self.cout, self.planes(1), dx, self.cin, self.cin, self.cout)
+            self._x3("x3 ab", dy, self.planes(1), dx, self.cin, self.cout)
         elif dx is not None:    # dx[M,cin] = dy[M,cout] @ W^T: W read in place as a K-major B operand
             _gemm(dy, K_MAJOR, self.cout, self.w, K_MAJOR, self.cout, dx, self.cin, self.M, self.cin, self.cout, e)
-
 
     def bwd_blend(self, x, g, yp, bn, dyb, dx):
         """Backward through BatchNorm + this 1x1 conv in two GEMMs and no elementwise pass: the data-gradient GEMM
         builds dy = BN'(g, yp) while staging its A operand (coefficients in bn.coef) and writes it to dyb once;
-        the weight-gradient GEMM (side stream / deferred batched launch) then reads dyb."""
-        e = self.e
-        prof = e.prof
-        t0 = prof.start() if prof is not None else None
-        L.spnet_gemm_f32_bnblend(L.ptr(g), L.ptr(yp), L.ptr(bn.coef), bn.cld, self.cout, L.ptr(self.wT), self.cin,
-                                 L.ptr(dx), self.cin, self.M, self.cin, self.cout, 0, L.ptr(dyb), _stream())
-        if prof is not None:
-            prof.stop("gemm", t0, 2.0 * self.M * self.cin * self.cout, ("aB blend", self.M, self.cin, self.cout))
-        side = e.wgrad_stream
-        if self.defer_wgrad:
-            e.deferred_wgrads.append((x, dyb, self.gw, self.cin, self.cout, self.M))
-        elif side is None:
-            _gemm(x, OUT_MAJOR, self.cin, dyb, OUT_MAJOR, self.cout, self.gw, self.cout, self.cin, self.cout, self.M, e)
-        else:
-            side.wait_stream(torch.cuda.current_stream())      # dyb has just been produced on the main stream
-            with torch.cuda.stream(side):
-                _gemm(x, OUT_MAJOR, self.cin, dyb, OUT_MAJOR, self.cout, self.gw, self.cout, self.cin, self.cout,
-                      self.M, e, region=WS_GEMM2)
+        the weight-gradient GEMM (_wgrad) then reads dyb."""
+        self.e.timed("gemm", 2.0 * self.M * self.cin * self.cout, ("aB blend", self.M, self.cin, self.cout),
+                     L.spnet_gemm_f32_bnblend, L.ptr(g), L.ptr(yp), L.ptr(bn.coef), bn.cld, self.cout, L.ptr(self.wT), self.cin,
+                     L.ptr(dx), self.cin, self.M, self.cin, self.cout, 0, L.ptr(dyb), _stream())
+        self._wgrad(x, dyb)
 
 
 class Conv3x3Gemm(Node):
@@ -1567,12 +1513,8 @@ class Conv3x3Gemm(Node):
 
     def _timed(self, flops, call):
         """Count the launch in the GEMM family of the kernel timers (same MFMA tile machinery)."""
-        prof = self.e.prof
-        if prof is None:
-            return call()
-        t0 = prof.start()
-        call()
-        prof.stop("gemm", t0, flops, ("conv3x3 implicit", int(flops / (2.0 * 9 * self.cin * self.cout)), self.cout, 9 * self.cin))
+        self.e.timed("gemm", flops, ("conv3x3 implicit", int(flops / (2.0 * 9 * self.cin * self.cout)), self.cout, 9 * self.cin),
+                     call)
 
     def fwd(self, training):
         e = self.e
@@ -1589,13 +1531,7 @@ class Conv3x3Gemm(Node):
     def bwd(self, g):
         """dW on the weight-gradient stream (independent of dX, like every other layer's), then dX."""
         e = self.e
-        side = e.wgrad_stream
-        if side is None:
-            self._wgrad(g, WS_GEMM)
-        else:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._wgrad(g, WS_GEMM2)
+        e.on_wgrad_stream(lambda region: self._wgrad(g, region), WS_GEMM, WS_GEMM2)
         self._timed(2.0 * e.B * self.H * self.W * 9 * self.cout * self.cin,
                     lambda: L.spnet_conv3x3_dgrad(L.ptr(g), L.ptr(self.w), L.ptr(self.dx), e.B, self.H, self.W,
                                                   self.cin, self.cout, _stream()))
@@ -1667,39 +1603,23 @@ class BN:
     def apply(self, x, y, act, residual=None):
         L.spnet_bn_apply(L.ptr(x), self.M, self.C, L.ptr(self.ss), act, L.ptr(residual), 0, L.ptr(y), _stream())
 
-    def bwd_full(self, x, g, out, act):
-        """Stand-alone backward (own reduction pass) of y = act(BN(x)); `out` may alias g."""
+    def bwd_full(self, x, g, out, act, planes=False):
+        """Stand-alone backward (own reduction pass) of y = act(BN(x)); `out` may alias g, or, with planes, is the bf16x3
+        plane set the result is written as (the operand of the pointwise layer's two backward GEMMs)."""
         e, C = self.e, self.C
-        L.spnet_bn_bwd(L.ptr(x), L.ptr(g), self.M, C, L.ptr(self.gamma), L.ptr(self.beta), self.mean_ptr,
-                       self.invstd_ptr, act, L.ptr(out), L.ptr(self.ggamma), L.ptr(self.gbeta), L.ptr(e.small[:3 * C]),
-                       e.ws_ptr(WS_MISC), _stream())
+        bn_bwd = L.spnet_bn_bwd_x3 if planes else L.spnet_bn_bwd
+        bn_bwd(L.ptr(x), L.ptr(g), self.M, C, L.ptr(self.gamma), L.ptr(self.beta), self.mean_ptr, self.invstd_ptr, act,
+               L.ptr(out), L.ptr(self.ggamma), L.ptr(self.gbeta), L.ptr(e.small[:3 * C]), e.ws_ptr(WS_MISC), _stream())
         return out
 
-    def bwd_from_partials(self, x, g, out, rows):
+    def bwd_from_partials(self, x, g, out, rows, planes=False):
         """Backward when the consumer's depthwise-backward epilogue already left (sum g, sum g*xhat)
-        as `rows` partial rows in WS_BNP."""
+        as `rows` partial rows in WS_BNP; `out` as in bwd_full."""
         e, C = self.e, self.C
-        L.spnet_bn_bwd_from_partials(L.ptr(x), L.ptr(g), self.M, C, L.ptr(self.gamma), L.ptr(self.beta),
-                                     self.mean_ptr, self.invstd_ptr, rows, e.ws_ptr(WS_BNP), L.ptr(out),
-                                     L.ptr(self.ggamma), L.ptr(self.gbeta), L.ptr(e.small[:3 * C]), _stream())
+        bn_bwd = L.spnet_bn_bwd_from_partials_x3 if planes else L.spnet_bn_bwd_from_partials
+        bn_bwd(L.ptr(x), L.ptr(g), self.M, C, L.ptr(self.gamma), L.ptr(self.beta), self.mean_ptr, self.invstd_ptr, rows,
+               e.ws_ptr(WS_BNP), L.ptr(out), L.ptr(self.ggamma), L.ptr(self.gbeta), L.ptr(e.small[:3 * C]), _stream())
         return out
-
-
-    def bwd_full_x3(self, x, g, out_planes, act):
-        """bwd_full with the result written as bf16x3 planes (the operand of the pointwise layer's two backward GEMMs)"""
-        e, C = self.e, self.C
-        L.spnet_bn_bwd_x3(L.ptr(x), L.ptr(g), self.M, C, L.ptr(self.gamma), L.ptr(self.beta), self.mean_ptr,
-                          self.invstd_ptr, act, L.ptr(out_planes), L.ptr(self.ggamma), L.ptr(self.gbeta),
-                          L.ptr(e.small[:3 * C]), e.ws_ptr(WS_MISC), _stream())
-        return out_planes
-
-    def bwd_from_partials_x3(self, x, g, out_planes, rows):
-        """bwd_from_partials with the result written as bf16x3 planes"""
-        e, C = self.e, self.C
-        L.spnet_bn_bwd_from_partials_x3(L.ptr(x), L.ptr(g), self.M, C, L.ptr(self.gamma), L.ptr(self.beta),
-                                        self.mean_ptr, self.invstd_ptr, rows, e.ws_ptr(WS_BNP), L.ptr(out_planes),
-                                        L.ptr(self.ggamma), L.ptr(self.gbeta), L.ptr(e.small[:3 * C]), _stream())
-        return out_planes
 
 
 class Ref:
@@ -1713,21 +1633,24 @@ class Ref:
         self.stats_bn, self.stats_x = stats_bn, stats_x
 
 
-def _dw_fwd(x, w, y, B, H, W, C, relu_in, scale_ptr, shift_ptr):
-    """Stride-1 depthwise forward y = dw3x3(relu?(x * scale + shift)): the streaming kernel where the library prefers it
-    (every plane: spnet_dwconv3x3_prefers_stream), else the LDS-tiled one -- same bits either way."""
+def _dw_fwd(x, w, y, B, H, W, C, relu_in, scale_ptr, shift_ptr, planes=False):
+    """Stride-1 depthwise forward y = dw3x3(relu?(x * scale + shift)), y an fp32 tensor or, with planes, a bf16x3 plane set:
+    the streaming kernel where the library prefers it (every plane: spnet_dwconv3x3_prefers_stream), else the LDS-tiled
+    one -- same bits either way."""
     if L.spnet_dwconv3x3_prefers_stream(B, H, W, C, 0):
-        L.spnet_dwconv3x3_stream_fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, relu_in, scale_ptr, shift_ptr, 0, _stream())
+        fwd = L.spnet_dwconv3x3_stream_fwd_x3 if planes else L.spnet_dwconv3x3_stream_fwd
+        fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, relu_in, scale_ptr, shift_ptr, 0, _stream())
     else:
-        L.spnet_dwconv3x3_tiled_fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, relu_in, scale_ptr, shift_ptr, _stream())
+        fwd = L.spnet_dwconv3x3_tiled_fwd_x3 if planes else L.spnet_dwconv3x3_tiled_fwd
+        fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, relu_in, scale_ptr, shift_ptr, _stream())
 
 
-def _dw_fwd_x3(x, w, zp, B, H, W, C, relu_in, scale_ptr, shift_ptr):
-    """_dw_fwd with the output written as bf16x3 planes"""
-    if L.spnet_dwconv3x3_prefers_stream(B, H, W, C, 0):
-        L.spnet_dwconv3x3_stream_fwd_x3(L.ptr(x), L.ptr(w), L.ptr(zp), B, H, W, C, relu_in, scale_ptr, shift_ptr, 0, _stream())
-    else:
-        L.spnet_dwconv3x3_tiled_fwd_x3(L.ptr(x), L.ptr(w), L.ptr(zp), B, H, W, C, relu_in, scale_ptr, shift_ptr, _stream())
+def _dw_fwd_bnfin(x, w, y, B, H, W, C, relu_in, part_ptr, rows, bn, planes=False):
+    """The LDS-tiled _dw_fwd with the training-forward finalize of the producer's BatchNorm `bn` (from the `rows` partial
+    rows at part_ptr) in its prologue."""
+    fwd = L.spnet_dwconv3x3_tiled_fwd_bnfin_x3 if planes else L.spnet_dwconv3x3_tiled_fwd_bnfin
+    fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, relu_in, part_ptr, rows, bn.M, L.ptr(bn.gamma), L.ptr(bn.beta),
+        L.ptr(bn.mm), L.ptr(bn.mv), bn.mean_ptr, bn.invstd_ptr, L.ptr(bn.ss), BN_EPS, BN_MOMENTUM, _stream())
 
 
 class _DwBwdPlan:
@@ -1828,28 +1751,25 @@ class SepConvBN:
         r.owner = self
         return r
 
-    def fwd(self, training):
+    def _dw(self, training):
+        """This unit's depthwise forward into z (planes mode: the planes zp)."""
         e, sb = self.e, self.src.bn
-        prof = e.prof
-        if prof is not None:
-            t0 = prof.start()
+        z = self.zp if self.x3p else self.z
         owner = getattr(self.src, "owner", None)
-        ran_dw = True
-        if self._dw_done and not training:      # the producer's forward GEMM ran this depthwise in its epilogue
-            self._dw_done = ran_dw = False
-        elif training and owner is not None and owner.pending_rows:
-            bnfin = L.spnet_dwconv3x3_tiled_fwd_bnfin_x3 if self.x3p else L.spnet_dwconv3x3_tiled_fwd_bnfin
-            bnfin(L.ptr(self.src.t), L.ptr(self.wd), L.ptr(self.zp if self.x3p else self.z), e.B, self.H, self.W,
-                  self.cin, self.relu_in, e.ws_ptr(WS_BNP), owner.pending_rows, sb.M,
-                  L.ptr(sb.gamma), L.ptr(sb.beta), L.ptr(sb.mm), L.ptr(sb.mv), sb.mean_ptr,
-                  sb.invstd_ptr, L.ptr(sb.ss), BN_EPS, BN_MOMENTUM, _stream())
+        if training and owner is not None and owner.pending_rows:
+            _dw_fwd_bnfin(self.src.t, self.wd, z, e.B, self.H, self.W, self.cin, self.relu_in, e.ws_ptr(WS_BNP),
+                          owner.pending_rows, sb, planes=self.x3p)
             owner.pending_rows = 0
         else:
-            (_dw_fwd_x3 if self.x3p else _dw_fwd)(self.src.t, self.wd, self.zp if self.x3p else self.z, e.B, self.H, self.W,
-                                                  self.cin, self.relu_in, sb.scale_ptr if sb else None,
-                                                  sb.shift_ptr if sb else None)
-        if prof is not None and ran_dw:
-            prof.stop("dw", t0, 2.0 * 4 * self.M * self.cin, ("dw fwd", self.H, self.W, self.cin))   # read x + write z
+            _dw_fwd(self.src.t, self.wd, z, e.B, self.H, self.W, self.cin, self.relu_in, sb.scale_ptr if sb else None,
+                    sb.shift_ptr if sb else None, planes=self.x3p)
+
+    def fwd(self, training):
+        e = self.e
+        if self._dw_done and not training:      # the producer's forward GEMM ran this depthwise in its epilogue
+            self._dw_done = False
+        else:
+            e.timed("dw", 2.0 * 4 * self.M * self.cin, ("dw fwd", self.H, self.W, self.cin), self._dw, training)    # read x + write z
         if training:
             rows = self.pw.fwd_p(self.zp, self.yp, WS_BNP) if self.x3p else self.pw.fwd_colstats(self.z, self.yp)
             if self.fin_by_consumer and rows <= 128:
@@ -1870,11 +1790,9 @@ class SepConvBN:
                     and ((self.M + 191) // 192) * ((self.cout + 95) // 96) >= e.fuse_min_tiles):
                 # inference: pointwise GEMM + this BatchNorm's affine + the consumer's ReLU and depthwise in ONE launch,
                 # the result written as the consumer's z planes (spnet_gemm_bf16x3_pp_dwfwd); yp is never written
-                t0 = prof.start() if prof is not None else None
-                L.spnet_gemm_bf16x3_pp_dwfwd(L.ptr(self.zp), L.ptr(self.pw.planes(0)), e.B, self.H, self.W, self.cin,
-                                             self.cout, L.ptr(self.bn.ss), nxt.relu_in, L.ptr(nxt.wd), L.ptr(nxt.zp), _stream())
-                if prof is not None:
-                    prof.stop("gemm", t0, 2.0 * self.M * self.cin * self.cout, ("x3p aB+dwfwd", self.M, self.cout, self.cin))
+                e.timed("gemm", 2.0 * self.M * self.cin * self.cout, ("x3p aB+dwfwd", self.M, self.cout, self.cin),
+                        L.spnet_gemm_bf16x3_pp_dwfwd, L.ptr(self.zp), L.ptr(self.pw.planes(0)), e.B, self.H, self.W, self.cin,
+                        self.cout, L.ptr(self.bn.ss), nxt.relu_in, L.ptr(nxt.wd), L.ptr(nxt.zp), _stream())
                 nxt._dw_done = True
                 return
             if self.x3p:
@@ -1895,42 +1813,30 @@ class SepConvBN:
             else:
                 self.bn.coeffs_full(self.yp, g)
             self.pw.bwd_blend(self.z, g, self.yp, self.bn, self.dyb, self.dz)
-        elif self.x3p:
-            if from_partials:
-                self.bn.bwd_from_partials_x3(self.yp, g, self.dyp, self.consumer_rows)
-            else:
-                self.bn.bwd_full_x3(self.yp, g, self.dyp, self.act if self.mode == "apply" else ACT_NONE)
-            self.pw.bwd_p(self.zp, self.dyp, self.dz)        # (fuse_bwd: dz is None -> the weight gradient only)
-            if self.fuse_bwd:
-                st = self.src.stats_bn if self.src.stats_bn is not None else sb
-                prof = e.prof
-                t0 = prof.start() if prof is not None else None
-                L.spnet_gemm_bf16x3_pp_dwbwd(L.ptr(self.dyp), L.ptr(self.pw.planes(1)), e.B, self.H, self.W, self.cin,
-                                             self.cout, L.ptr(self.src.t), L.ptr(self.wd), L.ptr(self.dx), self.relu_in,
-                                             L.ptr(add), L.ptr(self.wpart), sb.scale_ptr if sb else None,
-                                             sb.shift_ptr if sb else None, st.mean_ptr if st else None,
-                                             st.invstd_ptr if st else None, e.ws_ptr(WS_BNP) if st else None,
-                                             L.ptr(self.src.stats_x), _stream())
-                if prof is not None:
-                    prof.stop("gemm", t0, 2.0 * self.M * self.cin * self.cout, ("x3p ab+dwbwd", self.M, self.cin, self.cout))
-                return self.dx
         else:
-            out = g if self.bwd_inplace else self.dbn
+            # dy: in planes mode the plane set the pointwise layer's two backward GEMMs read, else in place on the incoming
+            # gradient (or into dbn)
+            out = self.dyp if self.x3p else (g if self.bwd_inplace else self.dbn)
             if from_partials:
-                dy = self.bn.bwd_from_partials(self.yp, g, out, self.consumer_rows)
+                dy = self.bn.bwd_from_partials(self.yp, g, out, self.consumer_rows, planes=self.x3p)
             else:
-                dy = self.bn.bwd_full(self.yp, g, out, self.act if self.mode == "apply" else ACT_NONE)
-            self.pw.bwd(self.z, dy, self.dz)
+                dy = self.bn.bwd_full(self.yp, g, out, self.act if self.mode == "apply" else ACT_NONE, planes=self.x3p)
+            if not self.x3p:
+                self.pw.bwd(self.z, dy, self.dz)
+            else:
+                self.pw.bwd_p(self.zp, dy, self.dz)        # (fuse_bwd: dz is None -> the weight gradient only)
         st = self.src.stats_bn if self.src.stats_bn is not None else sb     # whose backward sums to emit
-        prof = e.prof
-        if prof is not None:
-            t0 = prof.start()
-        self.dwb.run(self.dz, self.src.t, self.wd, self.dx, self.relu_in, add, self.wpart,
-                     sb.scale_ptr if sb else None, sb.shift_ptr if sb else None,
-                     st.mean_ptr if st else None, st.invstd_ptr if st else None,
-                     e.ws_ptr(WS_BNP) if st else None, self.src.stats_x)
-        if prof is not None:
-            prof.stop("dw", t0, 3.0 * 4 * self.M * self.cin, ("dw bwd", self.H, self.W, self.cin))   # read dz, read x, write dx
+        bn_ptrs = (sb.scale_ptr if sb else None, sb.shift_ptr if sb else None, st.mean_ptr if st else None,
+                   st.invstd_ptr if st else None, e.ws_ptr(WS_BNP) if st else None)
+        if self.fuse_bwd:       # the depthwise backward in the epilogue of the planes x planes data-gradient GEMM
+            e.timed("gemm", 2.0 * self.M * self.cin * self.cout, ("x3p ab+dwbwd", self.M, self.cin, self.cout),
+                    L.spnet_gemm_bf16x3_pp_dwbwd, L.ptr(self.dyp), L.ptr(self.pw.planes(1)), e.B, self.H, self.W, self.cin,
+                    self.cout, L.ptr(self.src.t), L.ptr(self.wd), L.ptr(self.dx), self.relu_in, L.ptr(add), L.ptr(self.wpart),
+                    *bn_ptrs, L.ptr(self.src.stats_x), _stream())
+        else:
+            e.timed("dw", 3.0 * 4 * self.M * self.cin, ("dw bwd", self.H, self.W, self.cin),   # read dz, read x, write dx
+                    self.dwb.run, self.dz, self.src.t, self.wd, self.dx, self.relu_in, add, self.wpart, *bn_ptrs,
+                    self.src.stats_x)
         return self.dx
 
 
@@ -2189,8 +2095,7 @@ class IRv2Backbone(Node):
                 ksl = int(L.spnet_gemm_batched_ksplit(K, C, M, len(members), ctypes.addressof(tile)))
                 for o in members:
                     o.deferred_wgrad = True
-                self.wg_groups.append(dict(members=members, K=K, C=C, M=M, ldb=ldb, ksl=ksl, tile=tile.value, table=None,
-                                           key=None))
+                self.wg_groups.append(dict(members=members, K=K, C=C, M=M, ldb=ldb, ksl=ksl, tile=tile.value))
                 if ksl > 1:
                     need = max(need, len(members) * ksl * K * C)
             self.wg_ws = eng.new(need) if need else None
@@ -2244,13 +2149,13 @@ class IRv2Backbone(Node):
 
     def flush_wgrads(self, groups=None):
         """Deferred weight gradients, one batched launch (+ one slab reduce) per shape, on the weight-gradient stream.
-        The operand offset tables live in device memory and are rebuilt only if a buffer address changed."""
+        The operand offset tables live in device memory (Engine._job_table)."""
         groups = self.wg_groups if groups is None else groups
         if not groups:
             return
         e = self.e
 
-        def run():
+        def run(_):
             for g in groups:
                 ms = g["members"]
                 for o in ms:
@@ -2258,25 +2163,13 @@ class IRv2Backbone(Node):
                 a0, b0, c0 = ms[0]._A().data_ptr(), ms[0].out.g.data_ptr(), ms[0].gw.data_ptr()
                 offs = tuple(v for o in ms for v in ((o._A().data_ptr() - a0) // 4, (o.out.g.data_ptr() - b0) // 4,
                                                      (o.gw.data_ptr() - c0) // 4))
-                if g["key"] != (a0, b0, c0) + offs:
-                    g["key"] = (a0, b0, c0) + offs
-                    g["table"] = torch.tensor(offs, dtype=torch.int64, device=e.dev)
+                table = e._job_table((a0, b0, c0) + offs, lambda: offs)
                 K, C, M, nb = g["K"], g["C"], g["M"], len(ms)
-                prof = e.prof
-                t0 = prof.start() if prof is not None else None
-                L.spnet_gemm_f32_batched_splitk(a0, b0, c0, g["table"].data_ptr(), nb, OUT_MAJOR, K, OUT_MAJOR, g["ldb"], C, K, C, M,
-                                                g["tile"], g["ksl"], L.ptr(self.wg_ws),
-                                                self.wg_ws.numel() if self.wg_ws is not None else 0, _stream())
-                if prof is not None:
-                    prof.stop("gemm", t0, 2.0 * nb * K * C * M, ("AB x%d batched" % nb, K, C, M))
+                e.timed("gemm", 2.0 * nb * K * C * M, ("AB x%d batched" % nb, K, C, M), L.spnet_gemm_f32_batched_splitk,
+                        a0, b0, c0, table.data_ptr(), nb, OUT_MAJOR, K, OUT_MAJOR, g["ldb"], C, K, C, M, g["tile"], g["ksl"],
+                        L.ptr(self.wg_ws), self.wg_ws.numel() if self.wg_ws is not None else 0, _stream())
 
-        side = e.wgrad_stream
-        if side is None:
-            run()
-        else:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                run()
+        e.on_wgrad_stream(run)
 
 
 def _ir_acc(t, gbuf, eng):
@@ -2354,27 +2247,18 @@ class _IRGroup:
         L.spnet_bn_bwd_from_partials(L.ptr(self.yp), L.ptr(g), self.M, Ct, L.ptr(self.ones), L.ptr(self.beta),
                                      L.ptr(self.save), self.save[Ct:].data_ptr(), self.rows, L.ptr(self.sum_part), L.ptr(g),
                                      L.ptr(self.gscr), L.ptr(self.gbeta), L.ptr(e.small[:3 * Ct]), _stream())
-        side = e.wgrad_stream
         late = [m for m in self.members if not m.deferred_wgrad]      # (shapes that occur once: no batched launch)
         if late:
             def wgrads(region):
                 for m in late:
                     _gemm(self.src.buf, OUT_MAJOR, self.cin, m.g_view, OUT_MAJOR, Ct, m.gw, m.cout, self.cin, m.cout,
                           self.M, e, region=region)
-            if side is None:
-                wgrads(WS_GEMM)
-            else:
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    wgrads(WS_GEMM2)
+            e.on_wgrad_stream(wgrads, WS_GEMM, WS_GEMM2)
         src = self.src
         if src.g is not None:
-            prof = e.prof
-            t0 = prof.start() if prof is not None else None
-            L.spnet_gemm_f32_accumulate(L.ptr(g), K_MAJOR, Ct, L.ptr(self.Wm), K_MAJOR, Ct, L.ptr(src.g), self.cin, self.M,
-                                        self.cin, Ct, _tile_for(K_MAJOR, K_MAJOR, 0, self.M, self.cin, Ct, 0), _stream())
-            if prof is not None:
-                prof.stop("gemm", t0, 2.0 * self.M * self.cin * Ct, ("aA+=", self.M, self.cin, Ct))
+            e.timed("gemm", 2.0 * self.M * self.cin * Ct, ("aA+=", self.M, self.cin, Ct), L.spnet_gemm_f32_accumulate,
+                    L.ptr(g), K_MAJOR, Ct, L.ptr(self.Wm), K_MAJOR, Ct, L.ptr(src.g), self.cin, self.M, self.cin, Ct,
+                    _tile_for(K_MAJOR, K_MAJOR, 0, self.M, self.cin, Ct, 0), _stream())
         else:
             _gemm(g, K_MAJOR, Ct, self.Wm, K_MAJOR, Ct, self.dx, self.cin, self.M, self.cin, Ct, e)
             _ir_acc(src, self.dx, e)
@@ -2468,19 +2352,16 @@ class _IRConv:
                                   self.W, e.ws_ptr(WS_MISC), WS_MISC[1], _stream())
         elif self.gathered:
             stats = training and not self.bias
-            prof = e.prof
-            t0 = prof.start() if prof is not None else None
-            L.spnet_conv_gemm_f32(L.ptr(self.src.buf), self.src.buf.stride(2), L.ptr(self.w), L.ptr(dst), C, e.B, self.H,
-                                  self.W, self.cin, C, self.kh, self.kw, self.stride, self.same,
-                                  L.ptr(self.b) if self.bias else None,
-                                  _tile_for(K_MAJOR, OUT_MAJOR, 1 if stats else 0, self.M, C, self.K, 0),
-                                  e.ws_ptr(WS_BNP) if stats else None,
-                                  ctypes.addressof(_stat_rows) if stats else None, _stream())
-            if prof is not None:
-                prof.stop("gemm", t0, 2.0 * self.M * C * self.K, ("conv gathered", self.M, C, self.K))
-                prof.keys[len(prof.records) - 1] = (K_MAJOR, OUT_MAJOR, 1 if stats else 0, self.M, C, self.K)
+            work, tag, key = 2.0 * self.M * C * self.K, ("conv gathered", self.M, C, self.K), \
+                (K_MAJOR, OUT_MAJOR, 1 if stats else 0, self.M, C, self.K)
+            args = (L.ptr(self.src.buf), self.src.buf.stride(2), L.ptr(self.w), L.ptr(dst), C, e.B, self.H, self.W, self.cin, C,
+                    self.kh, self.kw, self.stride, self.same, L.ptr(self.b) if self.bias else None, _tile_for(*key, 0))
             if stats:
-                L.spnet_bn_finalize_apply_ld(e.ws_ptr(WS_BNP), _stat_rows.value, L.ptr(self.yp), self.M, C, L.ptr(self.ones),
+                rows = e.timed("gemm", work, tag, _partial_rows, e, WS_BNP, self.M, C, 32, L.spnet_conv_gemm_f32, *args, key=key)
+            else:
+                e.timed("gemm", work, tag, L.spnet_conv_gemm_f32, *args, None, None, _stream(), key=key)
+            if stats:
+                L.spnet_bn_finalize_apply_ld(e.ws_ptr(WS_BNP), rows, L.ptr(self.yp), self.M, C, L.ptr(self.ones),
                                              L.ptr(self.beta), L.ptr(self.mm), L.ptr(self.mv), L.ptr(self.save),
                                              self.save[C:].data_ptr(), L.ptr(self.ss), ACT_RELU if self.relu else ACT_NONE,
                                              None, L.ptr(y), self.ldy, BN_EPS, BN_MOMENTUM, _stream())
@@ -2518,12 +2399,8 @@ class _IRConv:
             return
         e, C, g = self.e, self.cout, self.out.g
         if self.bias:       # a weight gradient like the kernel's: off the data-gradient chain (two launches per block)
-            if e.wgrad_stream is None:
-                L.spnet_reduce_rows_ws(L.ptr(g), self.M, C, L.ptr(self.gb), e.ws_ptr(WS_MISC), WS_MISC[1], _stream())
-            else:
-                e.wgrad_stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(e.wgrad_stream):
-                    L.spnet_reduce_rows_ws(L.ptr(g), self.M, C, L.ptr(self.gb), e.ws_ptr(WS_GEMM2), WS_GEMM2[1], _stream())
+            e.on_wgrad_stream(lambda region: L.spnet_reduce_rows_ws(L.ptr(g), self.M, C, L.ptr(self.gb), e.ws_ptr(region), region[1],
+                                                                    _stream()), WS_MISC, WS_GEMM2)
         elif self.sum_rows:     # my one consumer left the masked gradient in g and the two sums in sum_part
             L.spnet_bn_bwd_from_partials(L.ptr(self.yp), L.ptr(g), self.M, C, L.ptr(self.ones), L.ptr(self.beta),
                                          L.ptr(self.save), self.save[C:].data_ptr(), self.sum_rows, L.ptr(self.sum_part),
@@ -2532,7 +2409,6 @@ class _IRConv:
             L.spnet_bn_bwd(L.ptr(self.yp), L.ptr(g), self.M, C, L.ptr(self.ones), L.ptr(self.beta), L.ptr(self.save),
                            self.save[C:].data_ptr(), ACT_RELU if self.relu else ACT_NONE, L.ptr(g), L.ptr(self.gscr),
                            L.ptr(self.gbeta), L.ptr(e.small[:3 * C]), e.ws_ptr(WS_MISC), _stream())
-        side = e.wgrad_stream
         if self.small:
             def wgrad(region):
                 L.spnet_conv3x3_small(2, 3, C, self.stride, 0, L.ptr(self.src.buf), L.ptr(g), L.ptr(self.gw), e.B, self.H,
@@ -2541,26 +2417,17 @@ class _IRConv:
             def wgrad(region):
                 self.gather_patches()
                 _gemm(self._A(), OUT_MAJOR, self.K, g, OUT_MAJOR, C, self.gw, C, self.K, C, self.M, e, region=region)
-        if self.deferred_wgrad:
-            pass                                     # IRv2Backbone.flush_wgrads: g (= dy now) stays as it is until then
-        elif side is None:
-            wgrad(WS_GEMM)
-        else:           # weight gradient off the data-gradient chain (see Pointwise.bwd)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                wgrad(WS_GEMM2)
+        if not self.deferred_wgrad:     # (else IRv2Backbone.flush_wgrads: g (= dy now) stays as it is until then)
+            e.on_wgrad_stream(wgrad, WS_GEMM, WS_GEMM2)     # off the data-gradient chain (see Pointwise._wgrad)
         if self.small:
             L.spnet_conv3x3_small(1, 3, C, self.stride, 0, L.ptr(g), L.ptr(self.w), L.ptr(self.dx), e.B, self.H, self.W,
                                   e.ws_ptr(WS_MISC), WS_MISC[1], _stream())
         elif self.direct and self.src.g is not None:
             # another consumer of my input has already left its gradient in the accumulator: add mine in the GEMM's
             # epilogue (C += dY W^T) instead of a GEMM into dx + an accumulation pass -- same sum, same rounding
-            prof = e.prof
-            t0 = prof.start() if prof is not None else None
-            L.spnet_gemm_f32_accumulate(L.ptr(g), K_MAJOR, C, L.ptr(self.w), K_MAJOR, C, L.ptr(self.src.g), self.K, self.M,
-                                        self.K, C, _tile_for(K_MAJOR, K_MAJOR, 0, self.M, self.K, C, 0), _stream())
-            if prof is not None:
-                prof.stop("gemm", t0, 2.0 * self.M * self.K * C, ("aA+=", self.M, self.K, C))
+            e.timed("gemm", 2.0 * self.M * self.K * C, ("aA+=", self.M, self.K, C), L.spnet_gemm_f32_accumulate,
+                    L.ptr(g), K_MAJOR, C, L.ptr(self.w), K_MAJOR, C, L.ptr(self.src.g), self.K, self.M, self.K, C,
+                    _tile_for(K_MAJOR, K_MAJOR, 0, self.M, self.K, C, 0), _stream())
             return
         elif self.direct:
             _gemm(g, K_MAJOR, C, self.w, K_MAJOR, C, self.dx, self.K, self.M, self.K, C, e)
@@ -2777,14 +2644,13 @@ class Dense(Node):
 
     def bwd(self, g):
         e = self.e
-        side = e.wgrad_stream if e.early_head else None
-        if side is None:
-            _gemm(self.x, OUT_MAJOR, self.K, g, OUT_MAJOR, self.n_out, self.gw, self.n_out, self.K, self.n_out, e.B, e)
-        else:       # the 226 MB weight gradient (an outer product over the batch: pure HBM writes) leaves the dependency chain
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                _gemm(self.x, OUT_MAJOR, self.K, g, OUT_MAJOR, self.n_out, self.gw, self.n_out, self.K, self.n_out, e.B, e,
-                      region=WS_GEMM2)
+        def wgrad(region):
+            _gemm(self.x, OUT_MAJOR, self.K, g, OUT_MAJOR, self.n_out, self.gw, self.n_out, self.K, self.n_out, e.B, e,
+                  region=region)
+        if e.early_head:    # the 226 MB weight gradient (an outer product over the batch: pure HBM writes) leaves the dependency chain
+            e.on_wgrad_stream(wgrad, WS_GEMM, WS_GEMM2)
+        else:
+            wgrad(WS_GEMM)
         L.spnet_reduce_rows(L.ptr(g), e.B, self.n_out, L.ptr(self.gb), _stream())
         _gemm(g, K_MAJOR, self.n_out, self.w, K_MAJOR, self.n_out, self.dx, self.K, e.B, self.K, self.n_out, e)
         return self.dx

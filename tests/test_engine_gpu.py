@@ -363,3 +363,56 @@ def test_exact_chain_mode_and_bf16x3_mode_agree(setup):
     assert rel_err(outs[1].numpy(), outs[0].numpy()) <= 1e-5      # ... the same numbers
     with pytest.raises(ValueError):
         Engine(H, W, B, device="cuda:0", pointwise="bf16")
+
+
+# the weight-gradient launches of the Xception plan: entry -> (is this call one, index of its workspace argument or None)
+_WGRAD_LAUNCHES = {
+    "spnet_gemm_f32": (lambda a: (a[1], a[4]) == (1, 1), 12),
+    "spnet_gemm_f32_batched": (lambda a: True, None),
+    "spnet_gemm_bf16x3_wgrad_batched": (lambda a: True, None),
+    "spnet_reduce_slabs": (lambda a: True, 0),              # the ordered sum behind a K-split batched launch
+    "spnet_conv3x3_wgrad": (lambda a: True, 8),
+    "spnet_conv3x3_small": (lambda a: a[0] == 2, 11),
+    "spnet_stem_head": (lambda a: a[0] == 2, 8),
+    "spnet_reduce_rows_batched": (lambda a: True, None),
+}
+
+
+@pytest.mark.parametrize("overlap", ["1", "0"])
+def test_weight_gradient_launches_take_their_stream_and_its_workspace(monkeypatch, overlap):
+    """What Engine.on_wgrad_stream owns, under a tracer during one train step: with SPNET_OVERLAP_WGRAD=1 every
+    weight-gradient launch carries the weight-gradient stream's handle and, where it takes a workspace, one inside WS_GEMM2;
+    with SPNET_OVERLAP_WGRAD=0 every launch of the step is on the main stream and none of those workspaces is in WS_GEMM2."""
+    _need_gpu()
+    from spnet_amd import _lib as L
+    from spnet_amd.engine import Engine, WS_GEMM2
+    monkeypatch.setenv("SPNET_OVERLAP_WGRAD", overlap)
+    rs = np.random.RandomState(8)
+    X = torch.tensor(rs.rand(B, H, W, 1) * 2 - 1, dtype=torch.float32).cuda()
+    Y = torch.tensor(rs.rand(B, 576), dtype=torch.float32).cuda()
+    eng = Engine(H, W, B, device="cuda:0", seed=13, x3_min_tiles=0)
+    calls = []
+    L.set_tracer(lambda name, args, tok: calls.append((name, args)) if tok is None else None)
+    try:
+        eng.train_step(X, Y, 1e-3)
+    finally:
+        L.set_tracer(None)
+    torch.cuda.synchronize()
+    main = torch.cuda.current_stream().cuda_stream
+    lo = eng.ws_ptr(WS_GEMM2)
+    in_side_ws = lambda p: lo <= p < lo + 4 * WS_GEMM2[1]
+    wgrads = [(name, args) for name, args in calls if name in _WGRAD_LAUNCHES and _WGRAD_LAUNCHES[name][0](args)]
+    seen = {name for name, _ in wgrads}
+    assert seen >= {"spnet_gemm_f32", "spnet_gemm_bf16x3_wgrad_batched", "spnet_conv3x3_wgrad", "spnet_conv3x3_small",
+                    "spnet_stem_head", "spnet_reduce_rows_batched"}, seen
+    with_ws = [(name, args[_WGRAD_LAUNCHES[name][1]]) for name, args in wgrads if _WGRAD_LAUNCHES[name][1] is not None]
+    assert len(wgrads) > 0 and len(with_ws) > 0, (len(wgrads), len(with_ws))          # (not vacuous)
+    if overlap == "1":
+        side = eng.wgrad_stream.cuda_stream
+        assert side != main
+        assert [name for name, args in wgrads if args[-1] != side] == []
+        assert [name for name, p in with_ws if not in_side_ws(p)] == []
+    else:
+        assert eng.wgrad_stream is None
+        assert [name for name, args in calls if args[-1] != main] == []
+        assert [name for name, p in with_ws if in_side_ws(p)] == []

@@ -467,6 +467,34 @@ int spnet_warp_affine_fixed(const float* src, float* dst, int N, int H, int W, i
  * zeros, other flip codes mean none. */
 int spnet_warp_chain_u8(const unsigned char* src, int n_src, const int* sel, const void* params, int N, int H, int W,
                         unsigned char* out_u8, float* out_f, void* stream);
+/* Grid targets of B frames from their metadata rows (csrc/targets.hip): parse_meta_file's row processing ->
+ * true_to_pred_grid -> norm_Y (spnet/utils.py:260-286, 191-244, 181-184), one wave per frame, bit-identical to
+ * spnet_amd/augmentation.py _encode_targets.  rows [B][K][6] = cx, cy, a, b, angle_deg, rings in float64 (pad_metadata's
+ * layout), 1 <= K <= 16; count [B] = valid rows per frame, clamped to 0..K.  Per frame: a/b swapped and 90 degrees added
+ * where b > a; rows with rings <= 0 dropped; the kept rows ordered by (cx, cy), stably; ix = clip(trunc((cx - 40) / xbin),
+ * 0, nx - 1), iy likewise, in float64, xbin = 430 / nx, ybin = 310 / ny (integer divisions); an ellipse takes the next free
+ * slot of its cell; every other slot holds setup_means_and_ranges' blank values; the ellipse is cast to float32 and
+ * (G - means) / ranges formed in float32 with one correctly rounded subtract and one correctly rounded divide.
+ * Y [B][nx*ny*ns*8].  flags [B]: 0 fine; 1 a cell would take more than ns ellipses, Y holds those that fit.
+ * trig [360][2] = (cos, sin) of 2 * deg2rad(k) for the whole degrees k = 0..359, computed by the host in float64 and
+ * rounded to float: an angle that is integer-valued and in [0, 360) takes its entry (the same bits as the host codec), any
+ * other is cos / sin (2.0 * (angle * (pi / 180.0))) in float64, then cast (within one float32 step of the host's libm).
+ * fwd with warp_records (both or neither; then H, W = the frame size, >= 1): warp_metadata (spnet_amd/augmentation.py)
+ * is applied to the rows first, in float64 with its roundings.  fwd [B][8] = the six entries of the FORWARD
+ * rotation_matrix_2d, the rotation angle in degrees, one unused double; warp_records = the 64-byte records
+ * spnet_warp_chain_u8 reads, of which flip, xt and yt are used: cy = H - cy and angle = -angle for flip 0 / -1, cx = W - cx
+ * and angle = 180 - angle for flip 1 / -1, cleanup_angle's add / subtract 180 loops after each for every flip but -2; for
+ * a rotation angle != 0, angle + rot with the same cleanup and the centres as rint((m00 cx + m01 cy) + m02), each product
+ * and sum rounded on its own; then cx + xt, cy + yt.  A warped frame that overflows a cell is REJECTED as warp_targets
+ * rejects it: its UNWARPED rows are encoded, its warp record is overwritten with the identity (m = 1,0,0,0,1,0, flip -2,
+ * xt = yt = 0) and flags[b] = 1; flags[b] = 2 when the unwarped rows overflow as well (Y then holds those that fit).
+ * B == 0: nothing to do, success.  hipErrorInvalidValue (nothing launched or written): K outside 1..16; nx, ny or ns < 1;
+ * nx > 430 or ny > 310 (a bin of 0 pixels) or more than 2^24 slots; a NULL rows / count / trig / Y / flags; exactly one of
+ * fwd and warp_records; with them H or W < 1; rows / fwd / warp_records not 8-byte, the others not 4-byte aligned.  No
+ * value in rows causes an out-of-range access: NaN and huge centres clip into an edge cell, and cleanup_angle's loops end
+ * after 64 turns (bit-identity holds for angles within +-11,520 degrees). */
+int spnet_encode_targets(const double* rows, const int* count, int B, int K, int nx, int ny, int ns, int H, int W,
+                         const float* trig, const double* fwd, void* warp_records, float* Y, int* flags, void* stream);
 /* Dropout(0.1) of the stem (spnet/models.py:340); same call with dy regenerates the mask in backward. */
 int spnet_dropout(const float* x, float* y, long n, unsigned seed, float rate, const unsigned* seed_dev,
                   void* stream);   /* seed_dev (or NULL): device uint32 overriding seed (hipGraph replay) */

@@ -8,7 +8,9 @@ the PIXEL work runs in HIP kernels on frames that never leave HBM (csrc/augment.
 Offline warps (augment_preproc.py:56-100): flip / rotate / translate = one inverse-affine bilinear
 gather kernel plus the reference's host-side metadata arithmetic.  DeviceWarper is the batched, device-resident form: the
 whole flip -> rotate -> translate chain of a batch in one launch (csrc/warp.hip), bit-identical to the three calls, with the
-metadata arithmetic and the target codec vectorised on the host (warp_metadata, warp_targets).
+metadata arithmetic and the target codec vectorised on the host (warp_metadata, warp_targets) -- the oracle -- and run on the
+device by one more launch (csrc/targets.hip: encode_targets_device, DeviceWarper.targets_device), which keeps the labels of
+device-resident metadata in HBM.
 
 Band-pass mix-up (augmentation.py:10-62): BandpassPool holds the real frames and their low-frequency windows on the
 device, BandpassMixer draws and applies the mix-up (csrc/bandpass.hip), bandpass_mixup is the reference's function.
@@ -634,19 +636,94 @@ def warp_targets(meta, params, pred_grid=(6, 6, 2)):
     Y, rejected = _encode_targets(rows, count, pred_grid)
     if rejected.any():
         Y0, bad = _encode_targets(meta[0][rejected], meta[1][rejected], pred_grid)
-        assert not bad.any(), "the unwarped metadata itself puts more ellipses into a grid cell than it has slots"
+        assert not bad.any(), UNWARPED_OVERFLOW
         Y[rejected] = Y0
         for j in np.nonzero(rejected)[0]:
             set_warp(params, j, -2, 0.0, 0, 0)
     return Y, rejected
 
 
+_TRIG_2DEG = {}
+UNWARPED_OVERFLOW = "the unwarped metadata itself puts more ellipses into a grid cell than it has slots"
+
+
+def trig_2deg_table(device=None):
+    """(cos, sin) of 2 * deg2rad(k) for the whole degrees k = 0..359 as float32 [360,2], computed in float64 as
+    _encode_targets computes them: the table spnet_encode_targets reads for whole-degree angles (fake_espi.trig2_table's
+    idiom).  device: a cached device tensor instead of the numpy array."""
+    if "host" not in _TRIG_2DEG:
+        t = 2 * np.deg2rad(np.arange(360, dtype=np.float64))
+        _TRIG_2DEG["host"] = np.stack([np.cos(t), np.sin(t)], 1).astype(np.float32)
+    if device is None:
+        return _TRIG_2DEG["host"]
+    key = str(torch.device(device))
+    if key not in _TRIG_2DEG:
+        _TRIG_2DEG[key] = torch.from_numpy(_TRIG_2DEG["host"]).to(device)
+    return _TRIG_2DEG[key]
+
+
+def warp_fwd(params):
+    """float64 [B,8] for spnet_encode_targets: the six entries of the FORWARD rotation_matrix_2d of each frame of params
+    (the identity for angle 0, where it is not used), the angle, one unused zero -- the matrices warp_metadata forms."""
+    H, W = params["H"], params["W"]
+    fwd = np.zeros((len(params["angle"]), 8), np.float64)
+    fwd[:, 0] = fwd[:, 4] = 1.0
+    for j, a in enumerate(np.asarray(params["angle"], np.float64)):
+        if a != 0:
+            fwd[j, :6] = rotation_matrix_2d((W / 2, H / 2), a, 1.0).reshape(6)
+    fwd[:, 6] = params["angle"]
+    return fwd
+
+
+def encode_targets_device(rows, count, pred_grid=(6, 6, 2), fwd=None, records=None, frame_size=None):
+    """_encode_targets on the device (spnet_encode_targets, csrc/targets.hip): rows float64 [B,K,6], count int32 [B] device
+    tensors in pad_metadata's layout (K <= MAX_OBJECTS) -> (Y float32 [B, prod(pred_grid) * 8], flags int32 [B]) device
+    tensors; flags 0 = fine, 1 = a cell would take more ellipses than it has slots (Y holds those that fit).  Enqueued on
+    the current stream, nothing is copied to the host.  Whole-degree angles give the host codec's bits, others are within
+    one float32 step on cos / sin.
+    fwd (float64 [B,8], see warp_fwd) with records (the B 64-byte records of WARP_RECORD as a device tensor, 8-byte
+    aligned) and frame_size = (H, W): warp_targets instead -- the rows are warped first; a frame whose warp overflows a cell
+    has its unwarped rows encoded, its record overwritten with the identity IN PLACE and flag 1 (2: its unwarped rows
+    overflow as well, where warp_targets asserts)."""
+    for t, dt, name in ((rows, torch.float64, "rows"), (count, torch.int32, "count")):
+        _require_cuda(t)
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError("encode_targets_device: %s must be a contiguous %s device tensor" % (name, dt))
+    if rows.dim() != 3 or rows.shape[2] != 6 or count.shape != (rows.shape[0],):
+        raise ValueError("encode_targets_device: rows [B,K,6] and count [B], got %s and %s" % (tuple(rows.shape), tuple(count.shape)))
+    if (fwd is None) != (records is None) or (fwd is not None and frame_size is None):
+        raise ValueError("encode_targets_device: fwd, records and frame_size go together")
+    B, K = int(rows.shape[0]), int(rows.shape[1])
+    if fwd is not None:
+        if fwd.dtype != torch.float64 or not fwd.is_contiguous() or fwd.numel() != B * 8 or not records.is_contiguous() or \
+                records.numel() * records.element_size() != B * WARP_RECORD.itemsize:
+            raise ValueError("encode_targets_device: fwd must be contiguous float64 [%d,8] and records %d records of %d bytes"
+                             % (B, B, WARP_RECORD.itemsize))
+    nx, ny, ns = (int(v) for v in pred_grid)
+    H, W = (int(v) for v in frame_size) if frame_size is not None else (0, 0)
+    dev = rows.device
+    Y = torch.empty((B, nx * ny * ns * 8), dtype=torch.float32, device=dev)
+    flags = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B == 0:                           # (empty tensors have no address to pass)
+        return Y, flags
+    with torch.cuda.device(dev):
+        L.spnet_encode_targets(rows.data_ptr(), count.data_ptr(), B, K, nx, ny, ns, H, W, trig_2deg_table(dev).data_ptr(),
+                               L.ptr(fwd), L.ptr(records), Y.data_ptr(), flags.data_ptr(), _stream())
+    return Y, flags
+
+
 class DeviceWarper:
-    """Keeps pristine full-size uint8 frames [N,H,W] in HBM and their metadata rows on the host; warps batches of them
-    with one launch (csrc/warp.hip) and computes the matching targets on the host.
+    """Keeps pristine full-size uint8 frames [N,H,W] in HBM and their metadata rows on the host -- or, given as a pair of
+    device tensors (rows float64 [N,K,6], count int32 [N]), in HBM as well; warps batches of them with one launch
+    (csrc/warp.hip) and computes the matching targets on the host, or on the device (csrc/targets.hip).
       draw(indices, seeds=None) -> params (draw_warp per frame; per-frame seeding as DeviceAugmenter.draw)
-      targets(params)           -> (Y, rejected), see warp_targets (resets rejected frames' parameters to the identity)
-      apply(params, out_u8=None, out_f=None)   out[j] = warp of frame params['index'][j]"""
+      targets(params)           -> (Y, rejected), see warp_targets (resets rejected frames' parameters to the identity);
+                                   host metadata only: the oracle path
+      targets_device(params)    -> (Y, flags) device tensors, see encode_targets_device: params' records are uploaded,
+                                   the kernel rewrites those of rejected frames, and the apply(params) that follows
+                                   reuses them -- params on the host stay as drawn, and nothing is read back
+      apply(params, out_u8=None, out_f=None)   out[j] = warp of frame params['index'][j]
+      set_frames(X_u8, rows, count)            new frames and device metadata of the same shapes, copied in place"""
 
     def __init__(self, X_u8, meta=None, pred_grid=(6, 6, 2)):
         if isinstance(X_u8, np.ndarray):
@@ -663,12 +740,38 @@ class DeviceWarper:
         if not (1 <= self.H <= 2048 and 1 <= self.W <= 2048):
             raise ValueError("DeviceWarper: frames of %d x %d (sizes 1 .. 2048)" % (self.H, self.W))
         self.pred_grid = tuple(pred_grid)
-        self.meta = None
-        if meta is not None:
+        self.meta = self.meta_dev = None
+        if isinstance(meta, tuple) and isinstance(meta[0], torch.Tensor):
+            self.meta_dev = self._check_meta_dev(*meta)
+        elif meta is not None:
             self.meta = pad_metadata(meta)
             if self.meta[0].shape[0] != self.N:
                 raise ValueError("DeviceWarper: %d metadata entries for %d frames" % (self.meta[0].shape[0], self.N))
         self._upload = None
+        self._sent = None                   # (params, records, indices) of the last targets_device, for apply
+
+    def _check_meta_dev(self, rows, count):
+        if rows.device != self.X.device or count.device != self.X.device or rows.dtype != torch.float64 or \
+                count.dtype != torch.int32 or rows.dim() != 3 or tuple(rows.shape[::2]) != (self.N, 6) or \
+                not 1 <= rows.shape[1] <= MAX_OBJECTS or tuple(count.shape) != (self.N,):
+            raise ValueError("DeviceWarper: device metadata is (rows float64 [%d,K<=%d,6], count int32 [%d]) on %s"
+                             % (self.N, MAX_OBJECTS, self.N, self.X.device))
+        return rows.contiguous(), count.contiguous()
+
+    def set_frames(self, X_u8, rows, count):
+        """Refill for a new epoch, in place: frames uint8 [N,H,W] and device metadata of the shapes this warper holds
+        (tensors that ARE its own storage are left as they are).  Enqueued on the current stream."""
+        if self.meta_dev is None:
+            raise ValueError("DeviceWarper.set_frames: this warper holds host metadata")
+        rows, count = self._check_meta_dev(rows, count)
+        if X_u8.dtype != torch.uint8 or X_u8.device != self.X.device or X_u8.numel() != self.X.numel() or \
+                rows.shape != self.meta_dev[0].shape:
+            raise ValueError("DeviceWarper.set_frames: expected uint8 frames %s and rows %s"
+                             % (tuple(self.X.shape), tuple(self.meta_dev[0].shape)))
+        for dst, src in ((self.X, X_u8.reshape(self.X.shape)), (self.meta_dev[0], rows), (self.meta_dev[1], count)):
+            if dst.data_ptr() != src.data_ptr():
+                dst.copy_(src)
+        self._sent = None
 
     def new_params(self, indices):
         return new_warp_params(indices, self.H, self.W)
@@ -697,6 +800,30 @@ class DeviceWarper:
         idx = np.asarray(params["index"], np.int64)
         return warp_targets((self.meta[0][idx], self.meta[1][idx]), params, self.pred_grid)
 
+    def _send(self, params, fwd=None):
+        """One host -> device copy: the records (8-byte aligned at the front), fwd (or nothing), then the source indices.
+        Returns (records [16 B], fwd [B,8] float64 or None, indices [B]) as views of it."""
+        B = len(params["index"])
+        rec = np.zeros(B, WARP_RECORD)
+        rec["m"], rec["flip"], rec["xt"], rec["yt"] = params["minv"], params["flip"], params["xt"], params["yt"]
+        parts = [rec.view(np.int32).reshape(-1)] + ([] if fwd is None else [fwd.view(np.int32).reshape(-1)]) + \
+                [np.asarray(params["index"], np.int32)]
+        if self._upload is None:
+            self._upload = L.AsyncUploader(self.X.device)
+        packed = self._upload("warp" if fwd is None else "warp+fwd", np.concatenate(parts))
+        self._keep = packed
+        nf = 0 if fwd is None else 16 * B
+        return packed[:16 * B], (packed[16 * B:16 * B + nf].view(torch.float64).view(B, 8) if nf else None), packed[16 * B + nf:]
+
+    def targets_device(self, params):
+        if self.meta_dev is None:
+            raise ValueError("DeviceWarper.targets_device: the metadata must be device tensors (rows, count)")
+        rec, fwd, index = self._send(params, warp_fwd(params))
+        self._sent = (params, rec, index)
+        with torch.cuda.device(self.X.device):
+            rows, count = self.meta_dev[0].index_select(0, index), self.meta_dev[1].index_select(0, index)
+            return encode_targets_device(rows, count, self.pred_grid, fwd, rec, (self.H, self.W))
+
     def apply(self, params, out_u8=None, out_f=None):
         B = len(params["index"])
         if out_u8 is None and out_f is None:
@@ -708,15 +835,13 @@ class DeviceWarper:
                                  % (dt, B, self.H, self.W))
         if B == 0:
             return out_u8, out_f
-        rec = np.zeros(B, WARP_RECORD)
-        rec["m"], rec["flip"], rec["xt"], rec["yt"] = params["minv"], params["flip"], params["xt"], params["yt"]
-        if self._upload is None:
-            self._upload = L.AsyncUploader(self.X.device)
-        # one host -> device copy: the records (8-byte aligned at the front), then the source indices
-        packed = self._upload("warp", np.concatenate([rec.view(np.int32).reshape(-1), np.asarray(params["index"], np.int32)]))
-        self._keep = packed
+        if self._sent is not None and self._sent[0] is params:      # targets_device's upload, rejected records rewritten
+            _, rec, index = self._sent
+        else:
+            rec, _, index = self._send(params)
+        self._sent = None
         with torch.cuda.device(self.X.device):
-            L.spnet_warp_chain_u8(self.X.data_ptr(), self.N, packed[16 * B:].data_ptr(), packed.data_ptr(), B, self.H, self.W,
+            L.spnet_warp_chain_u8(self.X.data_ptr(), self.N, index.data_ptr(), rec.data_ptr(), B, self.H, self.W,
                                   L.ptr(out_u8), L.ptr(out_f), _stream())
         return out_u8, out_f
 

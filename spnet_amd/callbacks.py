@@ -93,7 +93,8 @@ class AugmentOnTheFly(Callback):
     fit() reads batches from (`model.set_train_frames`)."""
 
     def __init__(self, X, Y, orig_img_shape=(384, 512), aug_every=1, chunk=256, seed=1, real_blur=False,
-                 bandpass_real=None, bpmix_prob=0.3, warp=False, warp_files=None, pred_grid=(6, 6, 2)):
+                 bandpass_real=None, bpmix_prob=0.3, warp=False, warp_files=None, pred_grid=(6, 6, 2), warp_source=None,
+                 warp_targets="host"):
         """real_blur=False reproduces the reference, whose Gaussian blur is a no-op (the result of cv2.GaussianBlur is
         discarded, augmentation.py:66-70); True applies it (train_spnet.py --augment_blur).
         bandpass_real: directory of real *.png frames of the training frames' size -- after the blur, a frame is
@@ -107,7 +108,14 @@ class AugmentOnTheFly(Callback):
         warp_targets) into Y_aug, which fit() trains on (Model.set_train_targets).  A frame whose warp would put a third
         ellipse into a grid cell keeps its unwarped pixels and targets for that epoch (counted, printed once per epoch).
         The cutout fill range stays that of the unwarped frame.  warp=False (default): nothing of this exists, the RNG
-        stream and the frames are what they were."""
+        stream and the frames are what they were.
+        warp_source (instead of warp_files; implies warp): an augmentation.DeviceWarper that holds the full-size frames
+        of X's rows AND their metadata as device tensors -- frames that have no files (FreshFakeESPI(..., warper=...)
+        refills it every epoch).  warp_targets: "host" (default) = the targets of a chunk are computed in numpy
+        (warp_targets) before its warp is launched; "device" (needs device metadata, so a warp_source; and a warp_source
+        needs it) = they come from spnet_encode_targets, which also rewrites the warp records of the rejected frames: a
+        chunk is records upload -> targets -> warp -> resize -> cutout ... with no synchronisation between them, and the
+        rejected count is summed on the device and read once per epoch."""
         super().__init__()
         import torch
         from . import parallel
@@ -125,21 +133,36 @@ class AugmentOnTheFly(Callback):
                                          bpmix_prob=bpmix_prob)
         self.warper = None
         self.rejected = 0                     # frames of the last augmented epoch whose warp was rejected
-        if warp:
-            self._setup_warp(warp_files, pred_grid, dev)
+        if warp_targets not in ("host", "device"):
+            raise ValueError("AugmentOnTheFly: warp_targets must be 'host' or 'device', got %r" % (warp_targets,))
+        if (warp_source is not None) != (warp_targets == "device"):
+            raise ValueError("AugmentOnTheFly: warp_source and warp_targets='device' go together (the device codec reads "
+                             "device metadata; files' metadata is on the host)")
+        self.warp_targets = warp_targets
+        if warp or warp_source is not None:
+            self._setup_warp(warp_files, pred_grid, dev, warp_source)
 
-    def _setup_warp(self, warp_files, pred_grid, dev):
+    def _setup_warp(self, warp_files, pred_grid, dev, warp_source=None):
         import torch
         from .augmentation import DeviceWarper
         n = int(self.X_orig.shape[0])
-        if warp_files is None or len(warp_files) != n:
-            raise ValueError("AugmentOnTheFly(warp=True) needs warp_files: the PNG file of each of the %d training frames" % n)
         if self.X_orig.dim() != 4 or self.X_orig.shape[-1] != 1:
             raise ValueError("AugmentOnTheFly(warp=True) is for one-channel frames [N,H,W,1]")
-        files = list(warp_files)
-        X_full, _ = utils.build_X(n, files, grayscale=True, as_uint8=True, device_resize=True)
-        meta = [utils.read_metadata(os.path.splitext(f)[0] + cf.meta_extension) for f in files]
-        self.warper = DeviceWarper(torch.from_numpy(X_full[..., 0]).to(dev), meta, pred_grid=pred_grid)
+        if warp_source is not None:
+            if warp_files is not None:
+                raise ValueError("AugmentOnTheFly: warp_files or warp_source, not both")
+            if warp_source.N != n or warp_source.meta_dev is None or tuple(warp_source.pred_grid) != tuple(pred_grid):
+                raise ValueError("AugmentOnTheFly: warp_source must hold the %d training frames with device metadata and "
+                                 "pred_grid %s" % (n, tuple(pred_grid)))
+            self.warper = warp_source
+            self._counts = torch.zeros(2, dtype=torch.int64, device=dev)      # rejected warps, unwarped overflows
+        else:
+            if warp_files is None or len(warp_files) != n:
+                raise ValueError("AugmentOnTheFly(warp=True) needs warp_files: the PNG file of each of the %d training frames" % n)
+            files = list(warp_files)
+            X_full, _ = utils.build_X(n, files, grayscale=True, as_uint8=True, device_resize=True)
+            meta = [utils.read_metadata(os.path.splitext(f)[0] + cf.meta_extension) for f in files]
+            self.warper = DeviceWarper(torch.from_numpy(X_full[..., 0]).to(dev), meta, pred_grid=pred_grid)
         Yh = self.Y.detach().cpu().numpy() if isinstance(self.Y, torch.Tensor) else np.asarray(self.Y)
         self.Y_aug = torch.from_numpy(np.ascontiguousarray(Yh, dtype=np.float32)).to(dev)
         self._y_upload = None
@@ -147,7 +170,7 @@ class AugmentOnTheFly(Callback):
 
     def _augment_chunk(self, idx, seeds, out):
         """out[j] = augmented frame idx[j] (device [B,h,w,1]); with warp: warped first, and -> (Y [B,576] device, number
-        of rejected frames), else None."""
+        of rejected frames -- 0 with warp_targets="device", which counts them in self._counts instead), else None."""
         import torch
         from . import _lib as L
         aug, wr = self.augmenter, self.warper
@@ -156,8 +179,13 @@ class AugmentOnTheFly(Callback):
             return None
         wp = wr.new_params(idx)
         p = aug.draw(idx, seeds=seeds, before=lambda j, i: wr.draw_into(wp, j))
+        device_targets = self.warp_targets == "device"
         t0 = time.time()
-        Y, rejected = wr.targets(wp)
+        if device_targets:
+            Y, flags = wr.targets_device(wp)          # ahead of the warp: it rewrites the rejected frames' records
+            self._counts += torch.stack([(flags != 0).sum(), (flags == 2).sum()])
+        else:
+            Y, rejected = wr.targets(wp)
         self.label_seconds += time.time() - t0
         B, dev = len(idx), self.X_aug.device
         warped = torch.empty((B, aug.H, aug.W), dtype=torch.float32, device=dev)
@@ -168,13 +196,22 @@ class AugmentOnTheFly(Callback):
             full = torch.empty((B, wr.H, wr.W), dtype=torch.uint8, device=dev)
             wr.apply(wp, out_u8=full)
             resize_u8_device(full, (aug.H, aug.W), out_f=warped)
+            self.last_full = full             # the chunk's warped full-size frames (tests)
         aug.apply(p, out, src=warped)
+        self.last_warp = wp
+        if device_targets:
+            return Y, 0
         if self._y_upload is None:
             self._y_upload = L.AsyncUploader(dev)
-        self.last_warp = wp
         return self._y_upload("Y", Y), int(rejected.sum())
 
     def _report_rejected(self):
+        if self.warper is not None and self.warp_targets == "device":       # the epoch's one read back of the label path
+            from .augmentation import UNWARPED_OVERFLOW
+            self.rejected, overflowed = (int(v) for v in self._counts.tolist())
+            self._counts.zero_()
+            if overflowed:
+                raise AssertionError(UNWARPED_OVERFLOW)
         if self.warper is not None:
             print("   Augmenting on the fly: %d warps rejected (a third ellipse in one grid cell): those frames keep their "
                   "unwarped targets this epoch" % self.rejected)
@@ -246,12 +283,25 @@ class FreshFakeESPI(Callback):
     the augmenter's pristine set (it keeps a device tensor as it is); AugmentOnTheFly then writes cutout / salt and pepper
     / blur / band-pass mix-up of them into its X_aug, which is what fit() reads (it registers last).  The cutout fill
     range is the min / max of the frames AugmentOnTheFly was built on (epoch first_epoch's; a noisy fake-ESPI frame spans
-    the whole range).  warp=True is not meant for streamed frames (it needs files)."""
+    the whole range).
 
-    def __init__(self, X, Y, stream, first_epoch=0, verbose=True):
+    warper (True, or an augmentation.DeviceWarper with device metadata for n frames of 384 x 512): the stream also keeps
+    each epoch's full-size uint8 frames and label rows on the device (stream.epoch(keep_u8=True)) and the warper -- True:
+    one built on those very tensors, cb.warper -- is refilled with them (set_frames) at every epoch begin, before the
+    AugmentOnTheFly(cb.X_dev, cb.Y, warp_source=cb.warper, warp_targets="device") listed behind this callback warps them:
+    fresh frames every epoch and a fresh flip / rotation / shift of each, no file and no label on the host."""
+
+    def __init__(self, X, Y, stream, first_epoch=0, verbose=True, warper=None):
         super().__init__()
         self.stream, self.first_epoch, self.verbose = stream, int(first_epoch), verbose
-        self.X_dev, self.Y_dev = stream.epoch(self.first_epoch, verbose=False)
+        self.warper = None
+        self.X_dev, self.Y_dev = stream.epoch(self.first_epoch, verbose=False, keep_u8=bool(warper))
+        if warper:
+            if warper is True:
+                from .augmentation import DeviceWarper
+                warper = DeviceWarper(stream.U_full, (stream.rows, stream.count), pred_grid=stream.pred_grid)
+            self.warper = warper
+            warper.set_frames(stream.U_full, stream.rows, stream.count)
         self.X = self.X_dev if X is None else X
         self.Y = self.Y_dev.cpu().numpy() if Y is None else Y
         if tuple(self.X.shape) != tuple(self.X_dev.shape) or tuple(self.Y.shape) != tuple(self.Y_dev.shape):
@@ -266,7 +316,10 @@ class FreshFakeESPI(Callback):
 
     def on_epoch_begin(self, epoch, logs=None):
         e = self.first_epoch + len(self.epochs_filled)
-        self.stream.epoch(e, self.X_dev, self.Y_dev, verbose=self.verbose and getattr(self.model, "rank", 0) == 0)
+        self.stream.epoch(e, self.X_dev, self.Y_dev, verbose=self.verbose and getattr(self.model, "rank", 0) == 0,
+                          keep_u8=self.warper is not None)
+        if self.warper is not None:
+            self.warper.set_frames(self.stream.U_full, self.stream.rows, self.stream.count)
         self.epochs_filled.append(e)
 
 

@@ -190,8 +190,14 @@ def labels_from_params(nodes, nnode):
     return [[tuple(r) for r in fr[:int(k)]] for fr, k in zip(rows, np.asarray(nnode))]
 
 
+def rows_from_params(nodes, nnode):
+    """Device parameter arrays nodes [n,7,8], nnode [n] -> (rows float64 [n,7,6], count int32 [n]) device tensors in
+    augmentation.pad_metadata's layout: the values labels_from_params reads back (whole numbers), left in HBM."""
+    return nodes[..., :6].trunc().double().contiguous(), nnode.contiguous()
+
+
 def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk=1024, count_range=(1, 7),
-                    bandpass_real=None, size=None, params="host", first_frame=0):
+                    bandpass_real=None, size=None, params="host", first_frame=0, labels="host", full_u8=None):
     """n frames rasterised directly in HBM (csrc/espi.hip): the SAME per-frame parameters as generate(n, seed)
     (so the labels are identical), pixels from the analytic device rasteriser, sensor noise / dropout from a
     counter-based RNG.  Returns (float32 device tensor [n,384,512,1] in [-1,1], label rows[, uint8 device tensor]).
@@ -205,11 +211,20 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
     frame by frame; "device" = drawn by draw_params_device for the GLOBAL frames first_frame .. first_frame + n - 1, chunk
     by chunk, the labels read back in one copy per chunk: the same distributions, other frames, and parameters / labels /
     noise-free pixels that do not depend on `chunk`.  The sensor noise keeps its seed of (seed, chunk start) as before
-    (first_frame shifts the chunk start, so that another range of frames gets other noise); first_frame needs "device"."""
+    (first_frame shifts the chunk start, so that another range of frames gets other noise); first_frame needs "device".
+    labels: "host" (default) = the label rows as Python lists; "device" (needs params="device") = rows_from_params' pair of
+    device tensors instead, and no label crosses to the host.
+    full_u8 (with size; a uint8 device tensor [n,384,512]): also receives the frames at their full size, as rasterised (and
+    mixed), i.e. what the resize reads."""
     import torch
     from . import _lib as L
     if params not in ("host", "device"):
         raise ValueError("generate_device: params must be 'host' or 'device', got %r" % (params,))
+    if labels not in ("host", "device") or (labels == "device" and params != "device"):
+        raise ValueError("generate_device: labels must be 'host' or 'device' (which needs params='device'), got %r" % (labels,))
+    if full_u8 is not None and (size is None or full_u8.dtype != torch.uint8 or tuple(full_u8.shape) != (n, IM_H, IM_W)
+                                or not full_u8.is_contiguous()):
+        raise ValueError("generate_device: full_u8 goes with size and is a contiguous uint8 tensor [%d,%d,%d]" % (n, IM_H, IM_W))
     if first_frame and params != "device":
         raise ValueError("generate_device: first_frame needs params='device' (the host stream is keyed by (n, seed))")
     dev = torch.device(device)
@@ -224,13 +239,22 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
         OH, OW = _size(size)
     X = torch.empty((n, OH, OW, 1), dtype=torch.float32, device=dev)
     U = torch.empty((n, OH, OW), dtype=torch.uint8, device=dev) if (want_u8 or (mixer is not None and size is None)) else None
+    dev_labels = labels == "device"
     labels = []
+    if dev_labels:
+        rows_d = torch.empty((n, 7, 6), dtype=torch.float64, device=dev)
+        count_d = torch.empty((n,), dtype=torch.int32, device=dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     for lo in range(0, n, chunk):
         hi = min(n, lo + chunk)
         if params == "device":
             wd, ndd, nnd = draw_params_device(hi - lo, seed, dev, count_range, first_frame + lo)
-            labels += labels_from_params(ndd, nnd)
+            if dev_labels:
+                r, c = rows_from_params(ndd, nnd)
+                rows_d[lo:hi].copy_(r)
+                count_d[lo:hi].copy_(c)
+            else:
+                labels += labels_from_params(ndd, nnd)
         else:
             waves = np.zeros((hi - lo, 5), np.float32)
             nodes = np.zeros((hi - lo, 7, 8), np.float32)
@@ -247,7 +271,8 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
         if size is None:
             Xc, Uc = X[lo:hi], (U[lo:hi] if U is not None else None)
         else:               # the 384x512 uint8 frames of this chunk only; X / U receive them resized
-            Xc, Uc = None, torch.empty((hi - lo, IM_H, IM_W), dtype=torch.uint8, device=dev)
+            Xc = None
+            Uc = full_u8[lo:hi] if full_u8 is not None else torch.empty((hi - lo, IM_H, IM_W), dtype=torch.uint8, device=dev)
         L.spnet_fake_espi(wd.data_ptr(), ndd.data_ptr(), nnd.data_ptr(), hi - lo, IM_H, IM_W,
                           (seed * 2654435761 + (first_frame + lo) * 97 + 12345) & 0xFFFFFFFF, int(bool(noise)), L.ptr(Xc),
                           L.ptr(Uc), st)
@@ -258,6 +283,8 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
         if size is not None:
             resize_u8_device(Uc, (OH, OW), out_f=X[lo:hi], out_u8=None if U is None else U[lo:hi])
         torch.cuda.current_stream(dev).synchronize()       # wd / ndd / nnd (/ Uc) are freed on return
+    if dev_labels:
+        labels = (rows_d, count_d)
     return (X, labels, U) if want_u8 else (X, labels)
 
 
@@ -276,10 +303,16 @@ class FakeStream:
     """An endless supply of fake-ESPI training frames: epoch e is the n global frames e*n .. e*n + n - 1 of the device
     parameter stream (generate_device(params="device")), with their normalised grid targets.  Nothing is read from or
     written to disk.  size: None = native 384x512 frames (model_type 'big'), 331 = the default layout (resized on the device
-    as the input codec resizes)."""
+    as the input codec resizes).  targets: "device" (default) = the labels stay in HBM and the targets come from
+    spnet_encode_targets (augmentation.encode_targets_device; the drawn angles are whole degrees, so the same bits); "host"
+    = the labels are read back and encoded in numpy (targets_from_labels), the oracle of the former."""
 
     def __init__(self, n, seed=0, device="cuda:0", size=None, count_range=(1, 7), pred_grid=(6, 6, 2), bandpass_real=None,
-                 chunk=1024):
+                 chunk=1024, targets="device"):
+        if targets not in ("device", "host"):
+            raise ValueError("FakeStream: targets must be 'device' or 'host', got %r" % (targets,))
+        self.targets = targets
+        self.U_full = self.rows = self.count = None         # epoch(keep_u8=True): full-size frames and device label rows
         self.n, self.seed, self.device, self.size = int(n), int(seed), device, size
         self.count_range, self.pred_grid, self.bandpass_real, self.chunk = tuple(count_range), tuple(pred_grid), bandpass_real, chunk
         if size is None:
@@ -291,23 +324,48 @@ class FakeStream:
         self.n_targets = int(np.prod(self.pred_grid)) * cf.vars_per_pred
         self.overflowed = 0                 # frames of the last epoch() with a third ellipse in one grid cell
 
-    def frames(self, first_frame, n, want_u8=False):
+    def frames(self, first_frame, n, want_u8=False, **kw):
         """generate_device for the global frames first_frame .. first_frame + n - 1 of this stream."""
         return generate_device(n, self.seed, self.device, count_range=self.count_range, bandpass_real=self.bandpass_real,
-                               size=self.size, chunk=self.chunk, params="device", first_frame=first_frame, want_u8=want_u8)
+                               size=self.size, chunk=self.chunk, params="device", first_frame=first_frame, want_u8=want_u8, **kw)
 
-    def epoch(self, e, out_X=None, out_Y=None, verbose=True):
+    def epoch(self, e, out_X=None, out_Y=None, verbose=True, keep_u8=False):
         """Fills out_X [n,H,W,1] float32 and out_Y [n, n_targets] float32 (device tensors; allocated when None) with the
         frames and targets of epoch e; returns (out_X, out_Y).  A frame with a third ellipse in one grid cell keeps the two
-        that fit (the file path would assert); their number is kept in self.overflowed and printed."""
+        that fit (the file path would assert); their number is kept in self.overflowed (with targets="device": the
+        epoch's one scalar read back) and printed.
+        keep_u8 (needs targets="device"): the epoch's full-size 384x512 uint8 frames and its label rows stay in self.U_full
+        [n,384,512], self.rows [n,7,6] float64 and self.count [n] int32 -- the same three tensors every epoch, rewritten
+        in place: what a DeviceWarper built on them warps."""
         import torch
-        X, labels = self.frames(int(e) * self.n, self.n)
-        Y, overflow = targets_from_labels(labels, self.pred_grid)
-        self.overflowed = int(overflow.sum())
+        if keep_u8 and self.targets != "device":
+            raise ValueError("FakeStream.epoch: keep_u8 needs targets='device' (the label rows stay on the device)")
+        kw = {}
+        if keep_u8:
+            if self.U_full is None:
+                self.U_full = torch.empty((self.n, IM_H, IM_W), dtype=torch.uint8, device=self.device)
+            kw = dict(full_u8=self.U_full) if self.size is not None else dict(want_u8=True)
+        if self.targets == "device":
+            from .augmentation import encode_targets_device
+            X, (rows, count), *U = self.frames(int(e) * self.n, self.n, labels="device", **kw)
+            Yd, flags = encode_targets_device(rows, count, self.pred_grid)
+            self.overflowed = int((flags != 0).sum())
+            if keep_u8:
+                if U:                       # native frames: the uint8 frames themselves
+                    self.U_full.copy_(U[0])
+                if self.rows is None:
+                    self.rows, self.count = rows, count
+                else:
+                    self.rows.copy_(rows)
+                    self.count.copy_(count)
+        else:
+            X, labels = self.frames(int(e) * self.n, self.n)
+            Y, overflow = targets_from_labels(labels, self.pred_grid)
+            self.overflowed = int(overflow.sum())
+            Yd = torch.from_numpy(Y).to(X.device)
         if verbose:
             print("   Fresh fake-ESPI frames: epoch %d = frames %d .. %d; %d frames with a third ellipse in one grid cell keep "
                   "the two that fit" % (e, int(e) * self.n, int(e) * self.n + self.n - 1, self.overflowed))
-        Yd = torch.from_numpy(Y).to(X.device)
         if out_X is None:
             out_X = X
         else:

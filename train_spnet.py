@@ -24,13 +24,15 @@ from predict_spnet import default_image_dir, predict_network
 VAL_STREAM_TOP = 2 ** 40      # the validation frames of --fake_stream are the LAST M global frame indices below this
 
 
-def fake_stream_data(n_train, n_val, global_batch, pred_grid, seed):
+def fake_stream_data(n_train, n_val, global_batch, pred_grid, seed, warp=False):
     """--fake_stream: (X_train, Y_train, X_val, Y_val, FreshFakeESPI callback, pred_shape).  The training set is n_train
     (rounded down to a multiple of the global batch) fresh frames per epoch: epoch e = the global frames e*n .. e*n + n - 1
     of the device parameter stream.  The validation set, n_val frames (default n_train // 4), is generated once from the
     frame indices VAL_STREAM_TOP - n_val .. VAL_STREAM_TOP - 1: the top of the index space this script uses, which training
     would reach only after 2^40 / n frames' worth of epochs.  The layout follows cf.model_type: 331 x 331 frames, or the
-    native 384 x 512 for 'big'.  X_train / Y_train are the callback's device tensors (fit() reads them in place)."""
+    native 384 x 512 for 'big'.  X_train / Y_train are the callback's device tensors (fit() reads them in place).
+    warp (--warp): the callback also keeps each epoch's full-size frames and label rows on the device in its .warper, the
+    warp_source of AugmentOnTheFly."""
     from spnet_amd import fake_espi
     n = utils.nearest_multiple(int(n_train), global_batch)
     if n < 1:
@@ -49,7 +51,7 @@ def fake_stream_data(n_train, n_val, global_batch, pred_grid, seed):
     Xv, labels = val.frames(VAL_STREAM_TOP - m, m)
     Yv, _ = fake_espi.targets_from_labels(labels, pred_grid)
     fresh = callbacks.FreshFakeESPI(None, None, fake_espi.FakeStream(n, seed=seed, device=device, size=size,
-                                                                     pred_grid=pred_grid))
+                                                                     pred_grid=pred_grid), warper=bool(warp))
     return fresh.X, fresh.Y, Xv.cpu().numpy(), Yv, fresh, pred_shape
 
 
@@ -64,10 +66,8 @@ def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch
     fresh = None
     if fake_stream:
         X_train, Y_train, X_val, Y_val, fresh, pred_shape = fake_stream_data(fake_stream, fake_val, batch_size * world,
-                                                                             pred_grid, random_seed)
+                                                                             pred_grid, random_seed, warp and not noaugment)
         train_file_list, val_file_list = None, None          # no files: MyProgressCallback draws no overlays
-        if warp:
-            raise ValueError("--warp needs the PNG + CSV files of Train/; --fake_stream has none")
     else:
         X_train, Y_train, train_file_list, pred_shape = utils.build_dataset(
             path=datapath + "/Train/", load_frac=fraction, set_means_ranges=True, batch_size=batch_size, pred_grid=pred_grid)
@@ -92,10 +92,13 @@ def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch
         callback_list.append(fresh)
     if not noaugment:
         print("Adding callback for augment on the fly")
+        if warp and fresh is not None:      # streamed frames: warped from the device tensors the stream keeps
+            warp_args = dict(warp_source=fresh.warper, warp_targets="device")
+        else:
+            warp_args = dict(warp=warp, warp_files=list(train_file_list[:X_train.shape[0]]) if warp else None)
         callback_list.append(callbacks.AugmentOnTheFly(X_train, Y_train, aug_every=1, seed=random_seed,
                                                        real_blur=augment_blur, bandpass_real=bp_real,
-                                                       bpmix_prob=bpmix_prob, warp=warp, pred_grid=pred_grid,
-                                                       warp_files=list(train_file_list[:X_train.shape[0]]) if warp else None))
+                                                       bpmix_prob=bpmix_prob, pred_grid=pred_grid, **warp_args))
 
     fit_args = dict(batch_size=batch_size, shuffle=True, verbose=1, validation_data=(X_val, Y_val), callbacks=callback_list)
     if frozen_epochs > 0 and freeze_fac > 0.0:        # warm-up phase with the first layers frozen
@@ -144,7 +147,8 @@ if __name__ == '__main__':
                    help="warp every training frame afresh each epoch (random flip, rotation of +-20 degrees, shift of up to "
                         "+-40 px: what augment_preproc.py writes offline) and recompute its targets.  NEEDS the PNG + CSV "
                         "files of Train/ on disk: the frames are warped at their full size and the targets come from the "
-                        "CSV rows.  Ignored with --noaugment")
+                        "CSV rows -- or --fake_stream, whose full-size frames and label rows stay on the GPU.  Ignored "
+                        "with --noaugment")
     p.add_argument('--fake_stream', type=int, default=None, metavar='N',
                    help="train on N fresh fake-ESPI frames per epoch, generated on the GPU (rounded down to a multiple of "
                         "the global batch); no Train/ or Val/ directory is read")

@@ -31,10 +31,19 @@ extern "C" {
  * split_k: 0 = choose automatically, >1 = that many K slices summed deterministically through
  * `workspace` (>= split_k*M*N floats).  tile (BM x BN): 0 auto (cost model over ids 1-8), 1 128x128, 2 128x64, 3 64x64,
  * 4 32x128, 5 96x96, 6 96x64, 7 64x128, 8 128x96, 9 32x64, 10 32x32 (9 and 10: few-row problems, chosen only through
- * spnet_amd/gemm_tiles.json, where tools/autotune_gemm.py measured them faster inside the step). */
+ * spnet_amd/gemm_tiles.json, where tools/autotune_gemm.py measured them faster inside the step); any other id = 0.  The table
+ * itself: GEMM_TILES in csrc/gemm_plan.h. */
 int spnet_gemm_f32(const float* A, int a_major, int lda, const float* B, int b_major, int ldb, float* C,
                    int ldc, int M, int N, int K, int split_k, float* workspace, long ws_floats,
                    const float* bias, int tile, void* stream);
+/* What spnet_gemm_f32 and its siblings (_accumulate, _batched(_splitk), _bnblend / _bnrelu = xf 1 / 2, _colstats,
+ * spnet_conv_gemm_f32) would run for a problem of this shape with dense, aligned operands: no launch, no device.  The have_* /
+ * accumulate / conv flags say which optional operands the call carries.  plan (HOST int[10]) = {form (0 K/OUT, 1 K/K,
+ * 2 OUT/OUT), tile id, BM, BN, K slices, floats of K per slice, slices per problem in the kernel (batched; else 1), pipelined
+ * main loop, slabs go to the workspace, colstats rows}; the tile ids are the rows of GEMM_TILES in csrc/gemm_plan.h.
+ * Returns non-zero, and leaves plan untouched, where the launch would be refused. */
+int spnet_gemm_plan(int a_major, int b_major, int M, int N, int K, int split_k, int have_workspace, long ws_floats,
+                    int have_colstats, int have_batch, int nbatch, int xf, int accumulate, int conv, int tile, int* plan);
 /* ---- fp32 GEMM on the bf16 matrix cores by operand splitting (csrc/gemm_bf16x3.hip): the forward, data-gradient and
  * weight-gradient GEMMs of the pointwise convolutions (keras SeparableConv2D pointwise step / 1x1 Conv2D;
  * spnet/models.py:346-359).  Every fp32 operand is the exact sum of three bf16 pieces; six bf16 MFMAs with fp32 accumulation
@@ -91,7 +100,8 @@ int spnet_gemm_bf16x3_pp_dwbwd(const void* dy_planes, const void* w_planes, int 
                                float* bn_partial, const float* bn_x, void* stream);
 int spnet_gemm_bf16x3_wgrad_batched(const void* jobs, int nbatch, int cin, int cout, int M, int ksplit, void* stream);
 /* C += A B, formed in the epilogue (no K split): a data gradient added onto what another consumer of the same tensor
- * has already left in C (the branch convolutions of an inception block; call site spnet/models.py:357-359). */
+ * has already left in C (the branch convolutions of an inception block; call site spnet/models.py:357-359).  tile: 0 or an
+ * id of spnet_gemm_f32's list; any other id is refused (hipErrorInvalidValue, C untouched), not read as 0. */
 int spnet_gemm_f32_accumulate(const float* A, int a_major, int lda, const float* B, int b_major, int ldb, float* C,
                               int ldc, int M, int N, int K, int tile, void* stream);
 

@@ -958,14 +958,13 @@ extern "C" int spnet_dwconv3x3_strided(int op, const float* a, const float* b, f
 
 // ---------------------------------------------------------------- tiled entry points
 struct DwGeom { int cfg, th, tw, cc4, tiles_h, tiles_w, cchunks; long nblk; size_t lds_fwd, lds_bwd; };
-// cfg 1: 6x8 pixel tile x 16 channel quads (exit flow, 6x8 planes); cfg 0: 12x16 tile x 8 quads;
-// cfg 2 (forward only): 24x16 tile x 8 quads for the large planes (halo read overhead 1.22 instead of 1.31)
-static DwGeom dw_geom(int B, int H, int W, int C, bool fwd) {
+// cfg 1: 6x8 pixel tile x 16 channel quads (exit flow, 6x8 planes); cfg 0: 12x16 tile x 8 quads
+static DwGeom dw_geom(int B, int H, int W, int C) {
   DwGeom g;
   g.cfg = (H <= 6 && W <= 8) ? 1 : 0;   // (a 24x16 forward tile was tried: 60 KB of LDS halves residency and loses)
   // (measured and dropped, round 2: 6x16 half-height tiles for the middle flow's 12x16 planes -- twice the workgroups,
   // forward 11.1 -> 10.8 us but backward 16.5 -> 18.4 us)
-  g.th = g.cfg == 1 ? 6 : (g.cfg == 2 ? 24 : 12);
+  g.th = g.cfg == 1 ? 6 : 12;
   g.tw = g.cfg == 1 ? 8 : 16;
   g.cc4 = g.cfg == 1 ? 16 : 8;
   g.tiles_h = (H + g.th - 1) / g.th;
@@ -987,13 +986,12 @@ static int dw_tiled_fwd(const float* x, const float* w, float* y, int B, int H, 
   if (C & 3) return (int)hipErrorInvalidValue;
   if (planes && !dw_planes_ok(planes, B, H, W, C)) return (int)hipErrorInvalidValue;
   const long plane_stride = x3t_plane_elems((long)B * H * W, C);
-  const DwGeom g = dw_geom(B, H, W, C, true);
+  const DwGeom g = dw_geom(B, H, W, C);
 #define DW_FWD(CC4, TW, TH)                                                                                     \
   hipLaunchKernelGGL((dw3x3_tile_fwd_kernel<CC4, TW, TH>), dim3((unsigned)g.nblk), dim3(256), g.lds_fwd,        \
                      (hipStream_t)stream, x, w, y, H, W, C, relu_in, g.tiles_h, g.tiles_w, g.cchunks, in_scale, \
                      in_shift, fin, planes, plane_stride)
   if (g.cfg == 1) DW_FWD(16, 8, 6);
-  else if (g.cfg == 2) DW_FWD(8, 16, 24);
   else DW_FWD(8, 16, 12);
 #undef DW_FWD
   SPNET_RETURN_LAUNCH_STATUS();
@@ -1159,13 +1157,13 @@ extern "C" int spnet_dwconv3x3_stream_bwd(const float* dy, const float* x_fwd, c
 }
 
 extern "C" long spnet_dwconv3x3_tiled_rows(int B, int H, int W, int C) {
-  const DwGeom g = dw_geom(B, H, W, C, false);
+  const DwGeom g = dw_geom(B, H, W, C);
   return (long)B * g.tiles_h * g.tiles_w;   // rows of the [rows][2][C] BatchNorm partial buffer
 }
 
 // floats of workspace needed by spnet_dwconv3x3_tiled_bwd
 extern "C" long spnet_dwconv3x3_tiled_bwd_ws(int B, int H, int W, int C) {
-  const DwGeom g = dw_geom(B, H, W, C, false);
+  const DwGeom g = dw_geom(B, H, W, C);
   return ((long)B * g.tiles_h * g.tiles_w + 32) * 9 * C;      // partial rows + 32 second-level slices
 }
 
@@ -1184,7 +1182,7 @@ extern "C" int spnet_dwconv3x3_tiled_bwd(const float* dy, const float* x_fwd, co
   if (bn_partial && (!bn_mean || !bn_invstd)) return (int)hipErrorInvalidValue;
   if (bn_x && !bn_partial) return (int)hipErrorInvalidValue;
   if (C & 3) return (int)hipErrorInvalidValue;
-  const DwGeom g = dw_geom(B, H, W, C, false);
+  const DwGeom g = dw_geom(B, H, W, C);
   if (g.cfg == 1)
     hipLaunchKernelGGL((dw3x3_tile_bwd_kernel<16, 8, 6>), dim3((unsigned)g.nblk), dim3(256), g.lds_bwd,
                        (hipStream_t)stream, dy, x_fwd, w, dx, workspace, add, H, W, C, relu_in, g.tiles_h,

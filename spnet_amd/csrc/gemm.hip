@@ -17,20 +17,8 @@
 // Split-K: grid.z slices write fp32 slabs to a workspace, a second kernel sums them in slice order
 // (deterministic; no float atomics).
 #include "gemm_tile.h"
-
-#ifndef SP_BK
-#define SP_BK 32
-#endif
-#ifndef SP_PIPE
-#define SP_PIPE 1        // 0: the compiler-scheduled main loop everywhere (A/B measurements)
-#endif
-#ifndef SP_SPLIT_BELOW_TILES
-#define SP_SPLIT_BELOW_TILES 256
-#define SP_SPLIT_MIN_K 2048
-#endif
-#ifndef SP_PIPE_MIN_TILES
-#define SP_PIPE_MIN_TILES 32
-#endif
+#include "gemm_plan.h"
+#include <utility>
 
 // 4 waves (WM x WN), each wave owns a (BM/WM) x (BN/WN) block built from 16x16 MFMA tiles
 // (v_mfma_f32_16x16x4_f32: D col = l&15, row = 4*(l>>4)+reg).  Tile t+1 travels global -> registers while
@@ -45,7 +33,6 @@
 // flow's 768-workgroup launches are exactly one resident wave of 3 per CU)
 // AX = 2: the A operand is relu(a[k]*A_ + c[k]) of ONE tensor (TileStage::xform_relu; X2 unused, coefficient row b
 // unused): BatchNorm + ReLU applied while the tile is staged, the pre-activation 1x1 convolution of keras DenseNet.
-
 
 // N x { one MFMA, PER instructions of class MASK } for the instruction scheduler
 template <int N, int MASK, int PER>
@@ -470,127 +457,8 @@ static void launch_reduce_slabs(const float* ws, int nslab, int M, int N, float*
 // out[M][ldc] = sum of nslab slabs of M*N floats (slice order); shared with conv_gemm.hip
 extern "C" int spnet_reduce_slabs(const float* ws, int nslab, int M, int N, float* out, int ldc, void* stream) {
   if ((N & 3) || (ldc & 3) || nslab < 1) return (int)hipErrorInvalidValue;
-  const long total4 = (long)M * N / 4;
   launch_reduce_slabs(ws, nslab, M, N, out, ldc, nullptr, (hipStream_t)stream);
   SPNET_RETURN_LAUNCH_STATUS();
-}
-
-
-// xf: 0 = plain operands, 1 = blended A (forward form only)
-template <int BM, int BN, int WM, int WN>
-static int launch_tile(const float* A, int amaj, int lda, const float* B, int bmaj, int ldb, float* C,
-                       int ldc, int M, int N, int K, int nsplit, int k_chunk, long slab_stride,
-                       const float* bias, float* colstats, const long long* batch, hipStream_t st,
-                       int xf = 0, const float* X2 = nullptr, const float* coef = nullptr, int cld = 0,
-                       float* dy_out = nullptr, int kslices = 1, int accumulate = 0, const ConvGeom* cgp = nullptr) {
-  const ConvGeom cg = cgp ? *cgp : ConvGeom{0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const int tm = spnet_cdiv(M, BM), tn = spnet_cdiv(N, BN);
-  dim3 grid(tm * tn * nsplit), block(256);
-  // the pipelined main loop from 32 K tiles per workgroup (see the kernel's header comment)
-  constexpr bool CAN_PIPE = SP_PIPE && (BM / WM / 16) * (BN / WN / 16) < 16;
-  const bool pipe = CAN_PIPE && !xf && spnet_cdiv(K < k_chunk ? K : k_chunk, SP_BK) >= SP_PIPE_MIN_TILES;
-#define SP_ARGS A, lda, B, ldb, C, ldc, M, N, K, k_chunk, slab_stride, tm, tn, nsplit, bias, colstats, batch, X2, coef, cld, dy_out, kslices, accumulate, cg
-#define SP_LAUNCH(BKV, AM, BMJ, AXV, PV) \
-  hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, BKV, WM, WN, AM, BMJ, AXV, PV>), grid, block, 0, st, SP_ARGS)
-#define SP_LAUNCH_P(AM, BMJ)                                          \
-  do {                                                                \
-    if constexpr (CAN_PIPE) {                                         \
-      if (pipe) SP_LAUNCH(SP_BK, AM, BMJ, 0, 1);                      \
-      else SP_LAUNCH(SP_BK, AM, BMJ, 0, 0);                           \
-    } else {                                                          \
-      SP_LAUNCH(SP_BK, AM, BMJ, 0, 0);                                \
-    }                                                                 \
-  } while (0)
-  if (cg.C) {          // gathered A (implicit-GEMM convolution): forward operand form only
-    if (xf || amaj != SP_K_MAJOR || bmaj != SP_OUT_MAJOR) return (int)hipErrorInvalidValue;
-    if constexpr (CAN_PIPE) {
-      if (pipe) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, SP_BK, WM, WN, SP_K_MAJOR, SP_OUT_MAJOR, 0, 1, 1>), grid, block, 0, st, SP_ARGS);
-      else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, SP_BK, WM, WN, SP_K_MAJOR, SP_OUT_MAJOR, 0, 0, 1>), grid, block, 0, st, SP_ARGS);
-    } else {
-      hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, SP_BK, WM, WN, SP_K_MAJOR, SP_OUT_MAJOR, 0, 0, 1>), grid, block, 0, st, SP_ARGS);
-    }
-  } else if (xf == 1) {
-    if (amaj == SP_K_MAJOR && bmaj == SP_OUT_MAJOR) SP_LAUNCH(SP_BK, SP_K_MAJOR, SP_OUT_MAJOR, 1, 0);
-    else return (int)hipErrorInvalidValue;
-  } else if (xf == 2) {
-    if (amaj == SP_K_MAJOR && bmaj == SP_OUT_MAJOR) SP_LAUNCH(SP_BK, SP_K_MAJOR, SP_OUT_MAJOR, 2, 0);
-    else return (int)hipErrorInvalidValue;
-  } else if (amaj == SP_K_MAJOR && bmaj == SP_OUT_MAJOR) SP_LAUNCH_P(SP_K_MAJOR, SP_OUT_MAJOR);
-  else if (amaj == SP_K_MAJOR && bmaj == SP_K_MAJOR) SP_LAUNCH_P(SP_K_MAJOR, SP_K_MAJOR);
-  else if (amaj == SP_OUT_MAJOR && bmaj == SP_OUT_MAJOR) SP_LAUNCH_P(SP_OUT_MAJOR, SP_OUT_MAJOR);
-  else return (int)hipErrorInvalidValue;
-#undef SP_LAUNCH_P
-#undef SP_LAUNCH
-#undef SP_ARGS
-  return 0;
-}
-
-// Tile ids: 0 = auto, 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 32x128, 5 = 96x96, 6 = 96x64, 7 = 64x128, 8 = 128x96,
-// 9 = 32x64 (few-row problems: M = 384 ... 4,096 rows of Inception-ResNet-v2 at batch 16, where 64-row tiles leave CUs empty),
-// 10 = 32x32 (the same problems with few columns as well: twice the workgroups, half the MFMA chain per K tile).
-// 9 and 10 are never chosen by the cost model: spnet_amd/gemm_tiles.json names the shapes where they win in the step.
-#define SP_NTILES 10
-static void tile_dims(int tile, int* bm, int* bn) {
-  switch (tile) {
-    case 1: *bm = 128; *bn = 128; break;
-    case 2: *bm = 128; *bn = 64; break;
-    case 3: *bm = 64; *bn = 64; break;
-    case 5: *bm = 96; *bn = 96; break;
-    case 6: *bm = 96; *bn = 64; break;
-    case 7: *bm = 64; *bn = 128; break;
-    case 8: *bm = 128; *bn = 96; break;
-    case 9: *bm = 32; *bn = 64; break;
-    case 10: *bm = 32; *bn = 32; break;
-    default: *bm = 32; *bn = 128; break;
-  }
-}
-
-// Automatic K split of one tile shape: enough workgroups for ~2 per CU, slices at least 4 K-tiles deep -- but only
-// while the unsplit launch leaves CUs empty: from one workgroup per CU on, the slabs and their reduce launch cost more
-// than the second workgroup buys (exit-flow shapes, tile / split sweep: 1536x1024x728 32.8 -> 26.7 us, 1536x1536x1024
-// 51.5 -> 43.9, 1536x1536x2048 in the data-gradient form 87.8 -> 74.4), and not below 64 K tiles, where even a launch
-// that fills three quarters of the CUs beats its split form (1536x728x1024, data-gradient form: 35.9 -> 29.3 us).
-// (weight-gradient form: few output tiles and a long pixel axis by nature; the original rule -- split below two
-// workgroups per CU -- measures better there: 1024x1536x1536 53.2 vs 56.7 us)
-static int auto_split(long tiles, int M, int N, int K, bool have_ws, long ws_floats, int form) {
-  if (!have_ws) return 1;
-  if (form == 2 ? tiles >= 512 : (tiles >= SP_SPLIT_BELOW_TILES || K < SP_SPLIT_MIN_K)) return 1;
-  long want = (512 + tiles - 1) / tiles;
-  long maxk = K / (SP_BK * 4);
-  if (maxk < 1) maxk = 1;
-  if (want > maxk) want = maxk;
-  const long fit = ws_floats / ((long)M * N);
-  if (want > fit) want = fit;
-  return want > 1 ? (int)want : 1;
-}
-
-// Tile choice: cost ~ (workgroups on the busiest CU) x (work per workgroup + a fixed prologue/epilogue worth
-// K0 reduction steps) / (measured efficiency of that tile's main loop for this operand form), plus the
-// slab traffic of a K split.  The efficiencies were fitted on MI355X to the network's GEMM shapes
-// (tools/gemm_sweep.py; every shape of the 512x384 batch-32 step gets its measured-fastest tile) but the
-// model itself is shape-agnostic.  Forms: 0 = K/OUT (forward), 1 = K/K (dgrad), 2 = OUT/OUT (wgrad).
-static int pick_tile(int form, int M, int N, int K, int split_k, bool have_ws, long ws_floats, int nbatch = 1) {
-  if (M <= 32) return 4;
-  const int cand[7] = {1, 2, 3, 5, 6, 7, 8};
-  static const double eff[3][7] = {{1.00, 0.95, 0.93, 0.93, 0.97, 1.00, 0.93},
-                                   {0.95, 0.93, 0.97, 0.97, 1.00, 0.90, 0.99},
-                                   {0.80, 0.85, 0.95, 1.00, 0.90, 0.85, 0.80}};
-  int best = 1;
-  double best_cost = 1e300;
-  // (tile 9, 32x64, is never chosen here: it is selected per shape from measurements -- spnet_amd/gemm_tiles.json)
-  for (int c = 0; c < 7; ++c) {
-    int bm, bn;
-    tile_dims(cand[c], &bm, &bn);
-    const long tiles = (long)spnet_cdiv(M, bm) * spnet_cdiv(N, bn);
-    int ns = split_k > 0 ? split_k : auto_split(tiles, M, N, K, have_ws, ws_floats, form);
-    const int kc = spnet_cdiv(spnet_cdiv(K, ns), SP_BK) * SP_BK;
-    ns = spnet_cdiv(K, kc);
-    const double rounds = (double)((tiles * ns * nbatch + 255) / 256) / nbatch;
-    double cost = rounds * bm * bn * ((double)kc + 128.0) / eff[form][c];
-    if (ns > 1) cost += 2.0 * ns * (double)M * N / 256.0;
-    if (cost < best_cost) { best_cost = cost; best = cand[c]; }
-  }
-  return best;
 }
 
 // out_j[i] = sum over the kslices slabs of problem j, slice order (deterministic); out_j = C0 + offsets[3j + 2].
@@ -609,192 +477,147 @@ __global__ __launch_bounds__(256) void reduce_slabs_batched_kernel(const float* 
   *reinterpret_cast<float4*>(C0 + offsets[3 * j + 2] + i) = s;
 }
 
-static int gemm_impl(const float* A, int a_major, int lda, const float* B, int b_major, int ldb, float* C,
-                     int ldc, int M, int N, int K, int split_k, float* workspace, long ws_floats,
-                     const float* bias, int tile, float* colstats, int* stat_rows, void* stream,
-                     const long long* batch = nullptr, int nbatch = 0, int xf = 0, const float* X2 = nullptr,
-                     const float* coef = nullptr, int cld = 0, float* dy_out = nullptr, int accumulate = 0,
-                     const ConvGeom* cg = nullptr) {
+static_assert((int)GEMM_K_MAJOR == (int)SP_K_MAJOR && (int)GEMM_OUT_MAJOR == (int)SP_OUT_MAJOR && GEMM_REFUSED == (int)hipErrorInvalidValue,
+              "gemm_plan.h restates the majors of gemm_tile.h and hipErrorInvalidValue");
+
+// Launch: executes the GemmPlan of a GemmProblem (gemm_plan.h), where every refusal and every choice has been made.
+// launch_form: one operand form of one tile; PIPE from the plan, where the tile and the form have a pipelined kernel.
+template <int BM, int BN, int WM, int WN, int AMAJ, int BMAJ, int AX, int AG>
+static void launch_form(const GemmProblem& p, const GemmPlan& pl, hipStream_t st) {
+  const ConvGeom cg = p.cg ? *p.cg : ConvGeom{0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int tm = spnet_cdiv(p.M, BM), tn = spnet_cdiv(p.N, BN);
+  const int nz = p.batch ? p.nbatch * pl.kslices : pl.nsplit;      // the kernel's slice index selects (problem, K slice)
+  const bool ws = pl.to_workspace;                                 // slabs: dense M x N, the reduce launch adds the bias
+  auto launch = [&](auto pipe) {
+    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, SP_BK, WM, WN, AMAJ, BMAJ, AX, decltype(pipe)::value, AG>), dim3(tm * tn * nz),
+                       dim3(256), 0, st, p.A, p.lda, p.B, p.ldb, ws ? p.workspace : p.C, ws ? p.N : p.ldc, p.M, p.N, p.K,
+                       pl.k_chunk, pl.slab, tm, tn, nz, ws ? nullptr : p.bias, p.colstats, p.batch, p.X2, p.coef, p.cld,
+                       p.dy_out, pl.kslices, p.accumulate, cg);
+  };
+  if constexpr (gemm_can_pipe(BM, BN, WM, WN) && !AX) {
+    if (pl.pipe) return launch(std::integral_constant<int, 1>());
+  }
+  launch(std::integral_constant<int, 0>());
+}
+
+// gathered (AG) and transformed (AX) A operands exist in the forward operand form only
+template <int BM, int BN, int WM, int WN>
+static void launch_tile(const GemmProblem& p, const GemmPlan& pl, hipStream_t st) {
+  if (p.cg) launch_form<BM, BN, WM, WN, SP_K_MAJOR, SP_OUT_MAJOR, 0, 1>(p, pl, st);
+  else if (p.xf == 1) launch_form<BM, BN, WM, WN, SP_K_MAJOR, SP_OUT_MAJOR, 1, 0>(p, pl, st);
+  else if (p.xf == 2) launch_form<BM, BN, WM, WN, SP_K_MAJOR, SP_OUT_MAJOR, 2, 0>(p, pl, st);
+  else if (pl.form == 0) launch_form<BM, BN, WM, WN, SP_K_MAJOR, SP_OUT_MAJOR, 0, 0>(p, pl, st);
+  else if (pl.form == 1) launch_form<BM, BN, WM, WN, SP_K_MAJOR, SP_K_MAJOR, 0, 0>(p, pl, st);
+  else launch_form<BM, BN, WM, WN, SP_OUT_MAJOR, SP_OUT_MAJOR, 0, 0>(p, pl, st);
+}
+
+template <size_t... I>     // launch_tile<BM, BN, WM, WN> of the plan's row of GEMM_TILES
+static void launch_planned_tile(const GemmProblem& p, const GemmPlan& pl, hipStream_t st, std::index_sequence<I...>) {
+  ((pl.tile == GEMM_TILES[I].id
+        ? launch_tile<GEMM_TILES[I].bm, GEMM_TILES[I].bn, GEMM_TILES[I].wm, GEMM_TILES[I].wn>(p, pl, st) : void()), ...);
+}
+
+static int gemm_impl(const GemmProblem& p, void* stream) {
+  const GemmPlan pl = gemm_plan(p);
+  if (pl.rc) return pl.rc;
   hipStream_t st = (hipStream_t)stream;
-  if (cg && (batch || xf || accumulate || a_major != SP_K_MAJOR || b_major != SP_OUT_MAJOR || split_k != 1))
-    return (int)hipErrorInvalidValue;     // gathered A: one whole forward-form problem
-  if (accumulate) {                  // C += A B in the epilogue: whole dot products only (no slabs), one problem
-    if (batch || colstats || xf) return (int)hipErrorInvalidValue;
-    split_k = 1;
-  }
-  if (batch) {                       // nbatch whole problems side by side; a K split only when the caller asks for one
-    if (nbatch < 1 || bias || colstats) return (int)hipErrorInvalidValue;
-    if (split_k <= 1 || !workspace) {
-      split_k = 1;
-      workspace = nullptr;
-      ws_floats = 0;
-    } else if (ldc != N) {
-      return (int)hipErrorInvalidValue;          // the slab reduce writes dense M x N outputs
-    }
-  }
-  if (colstats) split_k = 1;   // statistics are taken from complete dot products
-  if (M <= 0 || N <= 0 || K <= 0) return (int)hipErrorInvalidValue;
-  if ((lda & 3) || (ldb & 3) || (N & 3) || (ldc & 3)) return (int)hipErrorInvalidValue;
-  if ((a_major == SP_K_MAJOR || b_major == SP_K_MAJOR) && (K & 3)) return (int)hipErrorInvalidValue;
-  if (a_major == SP_OUT_MAJOR && (M & 3)) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return (int)hipErrorInvalidValue;
-  if (xf) {   // blended A operand: second tensor + [a|b|c] coefficients, zero-padded to whole K tiles; no K split
-    if ((xf != 1 && xf != 2) || batch || (xf == 1 && !X2) || !coef ||
-        (((uintptr_t)X2 | (uintptr_t)coef | (uintptr_t)dy_out) & 15) || (cld & 3) || (xf == 2 && dy_out))
-      return (int)hipErrorInvalidValue;
-    if (cld < spnet_cdiv(K, SP_BK) * SP_BK) return (int)hipErrorInvalidValue;
-    split_k = 1;
-  }
-  const bool auto_tile = (tile <= 0 || tile > SP_NTILES);
-  const int form = (a_major == SP_OUT_MAJOR) ? 2 : (b_major == SP_K_MAJOR ? 1 : 0);
-  if (tile <= 0 || tile > SP_NTILES)
-    tile = pick_tile(form, M, N, K, split_k, workspace != nullptr, ws_floats, batch ? nbatch : 1);
-  // the two-tensor blended 128x128 kernel does not fit the register file (it spills); the one-tensor BN+ReLU form (xf 2:
-  // 248 VGPRs, no scratch) keeps it -- a 128x96 tile would waste a third of every N = 128 problem of DenseNet
-  if (xf == 1 && auto_tile && tile == 1) tile = 8;
-  int bm, bn;
-  tile_dims(tile, &bm, &bn);
-  const long tiles = (long)spnet_cdiv(M, bm) * spnet_cdiv(N, bn);
-  const int BK = SP_BK;
-  int nsplit = split_k;
-  if (nsplit <= 0) nsplit = auto_split(tiles, M, N, K, workspace != nullptr, ws_floats, form);
-  const int bkt = BK;
-  int k_chunk = ((K + nsplit - 1) / nsplit + bkt - 1) / bkt * bkt;
-  nsplit = (K + k_chunk - 1) / k_chunk;
-  float* out = C;
-  int out_ld = ldc;
-  long slab = 0;
-  const float* kbias = bias;
-  if (nsplit > 1) {
-    if (!workspace || (long)nsplit * (batch ? nbatch : 1) * M * N > ws_floats) return (int)hipErrorInvalidValue;
-    if (((uintptr_t)workspace) & 15) return (int)hipErrorInvalidValue;
-    out = workspace;
-    out_ld = N;
-    slab = (long)M * N;
-    kbias = nullptr;
-  }
-  if (stat_rows) *stat_rows = spnet_cdiv(M, bm);
-  const int kslices = batch ? nsplit : 1;
-  float* C0 = C;
-  if (batch) nsplit = nbatch * kslices;      // the kernel's slice index selects (problem, K slice)
-  int rc;
-  switch (tile) {
-    case 1: rc = launch_tile<128, 128, 2, 2>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-    case 2: rc = launch_tile<128, 64, 2, 2>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-    case 3: rc = launch_tile<64, 64, 2, 2>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-    case 5: rc = launch_tile<96, 96, 2, 2>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-    case 6: rc = launch_tile<96, 64, 2, 2>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-    case 7: rc = launch_tile<64, 128, 2, 2>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-    case 8: rc = launch_tile<128, 96, 2, 2>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-    case 9: rc = launch_tile<32, 64, 2, 2>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-    case 10: rc = launch_tile<32, 32, 2, 2>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-    default: rc = launch_tile<32, 128, 1, 4>(A, a_major, lda, B, b_major, ldb, out, out_ld, M, N, K, nsplit, k_chunk, slab, kbias, colstats, batch, st, xf, X2, coef, cld, dy_out, kslices, accumulate, cg); break;
-  }
-  if (rc) return rc;
-  if (nsplit > 1 && !batch) {
-    const long total4 = (long)M * N / 4;
-    launch_reduce_slabs(workspace, nsplit, M, N, C, ldc, bias, st);
-  }
-  if (batch && kslices > 1) {
-    const long mn = (long)M * N;
-    hipLaunchKernelGGL(reduce_slabs_batched_kernel, dim3((unsigned)((mn / 4 + 255) / 256), nbatch), dim3(256), 0, st,
-                       workspace, kslices, mn, C0, batch);
-  }
+  if (p.stat_rows) *p.stat_rows = pl.stat_rows;
+  launch_planned_tile(p, pl, st, std::make_index_sequence<SP_NTILES>());
+  if (pl.to_workspace && !p.batch) launch_reduce_slabs(p.workspace, pl.nsplit, p.M, p.N, p.C, p.ldc, p.bias, st);
+  if (pl.to_workspace && p.batch)
+    hipLaunchKernelGGL(reduce_slabs_batched_kernel, dim3((unsigned)((pl.slab / 4 + 255) / 256), p.nbatch), dim3(256), 0, st,
+                       p.workspace, pl.kslices, pl.slab, p.C, p.batch);
   SPNET_RETURN_LAUNCH_STATUS();
 }
 
-extern "C" int spnet_gemm_f32(const float* A, int a_major, int lda, const float* B, int b_major,
-                              int ldb, float* C, int ldc, int M, int N, int K, int split_k,
-                              float* workspace, long ws_floats, const float* bias, int tile,
-                              void* stream) {
-  return gemm_impl(A, a_major, lda, B, b_major, ldb, C, ldc, M, N, K, split_k, workspace, ws_floats, bias,
-                   tile, nullptr, nullptr, stream);
+// Entry points (documented in include/spnet_hip.h).  gemm_problem: the operands each of them has; the rest it sets by name.
+static GemmProblem gemm_problem(const float* A, int a_major, int lda, const float* B, int b_major, int ldb, float* C, int ldc, int M, int N, int K, int tile) {
+  GemmProblem p;
+  p.A = A; p.a_major = a_major; p.lda = lda; p.B = B; p.b_major = b_major; p.ldb = ldb; p.C = C; p.ldc = ldc;
+  p.M = M; p.N = N; p.K = K; p.tile = tile;
+  return p;
 }
 
-// C += A B (no K split: the sum is formed in the epilogue, read-modify-write of C by the workgroup that owns the tile):
-// a data gradient added straight onto the gradient another consumer of the same tensor has already left in C, instead
-// of a GEMM into a scratch tensor + an accumulation pass (the branch convolutions of an inception block all read the
-// block input).
+extern "C" int spnet_gemm_f32(const float* A, int a_major, int lda, const float* B, int b_major, int ldb, float* C, int ldc, int M,
+                              int N, int K, int split_k, float* workspace, long ws_floats, const float* bias, int tile, void* stream) {
+  GemmProblem p = gemm_problem(A, a_major, lda, B, b_major, ldb, C, ldc, M, N, K, tile);
+  p.split_k = split_k; p.workspace = workspace; p.ws_floats = ws_floats; p.bias = bias;
+  return gemm_impl(p, stream);
+}
+
+// plan[10] = {form, tile, bm, bn, nsplit, k_chunk, kslices, pipe, to_workspace, stat_rows} for dense, aligned operands
+extern "C" int spnet_gemm_plan(int a_major, int b_major, int M, int N, int K, int split_k, int have_workspace, long ws_floats,
+                               int have_colstats, int have_batch, int nbatch, int xf, int accumulate, int conv, int tile, int* plan) {
+  float* const mem = reinterpret_cast<float*>(64);         // tested for NULL and alignment, never dereferenced
+  GemmProblem p = gemm_problem(mem, a_major, a_major == SP_K_MAJOR ? K : M, mem, b_major, b_major == SP_K_MAJOR ? K : N, mem, N, M, N, K, tile);
+  p.split_k = split_k; p.workspace = have_workspace ? mem : nullptr; p.ws_floats = ws_floats;
+  p.batch = have_batch ? reinterpret_cast<const long long*>(mem) : nullptr; p.nbatch = nbatch;
+  p.xf = xf; p.X2 = xf == 1 ? mem : nullptr; p.coef = xf ? mem : nullptr; p.cld = spnet_cdiv(K, SP_BK) * SP_BK;
+  p.accumulate = accumulate; p.colstats = have_colstats ? mem : nullptr;
+  p.cg = conv ? reinterpret_cast<const ConvGeom*>(mem) : nullptr;
+  const GemmPlan pl = gemm_plan(p);
+  const int v[10] = {pl.form, pl.tile, pl.bm, pl.bn, pl.nsplit, pl.k_chunk, pl.kslices, pl.pipe, pl.to_workspace, pl.stat_rows};
+  for (int i = 0; i < 10 && !pl.rc; ++i) plan[i] = v[i];
+  return pl.rc;
+}
+
+// C += A B (no K split: the sum is formed in the epilogue, read-modify-write of C by the workgroup that owns the tile)
+// instead of a GEMM into a scratch tensor + an accumulation pass
 extern "C" int spnet_gemm_f32_accumulate(const float* A, int a_major, int lda, const float* B, int b_major, int ldb,
                                          float* C, int ldc, int M, int N, int K, int tile, void* stream) {
-  return gemm_impl(A, a_major, lda, B, b_major, ldb, C, ldc, M, N, K, 1, nullptr, 0, nullptr, tile, nullptr, nullptr,
-                   stream, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 1);
+  GemmProblem p = gemm_problem(A, a_major, lda, B, b_major, ldb, C, ldc, M, N, K, tile);
+  p.accumulate = 1;
+  return gemm_impl(p, stream);
 }
 
-// nbatch independent problems of one shape in ONE launch (no K split).  A0/B0/C0: operands of problem 0;
-// offsets (device memory): {A_b - A0, B_b - B0, C_b - C0} in floats for b = 0..nbatch-1 (multiples of 4).
-// Used for the weight gradients of the eight middle-flow blocks, which individually are too small to fill
-// the chip without a K split.
-extern "C" int spnet_gemm_f32_batched(const float* A0, const float* B0, float* C0, const long long* offsets,
-                                      int nbatch, int a_major, int lda, int b_major, int ldb, int ldc, int M,
-                                      int N, int K, int tile, void* stream) {
+// nbatch problems of one shape in ONE launch: the weight gradients of the eight middle-flow blocks, each too small to fill the chip
+extern "C" int spnet_gemm_f32_batched(const float* A0, const float* B0, float* C0, const long long* offsets, int nbatch, int a_major,
+                                      int lda, int b_major, int ldb, int ldc, int M, int N, int K, int tile, void* stream) {
   if (!offsets || !A0 || !B0 || !C0) return (int)hipErrorInvalidValue;
-  return gemm_impl(A0, a_major, lda, B0, b_major, ldb, C0, ldc, M, N, K, 1, nullptr, 0, nullptr, tile, nullptr, nullptr,
-                   stream, offsets, nbatch);
+  GemmProblem p = gemm_problem(A0, a_major, lda, B0, b_major, ldb, C0, ldc, M, N, K, tile);
+  p.batch = offsets; p.nbatch = nbatch;
+  return gemm_impl(p, stream);
 }
 
-// The same with every problem's K axis cut into `ksplit` slices (fp32 slabs in `workspace`, nbatch * ksplit * M * N
-// floats, summed per problem in slice order by one more launch): many same-shaped weight gradients whose outputs are
-// too small to fill the chip even side by side -- the repeated blocks of Inception-ResNet-v2 at batch 16 (10 x block35,
-// 20 x block17, 10 x block8: dW of 288x32 ... 2080x192 over K = 384 ... 9,744 pixels).  ldc == N.
-// spnet_gemm_batched_ksplit: the slice count this library would choose (about three workgroups per CU, slices at
-// least four K tiles deep) and the tile it goes with; 1 = no split.
-extern "C" long spnet_gemm_batched_ksplit(int M, int N, int K, int nbatch, int* tile_out) {
-  const int tile = N <= 64 ? 6 : 5;                  // 96x64 | 96x96
-  int bm, bn;
-  tile_dims(tile, &bm, &bn);
-  const long tiles = (long)spnet_cdiv(M, bm) * spnet_cdiv(N, bn) * (nbatch < 1 ? 1 : nbatch);
-  long want = (768 + tiles - 1) / tiles;
-  long maxk = K / (SP_BK * 4);
-  if (maxk < 1) maxk = 1;
-  if (want > maxk) want = maxk;
-  if (want > 64) want = 64;
-  if (tile_out) *tile_out = tile;
-  return want < 1 ? 1 : want;
-}
-extern "C" int spnet_gemm_f32_batched_splitk(const float* A0, const float* B0, float* C0, const long long* offsets,
-                                             int nbatch, int a_major, int lda, int b_major, int ldb, int ldc, int M,
-                                             int N, int K, int tile, int ksplit, float* workspace, long ws_floats,
-                                             void* stream) {
+// The same with every problem's K axis cut into `ksplit` slices (fp32 slabs, summed per problem in slice order by one more launch):
+// weight gradients too small to fill the chip even side by side -- the repeated blocks of Inception-ResNet-v2 at batch 16
+extern "C" long spnet_gemm_batched_ksplit(int M, int N, int K, int nbatch, int* tile_out) { return gemm_batched_ksplit(M, N, K, nbatch, tile_out); }
+extern "C" int spnet_gemm_f32_batched_splitk(const float* A0, const float* B0, float* C0, const long long* offsets, int nbatch,
+                                             int a_major, int lda, int b_major, int ldb, int ldc, int M, int N, int K, int tile,
+                                             int ksplit, float* workspace, long ws_floats, void* stream) {
   if (!offsets || !A0 || !B0 || !C0) return (int)hipErrorInvalidValue;
   if (ksplit > 1 && (!workspace || (((uintptr_t)workspace) & 15))) return (int)hipErrorInvalidValue;
-  return gemm_impl(A0, a_major, lda, B0, b_major, ldb, C0, ldc, M, N, K, ksplit > 1 ? ksplit : 1, workspace, ws_floats,
-                   nullptr, tile, nullptr, nullptr, stream, offsets, nbatch);
+  GemmProblem p = gemm_problem(A0, a_major, lda, B0, b_major, ldb, C0, ldc, M, N, K, tile);
+  p.batch = offsets; p.nbatch = nbatch;
+  p.split_k = ksplit > 1 ? ksplit : 1; p.workspace = workspace; p.ws_floats = ws_floats;
+  return gemm_impl(p, stream);
 }
 
-// dX[M,N] = dY[M,K] B[K,N] where dY is the BatchNorm-backward output dy = a[k]*g + b[k]*yp + c[k], blended from the
-// incoming gradient g and the saved pre-normalisation tensor yp while the A tile is staged (forward operand form:
-// B = W^T kept by the engine).  coef = [a | b | c], cld floats each (zero beyond channel K-1, cld a multiple of 32
-// covering K).  dy_out (or NULL) receives dy itself, once, for the weight-gradient GEMM of the layer.
-extern "C" int spnet_gemm_f32_bnblend(const float* g, const float* yp, const float* coef, int cld, int lda,
-                                      const float* B, int ldb, float* C, int ldc, int M, int N, int K, int tile,
-                                      float* dy_out, void* stream) {
-  return gemm_impl(g, SP_K_MAJOR, lda, B, SP_OUT_MAJOR, ldb, C, ldc, M, N, K, 1, nullptr, 0, nullptr, tile, nullptr,
-                   nullptr, stream, nullptr, 0, 1, yp, coef, cld, dy_out);
+// dX = dY B with dY = a[k]*g + b[k]*yp + c[k], the BatchNorm-backward output, blended while the A tile is staged (AX = 1;
+// forward operand form: B = W^T kept by the engine).
+extern "C" int spnet_gemm_f32_bnblend(const float* g, const float* yp, const float* coef, int cld, int lda, const float* B, int ldb,
+                                      float* C, int ldc, int M, int N, int K, int tile, float* dy_out, void* stream) {
+  GemmProblem p = gemm_problem(g, SP_K_MAJOR, lda, B, SP_OUT_MAJOR, ldb, C, ldc, M, N, K, tile);
+  p.xf = 1; p.X2 = yp; p.coef = coef; p.cld = cld; p.dy_out = dy_out;
+  return gemm_impl(p, stream);
 }
 
-// Y[M,N] (row stride ldy) = relu(x[:, :K]*scale + shift) W[K,N] with the BatchNorm + ReLU of every input channel applied
-// while the A tile is staged (AX = 2): the pre-activation 1x1 convolutions of keras DenseNet121 read the first K
-// channels of their block's Concatenate buffer (pixels ldx floats apart) and the BN+ReLU output is never written.
-// coef = [scale | (unused) | shift], cld floats each, zero beyond channel K-1 (cld a multiple of 32 covering K).
-// colstats / stat_rows (or NULL / NULL): BatchNorm column sums of Y as spnet_gemm_f32_colstats.
-extern "C" int spnet_gemm_f32_bnrelu(const float* x, int ldx, const float* coef, int cld, const float* W, int ldw,
-                                     float* Y, int ldy, int M, int N, int K, int tile, float* colstats, int* stat_rows,
-                                     void* stream) {
+// Y = relu(x[:, :K]*scale + shift) W with the BatchNorm + ReLU of every input channel applied while the A tile is staged (AX = 2):
+// keras DenseNet121's 1x1 convolutions read the first K channels of their block's Concatenate buffer (pixels ldx floats apart)
+extern "C" int spnet_gemm_f32_bnrelu(const float* x, int ldx, const float* coef, int cld, const float* W, int ldw, float* Y, int ldy,
+                                     int M, int N, int K, int tile, float* colstats, int* stat_rows, void* stream) {
   if (!x || !W || !Y || (!colstats) != (!stat_rows) || ldx < K) return (int)hipErrorInvalidValue;
-  return gemm_impl(x, SP_K_MAJOR, ldx, W, SP_OUT_MAJOR, ldw, Y, ldy, M, N, K, 1, nullptr, 0, nullptr, tile, colstats,
-                   stat_rows, stream, nullptr, 0, 2, nullptr, coef, cld, nullptr);
+  GemmProblem p = gemm_problem(x, SP_K_MAJOR, ldx, W, SP_OUT_MAJOR, ldw, Y, ldy, M, N, K, tile);
+  p.xf = 2; p.coef = coef; p.cld = cld; p.colstats = colstats; p.stat_rows = stat_rows;
+  return gemm_impl(p, stream);
 }
 
-// Forward-form GEMM that also emits BatchNorm column statistics of C: colstats[rows][2][N] holds per
-// row-tile partial (sum, sum of squares); *stat_rows (host) receives `rows`.  colstats must hold
-// ceil(M/32)*2*N floats (an upper bound for every tile shape).
-extern "C" int spnet_gemm_f32_colstats(const float* A, int a_major, int lda, const float* B, int b_major,
-                                       int ldb, float* C, int ldc, int M, int N, int K, int tile,
-                                       float* colstats, int* stat_rows, void* stream) {
+extern "C" int spnet_gemm_f32_colstats(const float* A, int a_major, int lda, const float* B, int b_major, int ldb, float* C, int ldc,
+                                       int M, int N, int K, int tile, float* colstats, int* stat_rows, void* stream) {
   if (!colstats || !stat_rows) return (int)hipErrorInvalidValue;
-  return gemm_impl(A, a_major, lda, B, b_major, ldb, C, ldc, M, N, K, 1, nullptr, 0, nullptr, tile, colstats,
-                   stat_rows, stream);
+  GemmProblem p = gemm_problem(A, a_major, lda, B, b_major, ldb, C, ldc, M, N, K, tile);
+  p.colstats = colstats; p.stat_rows = stat_rows;
+  return gemm_impl(p, stream);
 }
 
 // The forward convolution of an NHWC tensor as an implicit GEMM on the same kernel: y[B*OH*OW][Cout] = patches(x) * Wk,
@@ -823,8 +646,9 @@ extern "C" int spnet_conv_gemm_f32(const float* x, long ldx, const float* Wk, fl
     cg.pt = cg.pl = 0;
   }
   if (cg.OH < 1 || cg.OW < 1) return (int)hipErrorInvalidValue;
-  return gemm_impl(x, SP_K_MAJOR, (int)ldx, Wk, SP_OUT_MAJOR, Cout, y, ldy, B * cg.OH * cg.OW, Cout, KH * KW * C, 1, nullptr, 0,
-                   bias, tile, colstats, stat_rows, stream, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, &cg);
+  GemmProblem p = gemm_problem(x, SP_K_MAJOR, (int)ldx, Wk, SP_OUT_MAJOR, Cout, y, ldy, B * cg.OH * cg.OW, Cout, KH * KW * C, tile);
+  p.bias = bias; p.colstats = colstats; p.stat_rows = stat_rows; p.cg = &cg;
+  return gemm_impl(p, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

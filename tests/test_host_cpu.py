@@ -467,6 +467,46 @@ def test_gemm_tile_table_precedence_and_format():
     assert E._tile_for(0, 1, 0, 12345, 4, 8, 0) == 0                    # unlisted shape: the library's cost model
 
 
+def test_gemm_plans_match_the_recorded_ones_and_hold_their_invariants():
+    """spnet_gemm_plan (csrc/gemm_plan.h: refusals, form, tile, K split, main loop -- no device) returns exactly the plans of
+    tests/golden/gemm_plans.json, which were recorded from the host code as it stood before it was split into plan and
+    launch (pick_tile, auto_split, the eff table and every threshold moved verbatim): every key of gemm_tiles.json with
+    tile 0, the GEMM shapes of the 512x384 batch-32 step (tools/gemm_sweep.py) and the Dense head in all three forms, the
+    edges M = 32 / 33, K = 2047 / 2048, 255 / 256 / 511 / 512 tiles, nbatch 1 / 8 with no / exactly 2*M*N / an ample
+    workspace, every forced tile id 0..11 in every operand form, and the shape-level refusals.  One row is NOT the old
+    code's: C += A B (accumulate) with tile id 11 took the cost model's choice then and is a refusal now (spnet_hip.h)."""
+    import ctypes
+    import json
+    from spnet_amd import _lib
+    with open(os.path.join(ROOT, "tests", "golden", "gemm_plans.json")) as f:
+        rec = json.load(f)
+    I = {n: i for i, n in enumerate(rec["inputs"])}
+    P = {n: i for i, n in enumerate(rec["plan"])}
+    assert len(rec["cases"]) > 800 and {c["in"][I["tile"]] for c in rec["cases"]} >= set(range(12))
+    for c in rec["cases"]:
+        a = c["in"]
+        plan = (ctypes.c_int * 10)(*([-7] * 10))
+        try:
+            _lib.spnet_gemm_plan(*a, ctypes.addressof(plan))
+            rc = 0
+        except _lib.HipError:
+            rc = 1
+        got = list(plan)
+        assert (rc != 0) == (c["rc"] != 0), a
+        if rc:
+            assert got == [-7] * 10, a               # a refusal leaves every output field untouched
+            continue
+        assert got == c["plan"], (a, got, c["plan"])
+        M, N, K = a[I["M"]], a[I["N"]], a[I["K"]]
+        ns, kc = got[P["nsplit"]], got[P["k_chunk"]]
+        assert kc % 32 == 0 and (ns - 1) * kc < K <= ns * kc, a
+        nprob = a[I["nbatch"]] if a[I["have_batch"]] else 1
+        assert got[P["to_workspace"]] == (ns > 1) and (ns == 1 or (a[I["have_workspace"]] and ns * nprob * M * N <= a[I["ws_floats"]])), a
+        assert got[P["kslices"]] == (ns if a[I["have_batch"]] else 1), a
+        assert got[P["stat_rows"]] == -(-M // got[P["bm"]]), a
+        assert 1 <= got[P["tile"]] <= 10 and got[P["form"]] == {(0, 1): 0, (0, 0): 1, (1, 1): 2}[(a[0], a[1])], a
+
+
 def test_bench_self_launches_its_ranks_on_gloo():
     """`python bench.py --gpus 2` started the way the driver starts N=1 (no launcher, no WORLD_SIZE): the parent
     spawns the two ranks as a child torchrun job before touching torch.cuda, relays rank 0's one JSON line and

@@ -607,6 +607,36 @@ def test_gemm_rejects_misaligned(L):
     a = torch.zeros(64, 6, device="cuda")
     with pytest.raises(L.HipError):
         L.spnet_gemm_f32(a.data_ptr(), 0, 6, a.data_ptr(), 1, 6, a.data_ptr(), 6, 8, 6, 6, 0, None, 0, None, 0, st())
+    # Every refusal reachable through the ABI beyond spnet_gemm_f32's own: M = N = K = 32 (convolution: B = 1, H = W = 4,
+    # C = 32, 3x3 SAME, Cout = 32); each must raise and leave its sentinel-filled output untouched (no kernel runs).
+    # (a tile id outside 0..10 is refused by C += A B alone: every other entry point reads it as 0, the cost model's choice)
+    z = torch.zeros(64 * 64, device="cuda")            # every input: zeros, 16-byte aligned
+    out = torch.empty(64 * 64, device="cuda")
+    ws = torch.empty(4 * 32 * 32, device="cuda")
+    off = torch.zeros(3, dtype=torch.int64, device="cuda")
+    zp, op = z.data_ptr(), out.data_ptr()
+    conv = lambda ldy=32, C=32, stride=1: L.spnet_conv_gemm_f32(zp, C, zp, op, ldy, 1, 4, 4, C, 32, 3, 3, stride, 1, None, 0, None, None, st())
+    table = [
+        ("batched, ldc != N under a K split", lambda: L.spnet_gemm_f32_batched_splitk(zp, zp, op, off.data_ptr(), 1, 1, 32, 1, 32, 36, 32, 32, 32, 0, 2, ws.data_ptr(), ws.numel(), st())),
+        ("bnblend, cld short of a whole K tile", lambda: L.spnet_gemm_f32_bnblend(zp, zp, zp, 28, 32, zp, 32, op, 32, 32, 32, 32, 0, None, st())),
+        ("bnrelu, ldx < K", lambda: L.spnet_gemm_f32_bnrelu(zp, 28, zp, 32, zp, 32, op, 32, 32, 32, 32, 0, None, None, st())),
+        ("conv_gemm, C % 32 != 0", lambda: conv(C=36)),
+        ("conv_gemm, stride 3", lambda: conv(stride=3)),
+        ("conv_gemm, ldy < Cout", lambda: conv(ldy=28)),
+        ("accumulate, bad tile id", lambda: L.spnet_gemm_f32_accumulate(zp, 0, 32, zp, 0, 32, op, 32, 32, 32, 32, 11, st())),
+    ]
+    wrong = []
+    for name, call in table:
+        out.fill_(7.0)
+        try:
+            call()
+            wrong.append(name + ": no HipError")
+        except L.HipError:
+            pass
+        torch.cuda.synchronize()
+        if not bool((out == 7.0).all()):
+            wrong.append(name + ": output written")
+    assert not wrong, wrong
 
 
 class _DwForm:

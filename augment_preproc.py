@@ -34,10 +34,14 @@ def _read_planes(filename):
     return a[None] if a.ndim == 2 else np.ascontiguousarray(np.moveaxis(a, 2, 0))
 
 
-def augment_data(path='Train', n_augs=39, seed=0, chunk=256):
+def augment_data(path='Train', n_augs=39, seed=0, chunk=256, device_png=False):
     """Writes n_augs warped copies of every PNG + CSV pair of `path`; returns [(prefix, params)] of the files written,
-    params = dict(flip, angle, xt, yt) with xt = yt = None where no shift was drawn.  chunk: planes warped per launch."""
+    params = dict(flip, angle, xt, yt) with xt = yt = None where no shift was drawn.  chunk: planes warped per launch.
+    device_png: the warped batch is encoded where DeviceWarper leaves it (spnet_amd.png) instead of copied out for Pillow:
+    the same pixels and modes, other file bytes."""
     import torch
+    if device_png:
+        from spnet_amd.png import write_png_device
     from spnet_amd import augmentation as A
     from spnet_amd import parallel, utils
     print("augment_data: Augmenting data in", path, 'by a factor of', n_augs + 1)
@@ -72,17 +76,28 @@ def augment_data(path='Train', n_augs=39, seed=0, chunk=256):
                 j += 1
         out = torch.empty((len(index), warper.H, warper.W), dtype=torch.uint8, device=warper.X.device)
         warper.apply(params, out_u8=out)
-        out = out.cpu().numpy()
+        if not device_png:
+            out = out.cpu().numpy()
         j = 0
+        held = {}                  # device_png: plane count -> ([first plane of an image], [its file]), encoded in one batch
         for (i, k, p0, c), (flip, angle, xt, yt) in zip(jobs, draws):
             md, suffix = A.chain_metadata(utils.read_metadata(meta_file_list[i]), flip, angle, xt, yt, warper.W, warper.H)
             prefix = os.path.splitext(img_file_list[i])[0] + suffix
-            img = out[j] if c == 1 else np.moveaxis(out[j:j + c], 0, 2)
-            j += c
             with open(prefix + meta_extension, "w") as f:
                 f.write(caption_from_metadata(md))
-            Image.fromarray(np.ascontiguousarray(img)).save(prefix + '.png')     # 1 / 3 / 4 planes: L / RGB / RGBA, the input's mode
+            if device_png:
+                first, paths = held.setdefault(c, ([], []))
+                first.append(j)
+                paths.append(prefix + '.png')
+            else:
+                img = out[j] if c == 1 else np.moveaxis(out[j:j + c], 0, 2)
+                Image.fromarray(np.ascontiguousarray(img)).save(prefix + '.png')     # 1 / 3 / 4 planes: L / RGB / RGBA, the input's mode
+            j += c
             written.append((prefix, dict(flip=flip, angle=angle, xt=xt, yt=yt)))
+        for c, (first, paths) in held.items():          # the warped planes stay in HBM; [n][c][H][W] -> [n][H][W][c]
+            idx = torch.tensor(first, device=out.device)[:, None] + torch.arange(c, device=out.device)[None, :]
+            frames = out[idx] if c > 1 else out[idx[:, 0]]
+            write_png_device(frames.permute(0, 2, 3, 1).contiguous() if c > 1 else frames, paths)
         jobs.clear()
         planes.clear()
 
@@ -118,5 +133,7 @@ if __name__ == "__main__":
     parser.add_argument('-d', '--datapath', help='dataset directory in which to augment', default="Train/")
     parser.add_argument('-n', '--naugs', type=int, help='number of augmentations per image to generate', default=42)
     parser.add_argument('--seed', type=int, help='seed of the per-(file, augmentation) random streams', default=0)
+    parser.add_argument('--device_png', action='store_true',
+                        help='(additive) encode the PNG files on the GPU (Huffman-only deflate): same pixels, other file bytes')
     args = parser.parse_args()
-    augment_data(path=args.datapath, n_augs=args.naugs, seed=args.seed)
+    augment_data(path=args.datapath, n_augs=args.naugs, seed=args.seed, device_png=args.device_png)

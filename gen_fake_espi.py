@@ -11,9 +11,11 @@ steelpan_NNNNNNN.png + steelpan_NNNNNNN.csv pairs, the layout utils.build_datase
 Additive flags: --seed; --count_range LO HI (antinodes per frame; 0 6 is the published Dataset A, see fake_espi.draw_params);
 --bp_real DIR --bp_path DIR (also the band-pass mixed copies, steelpan_NNNNNNN_bp.png + .csv, as a data set of their own
 under bp_path, as fake_espi.write_dataset writes them); --host_params (the parameters of the reference-ordered host stream,
-fake_espi.draw_params, instead of the device sampler's own stream: the same distributions, other frames).
+fake_espi.draw_params, instead of the device sampler's own stream: the same distributions, other frames); --device_png (the
+PNGs are encoded from HBM by spnet_amd.png instead of copied out for Pillow: the same pixels, other file bytes).
 
-The PNGs are encoded by at most 16 threads of this process; nothing is forked once the GPU is initialised."""
+The PNGs are encoded (by default) and written by at most 16 threads of this process; nothing is forked once the GPU is
+initialised."""
 import argparse
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -24,11 +26,15 @@ from PIL import Image
 TRAIN_FRACTION = 0.8
 
 
-def _write_pair(stem, frame, rows):
+def _write_csv(stem, rows):
     from spnet_amd.fake_espi import rows_to_csv
-    Image.fromarray(frame).save(stem + ".png")
     with open(stem + ".csv", "w") as f:
         f.write(rows_to_csv(rows))
+
+
+def _write_pair(stem, frame, rows):
+    Image.fromarray(frame).save(stem + ".png")
+    _write_csv(stem, rows)
 
 
 def split_dirs(n, everything):
@@ -38,8 +44,9 @@ def split_dirs(n, everything):
 
 
 def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_range=(1, 7), bp_real=None, bp_path=None,
-                host_params=False, chunk=256, device="cuda:0", threads=None):
-    """Writes the data set; returns the label rows of every frame, in frame order."""
+                host_params=False, chunk=256, device="cuda:0", threads=None, device_png=False):
+    """Writes the data set; returns the label rows of every frame, in frame order.  device_png: the frames are encoded where
+    they are (spnet_amd.png.write_png_device) and only the compressed bytes cross to the host."""
     import torch
     from spnet_amd import fake_espi as F
     if (bp_real is None) != (bp_path is None):
@@ -60,6 +67,16 @@ def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_ran
     if host_params:         # that stream is keyed by (n, seed): one call for the whole set
         _, labels_host, U_host = F.generate_device(n, seed, device, want_u8=True, chunk=chunk, count_range=count_range)
     labels = []
+
+    def submit(pool, root, suffix, frames_dev, rows, lo, hi):
+        stems = [os.path.join(root, sub[i], "steelpan_" + str(i).zfill(7) + suffix) for i in range(lo, hi)]
+        if device_png:
+            from spnet_amd.png import write_png_device
+            write_png_device(frames_dev, [st + ".png" for st in stems], pool=pool)
+            return [pool.submit(_write_csv, st, r) for st, r in zip(stems, rows)]
+        frames = frames_dev.cpu().numpy()
+        return [pool.submit(_write_pair, st, frames[k], rows[k]) for k, st in enumerate(stems)]
+
     with ThreadPoolExecutor(max_workers=threads) as pool:
         for lo in range(0, n, chunk):
             hi = min(n, lo + chunk)
@@ -68,16 +85,12 @@ def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_ran
             else:
                 _, rows, U = F.generate_device(hi - lo, seed, device, want_u8=True, chunk=chunk, count_range=count_range,
                                                params="device", first_frame=lo)
-            frames = U.cpu().numpy()
-            jobs = [pool.submit(_write_pair, os.path.join(datapath, sub[i], "steelpan_" + str(i).zfill(7)), frames[i - lo],
-                                rows[i - lo]) for i in range(lo, hi)]
+            jobs = submit(pool, datapath, "", U, rows, lo, hi)
             if mixer is not None:
                 bp = mixer.draw(hi - lo, seeds=F.bandpass_seeds(hi - lo, seed, lo))
                 mixed = U.clone()
                 mixer.apply(bp, mixed, out_u8=mixed)
-                mixed = mixed.cpu().numpy()
-                jobs += [pool.submit(_write_pair, os.path.join(bp_path, sub[i], "steelpan_" + str(i).zfill(7) + "_bp"),
-                                     mixed[i - lo], rows[i - lo]) for i in range(lo, hi)]
+                jobs += submit(pool, bp_path, "_bp", mixed, rows, lo, hi)
             for j in jobs:
                 j.result()
             labels += rows
@@ -98,6 +111,9 @@ if __name__ == "__main__":
     p.add_argument('--bp_path', default=None, help='directory for the band-pass mixed copies (a data set of its own)')
     p.add_argument('--host_params', action='store_true',
                    help="draw the parameters on the host in the reference's RNG order instead of on the device")
+    p.add_argument('--device_png', action='store_true',
+                   help="(additive) encode the PNG files on the GPU (Huffman-only deflate): the same pixels, other file bytes")
     args = p.parse_args()
     gen_dataset(datapath=args.datapath, numframes=args.numframes, everything=args.all, seed=args.seed,
-                count_range=tuple(args.count_range), bp_real=args.bp_real, bp_path=args.bp_path, host_params=args.host_params)
+                count_range=tuple(args.count_range), bp_real=args.bp_real, bp_path=args.bp_path, host_params=args.host_params,
+                device_png=args.device_png)

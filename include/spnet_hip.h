@@ -604,6 +604,32 @@ int spnet_dense_producer_fin(const float* G, long ldg, const float* u, const flo
                              const float* mean, const float* invstd, long M, int c0, int c1, float* out, long ldo,
                              void* stream);
 
+/* ---- PNG output (csrc/png.hip): the encoder behind cv2.imwrite (gen_fake_espi.py:274-275, augment_preproc.py:99,
+ *      spnet/utils.py:132) for frames that are already in device memory ------------------------------------------------- */
+/* src: N uint8 frames [N][H][W][channels], channels 1 .. 4 (PNG colour types 0, 4, 2, 6 at 8 bits), no alignment asked.  The
+ * FILTERED STREAM of a frame is PNG's scanline stream with filter type 0 on every row: H rows of 1 + W*channels bytes,
+ * at most 2^27 bytes.  Both entries run one workgroup per frame; spnet_amd/png.py is the host side (code lengths, header
+ * bits, offsets, container).  N == 0: nothing to do, success.  hipErrorInvalidValue (nothing launched) for a shape outside
+ * these limits, a NULL pointer, or a word array that is not 4-byte aligned (offsets: 8-byte).
+ *   spnet_png_hist  hist [N][256] = byte counts of the filtered stream (the H filter bytes are in bin 0); adler [N] = its
+ *                   Adler-32 (sums modulo 65521, formed so that no 32-bit intermediate can overflow at any allowed size).
+ *   spnet_png_pack  writes the complete zlib stream of frame n at out + offsets[n]: 0x78 0x01, ONE final dynamic-Huffman
+ *                   deflate block (header bits, one code per byte of the filtered stream, end of block; no length or
+ *                   distance code), zero bits up to a byte boundary, adler[n] most significant byte first.
+ *                   codes [N][257]: canonical code of symbol s (RFC 1951 3.2.2, most significant code bit in the highest
+ *                   of its bits) | length << 16, lengths 0 .. 15; the kernel reverses the bits.  header [N][64]: the block
+ *                   header from BFINAL up to the last code length, bit i of the stream in bit i % 32 of word i / 32;
+ *                   header_bits [N] <= 2048.  offsets [N + 1] (64-bit): frame n may write bytes offsets[n] .. offsets[n+1]
+ *                   - 1 only and anything that does not fit is dropped, as is a frame whose slot is not inside
+ *                   [0, out_bytes); the host sizes the slots exactly (2 + ceil((header_bits + sum hist*length + length of
+ *                   256) / 8) + 4 bytes).  out: 4-byte aligned, out_bytes a multiple of 4, ZEROED by the caller: bits are
+ *                   merged with 32-bit atomic OR (stream order protects it; the call does not clear it).  Bytes outside
+ *                   the slots are not changed.  The bytes do not depend on the order threads run in. */
+int spnet_png_hist(const unsigned char* src, int N, int H, int W, int channels, uint32_t* hist, uint32_t* adler, void* stream);
+int spnet_png_pack(const unsigned char* src, int N, int H, int W, int channels, const uint32_t* codes, const uint32_t* header,
+                   const int* header_bits, const long long* offsets, const uint32_t* adler, unsigned char* out, long out_bytes,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -257,14 +257,29 @@ def draw_ellipse(img, center, axes, angle, startAngle=0, endAngle=360, color=(0,
 
 
 def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_extra=None, out_csv=None,
-                       show_true=True, verbosity=0):
+                       show_true=True, verbosity=0, png="host", png_chunk=64):
     """Overlay PNGs steelpan_pred_%05d.png and the zooniverse-style CSV (cx,cy,file,rings,a,b,angle)
-    from de-normalised true / predicted grids (utils.py:67-137)."""
+    from de-normalised true / predicted grids (utils.py:67-137).  png = "host": every overlay is saved by Pillow as it is
+    drawn; "device" (additive): the drawn RGB overlays are collected png_chunk at a time, uploaded, encoded on the GPU
+    (spnet_amd.png) and written by a thread pool -- the same pixels, file names and CSV rows, other file bytes."""
+    if png not in ("host", "device"):
+        raise ValueError('show_pred_ellipses: png is "host" or "device", got %r' % (png,))
     m = Yt.shape[0]
     num_draw = min(num_draw, m, len(file_list))
     if out_csv is not None:
         open(out_csv, "w").close()
     n_pred = int(Yt[0].size / cf.vars_per_pred)
+    held = []                                   # png == "device": (overlay as uint8 [H,W,3], its file), frames of one size
+
+    def flush():
+        if held:
+            import torch
+            from .png import write_png_device
+            if not torch.cuda.is_available():
+                raise RuntimeError('show_pred_ellipses: png="device" encodes on the GPU (no CPU fallback)')
+            write_png_device(torch.from_numpy(np.stack([h[0] for h in held])).cuda(), [h[1] for h in held])
+            held.clear()
+
     for j in range(num_draw):
         in_filename = file_list[j]
         img = Image.open(in_filename).convert("RGB")
@@ -285,7 +300,14 @@ def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_ex
         if out_csv is not None and csv_str == '':
             csv_str = '0,0,' + os.path.basename(in_filename) + ',0,0,0,0\n'
         d.text((5, orig_img_dims[1] - 14), os.path.basename(in_filename), fill=(255, 255, 255))
-        img.save(log_dir + '/steelpan_pred_' + str(j).zfill(5) + '.png')
+        if png == "host":
+            img.save(log_dir + '/steelpan_pred_' + str(j).zfill(5) + '.png')
+        else:
+            frame = np.asarray(img, dtype=np.uint8)
+            if held and (held[0][0].shape != frame.shape or len(held) >= png_chunk):
+                flush()
+            held.append((frame, log_dir + '/steelpan_pred_' + str(j).zfill(5) + '.png'))
         if out_csv is not None:
             with open(out_csv, "a") as f:
                 f.write(csv_str)
+    flush()

@@ -34,11 +34,52 @@ def _read_planes(filename):
     return a[None] if a.ndim == 2 else np.ascontiguousarray(np.moveaxis(a, 2, 0))
 
 
-def augment_data(path='Train', n_augs=39, seed=0, chunk=256, device_png=False):
+class _DevicePlanes:
+    """A file whose planes the GPU decodes when its batch is warped (--device_decode): what _read_planes would return for
+    it has shape (channels, height, width)."""
+
+    def __init__(self, filename, info):
+        self.filename = filename
+        self.shape = (info.channels, info.height, info.width)
+
+
+def _planes_or_promise(filename):
+    """_read_planes, or for a file the device decodes to the same planes (8 bits, L / RGB / RGBA) a _DevicePlanes."""
+    from spnet_amd import png as P
+    info = P._read_and_parse(filename)
+    if info.device and info.channels in (1, 3, 4):
+        return _DevicePlanes(filename, info)
+    return _read_planes(filename)
+
+
+def _planes_on_device(planes):
+    """The batch's planes as one uint8 device tensor [P,H,W]: promised files are decoded on the GPU, one call per channel
+    count (a file the kernels reject is decoded by Pillow there), the others uploaded."""
+    import torch
+    from spnet_amd import png as P
+    total = sum(p.shape[0] for p in planes)
+    X = torch.empty((total,) + tuple(planes[0].shape[1:]), dtype=torch.uint8, device="cuda")
+    groups, p0 = {}, 0
+    for p in planes:
+        if isinstance(p, _DevicePlanes):
+            groups.setdefault(p.shape[0], []).append((p0, p.filename))
+        else:
+            X[p0:p0 + p.shape[0]] = torch.from_numpy(p).cuda()
+        p0 += p.shape[0]
+    for c, members in groups.items():
+        frames = P.read_png_device([f for _, f in members], channels="all", device=X.device)        # [n,H,W,c]
+        idx = torch.tensor([q for q, _ in members], device=X.device)[:, None] + torch.arange(c, device=X.device)[None, :]
+        X[idx] = frames.permute(0, 3, 1, 2)
+    return X
+
+
+def augment_data(path='Train', n_augs=39, seed=0, chunk=256, device_png=False, device_decode=False):
     """Writes n_augs warped copies of every PNG + CSV pair of `path`; returns [(prefix, params)] of the files written,
     params = dict(flip, angle, xt, yt) with xt = yt = None where no shift was drawn.  chunk: planes warped per launch.
     device_png: the warped batch is encoded where DeviceWarper leaves it (spnet_amd.png) instead of copied out for Pillow:
-    the same pixels and modes, other file bytes."""
+    the same pixels and modes, other file bytes.
+    device_decode: the originals are decoded on the GPU from the files' bytes (spnet_amd.png.read_png_device) into the
+    tensor DeviceWarper warps, instead of by Pillow and uploaded: the same planes, the same files written."""
     import torch
     if device_png:
         from spnet_amd.png import write_png_device
@@ -60,7 +101,7 @@ def augment_data(path='Train', n_augs=39, seed=0, chunk=256, device_png=False):
     def flush():
         if not jobs:
             return
-        X = np.concatenate(planes)
+        X = _planes_on_device(planes) if device_decode else np.concatenate(planes)
         warper = A.DeviceWarper(X)
         index, draws = [], []
         for i, k, p0, c in jobs:
@@ -107,8 +148,8 @@ def augment_data(path='Train', n_augs=39, seed=0, chunk=256, device_png=False):
         for i in range(numfiles):
             if 0 == i % 10:
                 print("     Progress: i =", i, "/", numfiles)
-            pl = _read_planes(img_file_list[i])
-            if shape is not None and pl.shape[1:] != shape:
+            pl = _planes_or_promise(img_file_list[i]) if device_decode else _read_planes(img_file_list[i])
+            if shape is not None and tuple(pl.shape[1:]) != tuple(shape):
                 flush()                      # a batch holds frames of one size
                 n_planes = 0
             shape = pl.shape[1:]
@@ -135,5 +176,8 @@ if __name__ == "__main__":
     parser.add_argument('--seed', type=int, help='seed of the per-(file, augmentation) random streams', default=0)
     parser.add_argument('--device_png', action='store_true',
                         help='(additive) encode the PNG files on the GPU (Huffman-only deflate): same pixels, other file bytes')
+    parser.add_argument('--device_decode', action='store_true',
+                        help='(additive) decode the original PNG files on the GPU (inflate + unfilter): same planes, same output')
     args = parser.parse_args()
-    augment_data(path=args.datapath, n_augs=args.naugs, seed=args.seed, device_png=args.device_png)
+    augment_data(path=args.datapath, n_augs=args.naugs, seed=args.seed, device_png=args.device_png,
+                 device_decode=args.device_decode)

@@ -12,12 +12,12 @@ import spnet.config as cf
 
 
 def evaluate_network(model=None, weights_file="", datapath="Test/", fraction=1.0, log_dir="", batch_size=32,
-                     pred_grid=[6, 6, 2], set_means_ranges=True, device_png=False):
+                     pred_grid=[6, 6, 2], set_means_ranges=True, device_png=False, device_decode=False):
     np.random.seed(1)
     print("Getting data..., fraction = ", fraction)
     X_test, Y_test, test_file_list, pred_shape = build_dataset(
         path=datapath, load_frac=fraction, set_means_ranges=set_means_ranges, batch_size=batch_size, shuffle=False,
-        pred_grid=pred_grid)
+        pred_grid=pred_grid, device_decode=device_decode)
     if model is None:
         print("Loading full model from full_model.h5")
         model = models.load_model("full_model.h5")
@@ -25,7 +25,9 @@ def evaluate_network(model=None, weights_file="", datapath="Test/", fraction=1.0
     m = X_test.shape[0]
     print("    Predicting... (m = ", m, " frames in this (Test?) dataset)", sep="")
     start_time = time.time()
-    Y_pred = model.predict(X_test, batch_size=batch_size)
+    # device_decode: uint8 device frames at the files' own size; every layout but 'big' resizes them on the device
+    Y_pred = model.predict(X_test, batch_size=batch_size, resize=True) if device_decode and cf.model_type != 'big' else \
+        model.predict(X_test, batch_size=batch_size)
     elapsed = time.time() - start_time
     print("    ...elapsed time to predict = ", elapsed, "s.   FPS = ", m * 1.0 / elapsed)
 
@@ -67,6 +69,9 @@ if __name__ == '__main__':
     p.add_argument('-b', '--batch_size', type=int, default=16, help='Batch size to use')
     p.add_argument('--model_type', default=None, help="override spnet.config.model_type ('monolithic' | 'big')")
     p.add_argument('--loss_type', default=None, help="override spnet.config.loss_type")
+    p.add_argument('--device_decode', action='store_true',
+                   help="(additive) upload the PNG files as they are and decode (and resize) them on the GPU; formats the "
+                        "device does not take are decoded by Pillow: same predictions")
     p.add_argument('--device_png', action='store_true',
                    help="(additive) encode the overlay PNG files on the GPU (Huffman-only deflate): the same pixels, "
                         "other file bytes")
@@ -75,7 +80,8 @@ if __name__ == '__main__':
         if val is not None:
             setattr(cf, attr, val)
     model = evaluate_network(weights_file=args.weights, datapath=args.datapath + '/', fraction=args.fraction,
-                             log_dir=args.logdir, batch_size=args.batch_size, device_png=args.device_png)
+                             log_dir=args.logdir, batch_size=args.batch_size, device_png=args.device_png,
+                             device_decode=args.device_decode)
     weights2name = "eval_end_weights.hdf5"
     print("Saving model to", weights2name)
     model.save_weights(weights2name)

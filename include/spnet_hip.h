@@ -630,6 +630,31 @@ int spnet_png_pack(const unsigned char* src, int N, int H, int W, int channels, 
                    const int* header_bits, const long long* offsets, const uint32_t* adler, unsigned char* out, long out_bytes,
                    void* stream);
 
+/* ---- PNG input (csrc/png_decode.hip, csrc/inflate_core.h): the decoder behind Image.open(...).convert("RGB")
+ *      (spnet/utils.py:325-345) for files whose bytes are uploaded as they sit on disk ---------------------------------- */
+/* One wave per file; spnet_amd/png.py is the host side (container, CRCs, classification, host fallback).  status [N]
+ * (int32) holds inflate_core.h's inflate::Status per file: 0 = decoded, non-zero = that file's work ended there (1 bad zlib
+ * header, 2 reserved block type, 3 LEN/NLEN mismatch, 4 over-subscribed / incomplete code, 5 invalid symbol, 6 distance
+ * before the start of the output, 7 input exhausted, 8 output longer than L, 9 output shorter than L, 10 Adler-32
+ * mismatch, 11 filter type above 4, 12 extent outside the blob); the other files of the launch are not affected.  N == 0:
+ * nothing to do, success.  hipErrorInvalidValue (nothing launched) for a NULL pointer, a misaligned offsets / status
+ * array or a size outside the limits below.
+ *   spnet_png_inflate   blob: the zlib streams (concatenated IDAT payloads) of N files, file n in bytes offsets[n] ..
+ *                       offsets[n+1] - 1 of the blob_bytes bytes (64-bit offsets, 8-byte aligned; a stream is at most 2^30
+ *                       bytes).  Accepts all of RFC 1950 / 1951 without a preset dictionary.  L = H * (1 + W * channels)
+ *                       <= 2^27 is the length every stream must inflate to; file n's filtered scanline stream is written
+ *                       to out + n * out_stride (out_stride >= L).  No byte before blob + offsets[n] or at or after blob +
+ *                       offsets[n+1] is read for file n; no byte outside out + n * out_stride .. + L - 1 is written; of a
+ *                       file with non-zero status a prefix of its slot may have been written.  Writes every status[n].
+ *   spnet_png_unfilter  inflated: the streams as written above (in_stride >= L); files whose status is non-zero are
+ *                       skipped.  channels (bytes per pixel) 1 .. 4, W * channels <= 32768.  first (may be NULL): uint8
+ *                       [N][H][W], channel 0 of every pixel; all (may be NULL): uint8 [N][H][W][channels]; at least one.
+ *                       A filter type above 4 sets status[n] = 11 and ends that file (rows above it are written). */
+int spnet_png_inflate(const unsigned char* blob, long blob_bytes, const long long* offsets, int N, long L, long out_stride,
+                      unsigned char* out, int* status, void* stream);
+int spnet_png_unfilter(const unsigned char* inflated, long in_stride, int N, int H, int W, int channels, unsigned char* first,
+                       unsigned char* all, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,8 @@ default_image_dir = '/home/shawley/datasets/zooniverse_steelpan/'
 
 
 def predict_network(weights_file="spnet.model", datapath=default_image_dir, fraction=1.0, log_dir='logs/Predicting/',
-                    batch_size=16, model=None, X_pred='', u8_frames=False, device_resize=False, device_png=False):
+                    batch_size=16, model=None, X_pred='', u8_frames=False, device_resize=False, device_png=False,
+                    device_decode=False):
     img_file_list = []
     resize = False
     if isinstance(X_pred, str) and X_pred == '':
@@ -35,9 +36,13 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
         print("      Total files = ", total_files, ", going to load total_load = ", total_load)
         # device_resize: the files' own grey levels travel, the GPU resizes them to force_dim (implies u8 frames; the
         # 'big' layout has nothing to resize)
-        resize = bool(device_resize) and grayscale and force_dim is not None
+        # device_decode: the files' bytes travel, the GPU inflates and unfilters them (implies device_resize)
+        if device_decode and not grayscale:
+            raise ValueError("device_decode is for grayscale input (model_type 'big' / 'monolithic')")
+        resize = (bool(device_resize) or bool(device_decode)) and grayscale and force_dim is not None
         X_pred, _ = build_X(total_load, img_file_list, force_dim=force_dim, grayscale=grayscale,
-                            as_uint8=(bool(u8_frames) or resize) and grayscale, device_resize=resize)
+                            as_uint8=(bool(u8_frames) or resize or bool(device_decode)) and grayscale, device_resize=resize,
+                            device_decode=bool(device_decode))
         print("")
 
     if model is None:
@@ -88,6 +93,9 @@ if __name__ == '__main__':
     p.add_argument('--device_resize', action='store_true',
                    help="(additive, implies --u8_frames) load the frames at their own size and resize them to the "
                         "network's on the GPU, bit-identical to the PIL resize of the default path")
+    p.add_argument('--device_decode', action='store_true',
+                   help="(additive, implies --device_resize) upload the PNG files as they are and decode them on the GPU "
+                        "(inflate + unfilter; formats the device does not take are decoded by Pillow): same predictions")
     p.add_argument('--device_png', action='store_true',
                    help="(additive) encode the overlay PNG files on the GPU (Huffman-only deflate): the same pixels, "
                         "other file bytes")
@@ -97,4 +105,4 @@ if __name__ == '__main__':
             setattr(cf, attr, val)
     predict_network(weights_file=args.weights, datapath=args.datapath, fraction=args.fraction, log_dir=args.logdir,
                     batch_size=args.batch_size, u8_frames=args.u8_frames, device_resize=args.device_resize,
-                    device_png=args.device_png)
+                    device_png=args.device_png, device_decode=args.device_decode)

@@ -84,7 +84,7 @@ def draw_blur_gate(blur_prob_outer=0.4, blur_prob=0.3):
 class DeviceAugmenter:
     """Keeps the pristine frames [N,H,W,1] in HBM and writes augmented batches into a device buffer."""
 
-    def __init__(self, X_orig, real_blur=False, bandpass_real=None, bpmix_prob=0.3):
+    def __init__(self, X_orig, real_blur=False, bandpass_real=None, bpmix_prob=0.3, device_decode=False):
         """bandpass_real (None = off, the reference's default: its bp_mixup call is commented out, callbacks.py:333): a
         directory of real *.png frames of the frames' size, a BandpassPool or a uint8 device tensor [R,H,W]; after the
         blur gate, np.random.rand() < bpmix_prob selects the frames that are band-pass mixed (callbacks.py:311-315).
@@ -107,7 +107,7 @@ class DeviceAugmenter:
         self.bp = None
         if bandpass_real is not None and self.bpmix_prob > 0:
             pool = bandpass_real if isinstance(bandpass_real, BandpassPool) else \
-                BandpassPool.get(bandpass_real, self.H, self.W, self.X.device)
+                BandpassPool.get(bandpass_real, self.H, self.W, self.X.device, device_decode=device_decode)
             if (pool.H, pool.W) != (self.H, self.W):
                 raise ValueError("DeviceAugmenter: band-pass pool is %dx%d, the frames are %dx%d" % (pool.H, pool.W, self.H, self.W))
             self.bp = pool.mixer
@@ -888,13 +888,43 @@ def bandpass_check_dims(H, W):
                          "frequencies), got %d x %d" % (H, W))
 
 
-def read_real_frames(path, H, W):
+def read_real_frames(path, H, W, device_decode=False, device=None, return_info=False):
     """The sorted *.png files of `path` (the reference's glob order is unspecified) read as greyscale uint8 [R,H,W].
-    FileNotFoundError when there are none, ValueError naming the first file of another size."""
+    FileNotFoundError when there are none, ValueError naming the first file of another size.
+    device_decode (additive): the frames come back as a uint8 DEVICE tensor.  Grey files (colour type 0, 8 bits: channel 0
+    is what convert("L") gives) are decoded on the GPU (spnet_amd.png); every other file -- convert("L") weighs R, G and
+    B -- is decoded here as before and uploaded into its place.  return_info: also the sorted indices of the files the
+    host decoded (a grey file the kernels reject is among them)."""
     from PIL import Image
     files = sorted(glob.glob(os.path.join(path, '*.png')))
     if not files:
         raise FileNotFoundError("bandpass_mixup: no real *.png images in %r" % path)
+    if device_decode:
+        from concurrent.futures import ThreadPoolExecutor
+        from . import png as P
+        if not torch.cuda.is_available():
+            raise RuntimeError("bandpass_mixup: device_decode decodes on the GPU (there is no CPU decoder here)")
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        with ThreadPoolExecutor(max_workers=P._pool_size(P.MAX_THREADS, len(files))) as tp:
+            infos = list(tp.map(P._read_and_parse, files))
+        out = torch.empty((len(files), H, W), dtype=torch.uint8, device=device)
+        grey = [k for k, i in enumerate(infos) if i.device and i.colour_type == 0]
+        host = [k for k in range(len(files)) if k not in set(grey)]
+        for k in grey:                  # the size check of the host path, before anything is decoded
+            if (infos[k].height, infos[k].width) != (H, W):
+                raise ValueError("bandpass_mixup: real image %s is %dx%d, the frames are %dx%d"
+                                 % (files[k], infos[k].height, infos[k].width, H, W))
+        if grey:
+            got, _, fell = P._decode_parsed([infos[k] for k in grey], [files[k] for k in grey], device, "first", True)
+            out[torch.as_tensor(grey, device=device)] = got
+            host = sorted(host + [grey[j] for j in fell])
+        for k in (k for k in host if k not in grey):
+            with Image.open(files[k]) as im:
+                a = np.array(im.convert("L"), dtype=np.uint8)
+            if a.shape != (H, W):
+                raise ValueError("bandpass_mixup: real image %s is %dx%d, the frames are %dx%d" % (files[k], a.shape[0], a.shape[1], H, W))
+            out[k] = torch.from_numpy(a).to(device)
+        return (files, out, host) if return_info else (files, out)
     imgs = []
     for f in files:
         with Image.open(f) as im:
@@ -908,10 +938,11 @@ def read_real_frames(path, H, W):
 class BandpassPool:
     """The real frames of the mix-up on the device, uint8 [R,H,W], and the low-frequency windows of all four flips of
     each, table [R,4,16,16,2] fp32 (flip order BP_FLIPS), computed once.  src: a directory of *.png (sorted) or a uint8
-    device tensor [R,H,W].  BandpassPool.get caches directory pools by (realpath, H, W, device)."""
+    device tensor [R,H,W].  BandpassPool.get caches directory pools by (realpath, H, W, device).  device_decode (additive,
+    directories only): the grey files are decoded on the GPU (read_real_frames): the same frames."""
     _cache = {}
 
-    def __init__(self, src, H, W, device=None):
+    def __init__(self, src, H, W, device=None, device_decode=False):
         bandpass_check_dims(H, W)
         self.H, self.W = int(H), int(W)
         if isinstance(src, torch.Tensor):
@@ -922,12 +953,16 @@ class BandpassPool:
             self.images = src.contiguous()
         else:
             self.path = str(src)
-            self.files, host = read_real_frames(self.path, H, W)
+            if not device_decode:
+                self.files, host = read_real_frames(self.path, H, W)
             if device is None:
                 if not torch.cuda.is_available():
                     raise RuntimeError("BandpassPool: the band-pass mix-up runs on the GPU (no CPU fallback)")
                 device = torch.device("cuda", torch.cuda.current_device())
-            self.images = torch.from_numpy(host).to(device)
+            if device_decode:
+                self.files, self.images = read_real_frames(self.path, H, W, device_decode=True, device=device)
+            else:
+                self.images = torch.from_numpy(host).to(device)
         self.n_real = int(self.images.shape[0])
         dev = self.images.device
         win = torch.empty((len(BP_FLIPS), self.n_real, 16, 16, 2), dtype=torch.float32, device=dev)
@@ -941,7 +976,7 @@ class BandpassPool:
         self.mixer = BandpassMixer(self)
 
     @classmethod
-    def get(cls, src, H, W, device=None):
+    def get(cls, src, H, W, device=None, device_decode=False):
         if isinstance(src, cls):
             return src
         if isinstance(src, torch.Tensor):
@@ -951,7 +986,7 @@ class BandpassPool:
         key = (os.path.realpath(str(src)), int(H), int(W), str(device))
         pool = cls._cache.get(key)
         if pool is None:
-            pool = cls._cache[key] = cls(src, H, W, device)
+            pool = cls._cache[key] = cls(src, H, W, device, device_decode=device_decode)
         return pool
 
 

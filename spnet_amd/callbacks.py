@@ -94,7 +94,7 @@ class AugmentOnTheFly(Callback):
 
     def __init__(self, X, Y, orig_img_shape=(384, 512), aug_every=1, chunk=256, seed=1, real_blur=False,
                  bandpass_real=None, bpmix_prob=0.3, warp=False, warp_files=None, pred_grid=(6, 6, 2), warp_source=None,
-                 warp_targets="host"):
+                 warp_targets="host", device_decode=False):
         """real_blur=False reproduces the reference, whose Gaussian blur is a no-op (the result of cv2.GaussianBlur is
         discarded, augmentation.py:66-70); True applies it (train_spnet.py --augment_blur).
         bandpass_real: directory of real *.png frames of the training frames' size -- after the blur, a frame is
@@ -115,7 +115,10 @@ class AugmentOnTheFly(Callback):
         (warp_targets) before its warp is launched; "device" (needs device metadata, so a warp_source; and a warp_source
         needs it) = they come from spnet_encode_targets, which also rewrites the warp records of the rejected frames: a
         chunk is records upload -> targets -> warp -> resize -> cutout ... with no synchronisation between them, and the
-        rejected count is summed on the device and read once per epoch."""
+        rejected count is summed on the device and read once per epoch.
+        device_decode (with warp_files and / or a bandpass_real directory): the full-size frames of the warp, and the grey
+        real frames of the mix-up, are decoded on the GPU from the files' bytes (spnet_amd.png) instead of by Pillow and
+        uploaded: the same frames."""
         super().__init__()
         import torch
         from . import parallel
@@ -130,7 +133,7 @@ class AugmentOnTheFly(Callback):
         self.X_orig = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X)).to(dev)
         self.X_aug = self.X_orig.clone()      # rows no epoch has augmented yet hold the pristine frame, not garbage
         self.augmenter = DeviceAugmenter(self.X_orig, real_blur=real_blur, bandpass_real=bandpass_real,
-                                         bpmix_prob=bpmix_prob)
+                                         bpmix_prob=bpmix_prob, device_decode=device_decode)
         self.warper = None
         self.rejected = 0                     # frames of the last augmented epoch whose warp was rejected
         if warp_targets not in ("host", "device"):
@@ -140,9 +143,9 @@ class AugmentOnTheFly(Callback):
                              "device metadata; files' metadata is on the host)")
         self.warp_targets = warp_targets
         if warp or warp_source is not None:
-            self._setup_warp(warp_files, pred_grid, dev, warp_source)
+            self._setup_warp(warp_files, pred_grid, dev, warp_source, device_decode)
 
-    def _setup_warp(self, warp_files, pred_grid, dev, warp_source=None):
+    def _setup_warp(self, warp_files, pred_grid, dev, warp_source=None, device_decode=False):
         import torch
         from .augmentation import DeviceWarper
         n = int(self.X_orig.shape[0])
@@ -160,9 +163,14 @@ class AugmentOnTheFly(Callback):
             if warp_files is None or len(warp_files) != n:
                 raise ValueError("AugmentOnTheFly(warp=True) needs warp_files: the PNG file of each of the %d training frames" % n)
             files = list(warp_files)
-            X_full, _ = utils.build_X(n, files, grayscale=True, as_uint8=True, device_resize=True)
+            if device_decode:
+                from .png import read_png_device
+                X_dev = read_png_device(files, device=dev)
+            else:
+                X_full, _ = utils.build_X(n, files, grayscale=True, as_uint8=True, device_resize=True)
+                X_dev = torch.from_numpy(X_full[..., 0]).to(dev)
             meta = [utils.read_metadata(os.path.splitext(f)[0] + cf.meta_extension) for f in files]
-            self.warper = DeviceWarper(torch.from_numpy(X_full[..., 0]).to(dev), meta, pred_grid=pred_grid)
+            self.warper = DeviceWarper(X_dev, meta, pred_grid=pred_grid)
         Yh = self.Y.detach().cpu().numpy() if isinstance(self.Y, torch.Tensor) else np.asarray(self.Y)
         self.Y_aug = torch.from_numpy(np.ascontiguousarray(Yh, dtype=np.float32)).to(dev)
         self._y_upload = None

@@ -19,8 +19,14 @@ The code construction is fixed, so that an independent restatement (tests/helper
             the 258 lengths run-length coded greedily as ONE sequence (zeros: 18 while >= 11 remain, then 17 for 3 .. 10, else
             literal zeros; other values: the value, then 16 while >= 3 repeats remain, then the value), the code-length code
             built by the same procedure with max_len 7
+
+Reading (csrc/png_decode.hip, csrc/inflate_core.h; opt-in --device_decode): parse_png takes the container apart on the host,
+decode_png_device / read_png_device upload the zlib streams as they are, inflate and unfilter them on the GPU (any deflate
+stream; 8-bit non-interlaced colour types 0 / 2 / 4 / 6) and leave every other file, and every file the kernels reject, to
+the default path's Pillow call.
 """
 import heapq
+import os
 import struct
 import zlib
 from concurrent.futures import ThreadPoolExecutor
@@ -342,3 +348,239 @@ def write_png_device(frames, paths, threads=MAX_THREADS, pool=None):
         return list(pool.map(job, range(N)))
     with ThreadPoolExecutor(max_workers=_pool_size(threads, N)) as own:
         return list(own.map(job, range(N)))
+
+
+# ----------------------------------------------------------------------------- reading: container
+MAX_STREAM = 1 << 27            # spnet_png_inflate: L = H * (1 + W * channels)
+MAX_ROW = 32768                 # spnet_png_unfilter: W * channels
+MAX_ZSTREAM = 1 << 30           # spnet_png_inflate: compressed bytes of one file
+CHANNELS = {0: 1, 4: 2, 2: 3, 6: 4}          # PNG colour type -> channels, 8 bits per sample
+STATUS_NAMES = ("ok", "bad zlib header", "reserved block type", "LEN/NLEN mismatch", "over-subscribed or incomplete code",
+                "invalid symbol", "distance too far", "input exhausted", "output longer than expected",
+                "output shorter than expected", "Adler-32 mismatch", "filter type above 4", "extent outside the blob")
+
+
+class PngInfo:
+    """What parse_png found.  width, height, bit_depth, colour_type, interlace: IHDR's (None where IHDR could not be
+    read); trns: a tRNS chunk was seen; zstream: the IDAT payloads, concatenated; channels: bytes per pixel of a file the
+    device takes; host_reason: None for a file the device decodes, else why the host has to (str)."""
+    __slots__ = ("width", "height", "bit_depth", "colour_type", "interlace", "trns", "zstream", "channels", "host_reason")
+
+    def __init__(self):
+        self.width = self.height = self.bit_depth = self.colour_type = self.interlace = self.channels = None
+        self.trns = False
+        self.zstream = b""
+        self.host_reason = None
+
+    @property
+    def device(self):
+        return self.host_reason is None
+
+
+def parse_png(data):
+    """The container reader, the inverse of png_pieces: signature, IHDR, the payloads of all IDAT chunks in order, the CRC
+    of every chunk (the content of ancillary chunks is skipped), up to IEND.  Raises nothing: a file the device cannot take
+    (8 bits, colour type 0 / 2 / 4 / 6, not interlaced, no tRNS, within the kernels' sizes is what it takes), a damaged
+    container included, comes back with host_reason set and is left to the host decoder, which decides what it is."""
+    info = PngInfo()
+    data = memoryview(data)
+    n = len(data)
+    if n < 8 or bytes(data[:8]) != PNG_SIGNATURE:
+        info.host_reason = "no PNG signature"
+        return info
+    pos = 8
+    idat = []
+    ended = False
+    first = True
+    while pos + 12 <= n:
+        length, = struct.unpack(">I", data[pos:pos + 4])
+        tag = bytes(data[pos + 4:pos + 8])
+        if pos + 12 + length > n:
+            info.host_reason = "chunk %r runs past the end of the file" % tag
+            return info
+        body = data[pos + 8:pos + 8 + length]
+        critical = not (tag[0] & 0x20)
+        crc, = struct.unpack(">I", data[pos + 8 + length:pos + 12 + length])
+        if zlib.crc32(body, zlib.crc32(tag)) != crc:           # (of an ancillary chunk too: the default decoder raises on it)
+            info.host_reason = "CRC of chunk %r" % tag
+            return info
+        pos += 12 + length
+        if first != (tag == b"IHDR"):
+            info.host_reason = "IHDR is not the first chunk" if first else "a second IHDR"
+            return info
+        first = False
+        if tag == b"IHDR":
+            if length != 13:
+                info.host_reason = "IHDR of %d bytes" % length
+                return info
+            (info.width, info.height, info.bit_depth, info.colour_type, compression, filt,
+             info.interlace) = struct.unpack(">IIBBBBB", body)
+            if compression or filt:
+                info.host_reason = "compression / filter method %d / %d" % (compression, filt)
+        elif tag == b"IDAT":
+            idat.append(body)
+        elif tag == b"tRNS":
+            info.trns = True
+        elif tag == b"IEND":
+            ended = True
+            break
+        elif critical and tag != b"PLTE":        # (a palette may accompany colour types 2 and 6 as a suggestion)
+            info.host_reason = info.host_reason or "critical chunk %r" % tag
+    info.zstream = idat[0] if len(idat) == 1 else b"".join(idat)
+    if info.host_reason is not None:
+        return info
+    if info.width is None or not ended:
+        info.host_reason = "no IEND"
+    elif info.bit_depth != 8:
+        info.host_reason = "bit depth %d" % info.bit_depth
+    elif info.colour_type not in CHANNELS:
+        info.host_reason = "colour type %d" % info.colour_type
+    elif info.interlace:
+        info.host_reason = "interlaced"
+    elif info.trns:
+        info.host_reason = "tRNS"
+    elif info.width < 1 or info.height < 1:
+        info.host_reason = "empty image"
+    else:
+        info.channels = CHANNELS[info.colour_type]
+        if info.width * info.channels > MAX_ROW or info.height * (1 + info.width * info.channels) > MAX_STREAM:
+            info.host_reason = "larger than the device decoder's budget"
+        elif len(info.zstream) > MAX_ZSTREAM:
+            info.host_reason = "compressed stream larger than the device decoder's budget"
+    return info
+
+
+# ----------------------------------------------------------------------------- reading: device
+def _host_frame(source, channels):
+    """The default path's decode of one file (spnet_amd.utils._load_one's Pillow call decides what a damaged file is):
+    channel 0 of convert("RGB") as [H,W], or every channel as the file holds them, [H,W,C]."""
+    import io
+    from PIL import Image
+    f = source if isinstance(source, (str, os.PathLike)) else io.BytesIO(source)
+    if channels == "first":
+        return np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8)[:, :, 0]
+    arr = np.asarray(Image.open(f))
+    if arr.dtype != np.uint8:
+        raise ValueError('png: channels="all" holds 8-bit samples, this file decodes to %s' % arr.dtype)
+    return arr.reshape(arr.shape[0], arr.shape[1], -1)
+
+
+def inflate_unfilter_device(blob, offsets, N, H, W, channels, first=None, full=None):
+    """The two launches on uploaded streams: blob (uint8 device tensor), offsets (int64 device tensor [N + 1], positions in
+    blob).  first [N,H,W] / full [N,H,W,channels]: uint8 device tensors to fill (either may be None).  Returns status, an
+    int32 DEVICE tensor [N]; nothing is synchronised."""
+    import torch
+    from . import _lib as L
+    length = H * (1 + W * channels)
+    inflated = torch.empty((N, length), dtype=torch.uint8, device=blob.device)
+    status = torch.empty((N,), dtype=torch.int32, device=blob.device)
+    with torch.cuda.device(blob.device):
+        L.spnet_png_inflate(blob.data_ptr(), int(blob.numel()), offsets.data_ptr(), N, length, length, inflated.data_ptr(),
+                            status.data_ptr(), L.current_stream())
+        L.spnet_png_unfilter(inflated.data_ptr(), length, N, H, W, channels, 0 if first is None else first.data_ptr(),
+                             0 if full is None else full.data_ptr(), status.data_ptr(), L.current_stream())
+    return status
+
+
+def _decode_parsed(infos, sources, device, channels, return_info):
+    import torch
+    if channels not in ("first", "all"):
+        raise ValueError('png: channels is "first" or "all", got %r' % (channels,))
+    if not torch.cuda.is_available():
+        raise RuntimeError("png: decode_png_device decodes on the GPU (there is no CPU decoder here)")
+    device = torch.device("cuda" if device is None else device)
+    N = len(infos)
+    status = np.zeros(N, np.int32)
+    host = [k for k in range(N) if not infos[k].device]
+    host_frames = {k: _host_frame(sources[k], channels) for k in host}          # raises what the default path raises
+
+    def shape_of(k):
+        if k in host_frames:
+            return host_frames[k].shape
+        return (infos[k].height, infos[k].width) + ((infos[k].channels,) if channels == "all" else ())
+
+    if N == 0:
+        out = torch.empty((0, 0, 0) if channels == "first" else (0, 0, 0, 0), dtype=torch.uint8, device=device)
+        return (out, status, []) if return_info else out
+    shape = shape_of(0)
+    for k in range(1, N):
+        if shape_of(k) != shape:
+            name = sources[k] if isinstance(sources[k], (str, os.PathLike)) else "file %d" % k
+            raise ValueError("png: %s is %s, the files before it are %s (one call decodes files of one size)"
+                             % (name, "x".join(str(v) for v in shape_of(k)), "x".join(str(v) for v in shape)))
+    out = torch.empty((N,) + tuple(shape), dtype=torch.uint8, device=device)
+    H, W = int(shape[0]), int(shape[1])
+    groups = {}                                  # bytes per pixel -> files: one pair of launches each
+    for k in range(N):
+        if infos[k].device:
+            groups.setdefault(infos[k].channels, []).append(k)
+    pending = []
+    for bpp, idx in groups.items():
+        n = len(idx)
+        sizes = np.array([len(infos[k].zstream) for k in idx], np.int64)
+        # one pinned upload: the offsets (64-bit, relative to the start of the streams) first, then the streams
+        head = 8 * (n + 1)
+        staging = torch.empty((head + int(sizes.sum()),), dtype=torch.uint8).pin_memory()
+        buf = staging.numpy()
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(sizes, out=offsets[1:])
+        buf[:head] = offsets.view(np.uint8)
+        for j, k in enumerate(idx):
+            buf[head + int(offsets[j]):head + int(offsets[j + 1])] = np.frombuffer(infos[k].zstream, np.uint8)
+        dev = staging.to(device, non_blocking=True)
+        whole = n == N
+        if channels == "first":
+            first = out if whole else torch.empty((n, H, W), dtype=torch.uint8, device=device)
+            st = inflate_unfilter_device(dev[head:], dev[:head].view(torch.int64), n, H, W, bpp, first=first)
+            got = first
+        else:
+            full = out if whole else torch.empty((n, H, W, bpp), dtype=torch.uint8, device=device)
+            st = inflate_unfilter_device(dev[head:], dev[:head].view(torch.int64), n, H, W, bpp, full=full)
+            got = full
+        pending.append((idx, st, got, whole, staging))
+    for idx, st, got, whole, _ in pending:
+        status[idx] = st.cpu().numpy()           # the D2H copy of the status: the only synchronisation
+        if not whole:
+            out[torch.as_tensor(idx, device=device)] = got
+    failed = [k for k in range(N) if status[k] != 0]
+    for k in failed:
+        host_frames[k] = _host_frame(sources[k], channels)      # a corrupt file raises here what it raises today
+        if host_frames[k].shape != tuple(shape):
+            raise ValueError("png: file %d decodes to %s on the host, %s was expected" % (k, host_frames[k].shape, shape))
+    fallback = sorted(host_frames)
+    if fallback:
+        up = torch.from_numpy(np.stack([host_frames[k] for k in fallback])).to(device)
+        out[torch.as_tensor(fallback, device=device)] = up
+    return (out, status, fallback) if return_info else out
+
+
+def decode_png_device(datas, device=None, channels="first", return_info=False, threads=MAX_THREADS):
+    """PNG files (a list of bytes) -> a uint8 DEVICE tensor [N,H,W] holding channel 0 of every pixel (what
+    utils._load_one(..., as_uint8=True) keeps: the grey level, or R), or [N,H,W,C] with channels="all".  The compressed
+    bytes are uploaded as they are and inflated and unfiltered on the GPU.  Files the device does not take (see parse_png)
+    and files it rejects (status != 0) are decoded by the default path's Pillow call and uploaded into their place, so the
+    pixels are the default path's in every case and a corrupt file raises what it raises there.  All files of a call
+    have one size (ValueError otherwise).  return_info: also the status array (inflate_core.h's codes, STATUS_NAMES) and
+    the sorted indices of the files the host decoded."""
+    datas = list(datas)
+    if not datas:
+        return _decode_parsed([], [], device, channels, return_info)
+    with ThreadPoolExecutor(max_workers=_pool_size(threads, len(datas))) as pool:      # zlib.crc32 releases the lock
+        infos = list(pool.map(parse_png, datas))
+    return _decode_parsed(infos, datas, device, channels, return_info)
+
+
+def _read_and_parse(path):
+    with open(path, "rb") as f:
+        return parse_png(f.read())
+
+
+def read_png_device(paths, threads=MAX_THREADS, device=None, channels="first", return_info=False):
+    """decode_png_device of files on disk, read and parsed by a thread pool of this process (at most 16 threads; nothing
+    is forked)."""
+    paths = list(paths)
+    if not paths:
+        return _decode_parsed([], [], device, channels, return_info)
+    with ThreadPoolExecutor(max_workers=_pool_size(threads, len(paths))) as pool:
+        infos = list(pool.map(_read_and_parse, paths))
+    return _decode_parsed(infos, paths, device, channels, return_info)

@@ -158,15 +158,25 @@ def _load_one(force_dim, grayscale, filename, as_uint8=False):
     return arr[:, :, 0:1] if grayscale else arr
 
 
-def build_X(total_load, img_file_list, force_dim=224, grayscale=False, as_uint8=False, device_resize=False):
+def build_X(total_load, img_file_list, force_dim=224, grayscale=False, as_uint8=False, device_resize=False,
+            device_decode=False):
     """PNG -> X float32 [N,H,W,C] scaled to [-1,1]; channel 0 only when grayscale (utils.py:325-421).
     as_uint8 (additive, grayscale only): keep the decoded grey levels, uint8 [N,H,W,1]; Model.predict applies the
     same scaling on the device (bit-identical), and the frames cross PCIe as bytes.
     device_resize (additive, with as_uint8): the grey levels are kept at the files' own size and force_dim is left to
-    Model.predict(X, resize=True), which resizes on the device exactly as PIL does here (spnet_amd/resize.py)."""
+    Model.predict(X, resize=True), which resizes on the device exactly as PIL does here (spnet_amd/resize.py).
+    device_decode (additive, with as_uint8; implies device_resize): the files' bytes are uploaded as they are and decoded
+    on the GPU (spnet_amd.png.read_png_device); X is then a uint8 DEVICE tensor [N,h,w,1] at the files' own size, with
+    the same grey levels."""
     print("      Reading images and assigning as input X...")
     if as_uint8 and not grayscale:
         raise ValueError("as_uint8 is for grayscale input (model_type 'big' / 'monolithic')")
+    if device_decode:
+        if not as_uint8:
+            raise ValueError("device_decode needs as_uint8=True (the device decodes to 8-bit grey levels)")
+        from .png import read_png_device
+        X = read_png_device(list(img_file_list[0:total_load])).unsqueeze(-1)
+        return X, tuple(int(v) for v in X.shape[1:])
     if device_resize:
         if not as_uint8:
             raise ValueError("device_resize needs as_uint8=True (the device resizes 8-bit grey levels)")
@@ -196,7 +206,7 @@ def build_X(total_load, img_file_list, force_dim=224, grayscale=False, as_uint8=
 
 
 def build_dataset(path="Train/", load_frac=1.0, set_means_ranges=False, pred_grid=[6, 6, 2], batch_size=None,
-                  shuffle=True):
+                  shuffle=True, device_decode=False):
     """X, Y, img_file_list, pred_shape for one directory of PNG + same-stem CSV (utils.py:425-482)."""
     if cf.model_type == 'simple':
         grayscale, force_dim = False, 224
@@ -220,7 +230,12 @@ def build_dataset(path="Train/", load_frac=1.0, set_means_ranges=False, pred_gri
     print("      Total files = ", total_files, ", going to load total_load = ", total_load)
     Y, pred_shape = build_Y(total_load, meta_file_list, img_file_list, pred_grid=pred_grid,
                             set_means_ranges=set_means_ranges)
-    X, _ = build_X(total_load, img_file_list, force_dim=force_dim, grayscale=grayscale)
+    if device_decode:          # (additive) uint8 device frames at the files' own size: Model.predict(X, resize=True)
+        if not grayscale:
+            raise ValueError("device_decode is for grayscale input (model_type 'big' / 'monolithic')")
+        X, _ = build_X(total_load, img_file_list, force_dim=force_dim, grayscale=True, as_uint8=True, device_decode=True)
+    else:
+        X, _ = build_X(total_load, img_file_list, force_dim=force_dim, grayscale=grayscale)
     return X, Y, img_file_list, pred_shape
 
 

@@ -57,8 +57,12 @@ def fake_stream_data(n_train, n_val, global_batch, pred_grid, seed, warp=False):
 
 def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch_size=32, epochs=30, pred_grid=[6, 6, 2],
                   noaugment=False, log_dir=".", lr_max=4e-5, freeze_fac=0.7, frozen_epochs=4, random_seed=1,
-                  augment_blur=False, bp_real=None, bpmix_prob=0.3, warp=False, fake_stream=None, fake_val=None):
+                  augment_blur=False, bp_real=None, bpmix_prob=0.3, warp=False, fake_stream=None, fake_val=None,
+                  device_decode=False):
     np.random.seed(random_seed)
+    if device_decode and (noaugment or not ((warp and not fake_stream) or bp_real)):
+        raise ValueError("--device_decode decodes the files of --warp (on a data set on disk) and of --bp_real on the GPU: "
+                         "it needs one of them, and not --noaugment")
     # Data parallel (launched by torch.distributed.run): choose this rank's GPU and join the process group before
     # anything touches the device; rank 0 alone logs, validates and writes checkpoints.
     rank, _, world = multi_gpu.parallel.init_distributed()
@@ -93,9 +97,10 @@ def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch
     if not noaugment:
         print("Adding callback for augment on the fly")
         if warp and fresh is not None:      # streamed frames: warped from the device tensors the stream keeps
-            warp_args = dict(warp_source=fresh.warper, warp_targets="device")
+            warp_args = dict(warp_source=fresh.warper, warp_targets="device", device_decode=bool(device_decode))
         else:
-            warp_args = dict(warp=warp, warp_files=list(train_file_list[:X_train.shape[0]]) if warp else None)
+            warp_args = dict(warp=warp, warp_files=list(train_file_list[:X_train.shape[0]]) if warp else None,
+                             device_decode=bool(device_decode))
         callback_list.append(callbacks.AugmentOnTheFly(X_train, Y_train, aug_every=1, seed=random_seed,
                                                        real_blur=augment_blur, bandpass_real=bp_real,
                                                        bpmix_prob=bpmix_prob, pred_grid=pred_grid, **warp_args))
@@ -149,6 +154,10 @@ if __name__ == '__main__':
                         "files of Train/ on disk: the frames are warped at their full size and the targets come from the "
                         "CSV rows -- or --fake_stream, whose full-size frames and label rows stay on the GPU.  Ignored "
                         "with --noaugment")
+    p.add_argument('--device_decode', action='store_true',
+                   help="(additive; needs --warp on a data set on disk, or --bp_real) decode the full-size frames of the warp "
+                        "and the grey real frames of --bp_real on the GPU from the PNG files' bytes instead of with "
+                        "Pillow: the same frames")
     p.add_argument('--fake_stream', type=int, default=None, metavar='N',
                    help="train on N fresh fake-ESPI frames per epoch, generated on the GPU (rounded down to a multiple of "
                         "the global batch); no Train/ or Val/ directory is read")
@@ -172,7 +181,7 @@ if __name__ == '__main__':
                           log_dir=log_dir, lr_max=args.lrmax, freeze_fac=args.freeze_fac,
                           frozen_epochs=args.frozen_epochs, random_seed=args.random_seed,
                           augment_blur=args.augment_blur, bp_real=args.bp_real, bpmix_prob=args.bpmix_prob, warp=args.warp,
-                          fake_stream=args.fake_stream, fake_val=args.fake_val)
+                          fake_stream=args.fake_stream, fake_val=args.fake_val, device_decode=args.device_decode)
 
     if int(os.environ.get("RANK", "0")) == 0:
         print("\n----------------------------\nStarting model evaluation...")

@@ -28,6 +28,10 @@ extern "C" {
  * a_major / b_major: 0 = reduction index contiguous (A[m*lda+k], B[n*ldb+k]),
  *                    1 = output index contiguous    (A[k*lda+m], B[k*ldb+n]).
  * Supported pairs: (0,1) forward, (0,0) dgrad, (1,1) wgrad.
+ * lda / ldb / ldc: row strides in floats, multiples of 4; an operand may be a column block of a wider tensor, and nothing
+ * outside the block is read or written.  A stride below the extent it strides over is refused by every entry point of this
+ * family (hipErrorInvalidValue, nothing launched): ld < K for a K-contiguous operand, lda < M / ldb < N for an
+ * output-contiguous one, ldc < N -- rows would overlap, and workgroups would race on the stores of an overlapping C.
  * split_k: 0 = choose automatically, >1 = that many K slices summed deterministically through
  * `workspace` (>= split_k*M*N floats).  tile (BM x BN): 0 auto (cost model over ids 1-8), 1 128x128, 2 128x64, 3 64x64,
  * 4 32x128, 5 96x96, 6 96x64, 7 64x128, 8 128x96, 9 32x64, 10 32x32 (9 and 10: few-row problems, chosen only through
@@ -133,7 +137,8 @@ int spnet_gemm_f32_batched_splitk(const float* A0, const float* B0, float* C0, c
  * g and the saved pre-normalisation tensor yp while the A tile is staged: dY never makes a pass of its own.
  * coef = [a | b | c], cld floats each (from spnet_bn_bwd_coeffs*; zero beyond channel K-1; cld % 32 == 0,
  * cld >= K rounded up to 32).  B is W^T in the output-major form (spnet_transpose_batched).  dy_out (or NULL)
- * receives dY once, for the layer's weight-gradient GEMM. */
+ * receives dY once, as a dense [M][K] matrix whatever lda (the row stride of g and yp), for the layer's weight-gradient
+ * GEMM. */
 int spnet_gemm_f32_bnblend(const float* g, const float* yp, const float* coef, int cld, int lda, const float* B,
                            int ldb, float* C, int ldc, int M, int N, int K, int tile, float* dy_out, void* stream);
 

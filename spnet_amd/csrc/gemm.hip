@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256, (AX && BM * BN <= 96 * 64) ? 3 : 2) void gemm_
       stA.xform_relu(a, c);
     } else if constexpr (AX) {
       stA.xform(a, b, c, wreg);
-      if (dy_out && ((k0 - kbeg) / BK) % tiles_n == tn) stA.store_global(dy_out, lda, m0, M, k0, kend, tid);
+      if (dy_out && ((k0 - kbeg) / BK) % tiles_n == tn) stA.store_global(dy_out, K, m0, M, k0, kend, tid);      // dense [M][K], whatever lda
     }
   };
   if (nt > 0) {

@@ -141,6 +141,10 @@ static GemmPlan gemm_plan(const GemmProblem& p) {
   if (M <= 0 || N <= 0 || K <= 0 || (p.lda & 3) || (p.ldb & 3) || (N & 3) || (p.ldc & 3) || gemm_misaligned(p.A, p.B, p.C)) return pl;
   if ((p.a_major == GEMM_K_MAJOR || p.b_major == GEMM_K_MAJOR) && (K & 3)) return pl;      // float4 fetches along the contiguous axis
   if (p.a_major == GEMM_OUT_MAJOR && (M & 3)) return pl;
+  // a row stride below the extent it strides over: rows overlap, and for ldc < N workgroups race on their stores
+  // (gathered A: lda is the pixel stride of the NHWC tensor, K spans KH*KW pixels -- spnet_conv_gemm_f32 checks ldx >= C)
+  if (!p.cg && p.lda < (p.a_major == GEMM_K_MAJOR ? K : M)) return pl;
+  if (p.ldb < (p.b_major == GEMM_K_MAJOR ? K : N) || p.ldc < N) return pl;
   if (p.xf) {   // blended A operand: second tensor + [a|b|c] coefficients, zero-padded to whole K tiles; forward form, no K split
     if ((p.xf != 1 && p.xf != 2) || !fwd_form || p.batch || (p.xf == 1 && !p.X2) || !p.coef ||
         gemm_misaligned(p.X2, p.coef, p.dy_out) || (p.cld & 3) || (p.xf == 2 && p.dy_out) || p.cld < gemm_cdiv(K, SP_BK) * SP_BK)

@@ -107,6 +107,7 @@ struct TileStage {
     }
   }
   // The (blended) tile as it stands in v[] -> out[row*ld + k] (K-major operands): only real rows / reduction steps.
+  // ld is the row stride of OUT, not the operand's: off[] carries the operand's stride and cannot serve here.
   __device__ __forceinline__ void store_global(float* __restrict__ out, int ld, int r0, int R, int k0, int kend,
                                                int tid) const {
     static_assert(MAJ == SP_K_MAJOR, "K-major operands only");
@@ -114,9 +115,8 @@ struct TileStage {
     for (int i = 0; i < NV; ++i) {
       const int f = tid + i * 256;
       const int r = f / (BK / 4), kq = f % (BK / 4);
-      // off[i] already is (row clamped into range)*ld + kq*4: a clamped (duplicate) row is simply not written
       if (((TOTAL % 256 == 0) || f < TOTAL) && r0 + r < R && k0 + kq * 4 < kend)
-        *reinterpret_cast<float4*>(out + off[i] + k0) = v[i];
+        *reinterpret_cast<float4*>(out + (long)(r0 + r) * ld + k0 + kq * 4) = v[i];
     }
   }
   // Gathered tile: slot i comes from base[offs[i] + shift], or is zero (and reads base[0]) when bit i of

@@ -1,7 +1,8 @@
 """Per-kernel parity: every HIP kernel, called through the C ABI, against the CPU oracle on the same
 seeded inputs.  fp32 tolerances are written next to each check (the kernels and the oracle sum in
 different orders, so agreement is to rounding, not bitwise, except where noted).
-The stem head, loss / head and augmentation kernels are pinned one by one in tests/test_small_kernels_gpu.py."""
+The stem head, loss / head and augmentation kernels are pinned one by one in tests/test_small_kernels_gpu.py.
+The GEMM family on strided operands, against exact integer products: tests/test_gemm_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -604,6 +605,7 @@ def test_reduce_rows_batched(L):
 
 
 def test_gemm_rejects_misaligned(L):
+    import ctypes
     a = torch.zeros(64, 6, device="cuda")
     with pytest.raises(L.HipError):
         L.spnet_gemm_f32(a.data_ptr(), 0, 6, a.data_ptr(), 1, 6, a.data_ptr(), 6, 8, 6, 6, 0, None, 0, None, 0, st())
@@ -615,6 +617,7 @@ def test_gemm_rejects_misaligned(L):
     ws = torch.empty(4 * 32 * 32, device="cuda")
     off = torch.zeros(3, dtype=torch.int64, device="cuda")
     zp, op = z.data_ptr(), out.data_ptr()
+    sr = ctypes.c_int(0)
     conv = lambda ldy=32, C=32, stride=1: L.spnet_conv_gemm_f32(zp, C, zp, op, ldy, 1, 4, 4, C, 32, 3, 3, stride, 1, None, 0, None, None, st())
     table = [
         ("batched, ldc != N under a K split", lambda: L.spnet_gemm_f32_batched_splitk(zp, zp, op, off.data_ptr(), 1, 1, 32, 1, 32, 36, 32, 32, 32, 0, 2, ws.data_ptr(), ws.numel(), st())),
@@ -624,6 +627,16 @@ def test_gemm_rejects_misaligned(L):
         ("conv_gemm, stride 3", lambda: conv(stride=3)),
         ("conv_gemm, ldy < Cout", lambda: conv(ldy=28)),
         ("accumulate, bad tile id", lambda: L.spnet_gemm_f32_accumulate(zp, 0, 32, zp, 0, 32, op, 32, 32, 32, 32, 11, st())),
+        # a row stride below the extent it strides over (rows would overlap; for ldc < N workgroups would race on their stores)
+        ("K-major A, lda < K", lambda: L.spnet_gemm_f32(zp, 0, 28, zp, 1, 32, op, 32, 32, 32, 32, 1, None, 0, None, 0, st())),
+        ("K-major B, ldb < K", lambda: L.spnet_gemm_f32(zp, 0, 32, zp, 0, 28, op, 32, 32, 32, 32, 1, None, 0, None, 0, st())),
+        ("out-major A, lda < M", lambda: L.spnet_gemm_f32(zp, 1, 28, zp, 1, 32, op, 32, 32, 32, 32, 1, None, 0, None, 0, st())),
+        ("out-major B, ldb < N", lambda: L.spnet_gemm_f32(zp, 0, 32, zp, 1, 28, op, 32, 32, 32, 32, 1, None, 0, None, 0, st())),
+        ("ldc < N", lambda: L.spnet_gemm_f32(zp, 0, 32, zp, 1, 32, op, 28, 32, 32, 32, 1, None, 0, None, 0, st())),
+        ("accumulate, ldc < N", lambda: L.spnet_gemm_f32_accumulate(zp, 0, 32, zp, 1, 32, op, 28, 32, 32, 32, 0, st())),
+        ("batched, lda < M", lambda: L.spnet_gemm_f32_batched(zp, zp, op, off.data_ptr(), 1, 1, 28, 1, 32, 32, 32, 32, 32, 0, st())),
+        ("bnblend, lda < K", lambda: L.spnet_gemm_f32_bnblend(zp, zp, zp, 32, 28, zp, 32, op, 32, 32, 32, 32, 0, None, st())),
+        ("colstats, ldb = 0", lambda: L.spnet_gemm_f32_colstats(zp, 0, 32, zp, 1, 0, op, 32, 32, 32, 32, 0, zp, ctypes.addressof(sr), st())),
     ]
     wrong = []
     for name, call in table:

@@ -180,7 +180,8 @@ long spnet_dwconv3x3_strided_ws(int B, int H, int W, int C, int stride);
 int spnet_dwconv3x3_strided(int op, const float* a, const float* b, float* out, int B, int H, int W, int C, int stride,
                             float* workspace, void* stream);
 /* LDS-tiled forms used by the engine: forward, and the FUSED backward (data + weight gradient in one
- * pass over x and dy).  workspace: spnet_dwconv3x3_tiled_bwd_ws(B,H,W,C) floats. */
+ * pass over x and dy).  workspace: spnet_dwconv3x3_tiled_bwd_ws(B,H,W,C) floats.  Every tiled and streaming entry point
+ * returns hipErrorInvalidValue, and launches nothing, for C % 4 != 0 or B, H or W < 1. */
 int spnet_dwconv3x3_tiled_fwd(const float* x, const float* w, float* y, int B, int H, int W, int C,
                               int relu_in, const float* in_scale, const float* in_shift, void* stream);
 /* The same with the PRODUCER BatchNorm's training-forward finalize folded into the prologue (one dependent launch less
@@ -313,7 +314,9 @@ int spnet_maxpool3x3s2_bwd(const float* dy, const uint32_t* idx4, float* dx, int
 /* The same, also emitting the backward sums (sum dx, sum dx*xhat) of the BatchNorm whose un-materialised output was
  * pooled -- yp = its pre-normalisation tensor [B,H,W,C], mean / invstd as saved by its forward -- as
  * partial[rows][2][C], rows = spnet_maxpool3x3s2_bwd_rows(B,H,W,C,max_rows) <= max_rows: the gradient path of block{2,3,4,13}_pool +
- * block*_sepconv2_bn in keras.applications.Xception (call site spnet/models.py:357-359) without a reduction pass. */
+ * block*_sepconv2_bn in keras.applications.Xception (call site spnet/models.py:357-359) without a reduction pass.
+ * `rows` may be any count from 1 to that answer (anything else: hipErrorInvalidValue).  Pixel r = (b*H + h)*W + w
+ * belongs to partial row (r / 32) % rows: a row takes 32 consecutive pixels, then strides by rows * 32. */
 long spnet_maxpool3x3s2_bwd_rows(int B, int H, int W, int C, int max_rows);
 int spnet_maxpool3x3s2_bwd_bnsums(const float* dy, const uint32_t* idx4, float* dx, int B, int H, int W, int C,
                                   const float* yp, const float* mean, const float* invstd, float* partial, int rows,

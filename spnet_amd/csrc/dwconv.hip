@@ -983,7 +983,7 @@ static bool dw_planes_ok(const void* p, int B, int H, int W, int C) {
 static int dw_tiled_fwd(const float* x, const float* w, float* y, int B, int H, int W, int C, int relu_in,
                         const float* in_scale, const float* in_shift, const DwBnFinalize& fin, void* stream,
                         unsigned short* planes = nullptr) {
-  if (C & 3) return (int)hipErrorInvalidValue;
+  if ((C & 3) || B < 1 || H < 1 || W < 1) return (int)hipErrorInvalidValue;
   if (planes && !dw_planes_ok(planes, B, H, W, C)) return (int)hipErrorInvalidValue;
   const long plane_stride = x3t_plane_elems((long)B * H * W, C);
   const DwGeom g = dw_geom(B, H, W, C);
@@ -1181,7 +1181,7 @@ extern "C" int spnet_dwconv3x3_tiled_bwd(const float* dy, const float* x_fwd, co
                                          void* stream) {
   if (bn_partial && (!bn_mean || !bn_invstd)) return (int)hipErrorInvalidValue;
   if (bn_x && !bn_partial) return (int)hipErrorInvalidValue;
-  if (C & 3) return (int)hipErrorInvalidValue;
+  if ((C & 3) || B < 1 || H < 1 || W < 1) return (int)hipErrorInvalidValue;
   const DwGeom g = dw_geom(B, H, W, C);
   if (g.cfg == 1)
     hipLaunchKernelGGL((dw3x3_tile_bwd_kernel<16, 8, 6>), dim3((unsigned)g.nblk), dim3(256), g.lds_bwd,

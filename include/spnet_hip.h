@@ -663,6 +663,29 @@ int spnet_png_inflate(const unsigned char* blob, long blob_bytes, const long lon
 int spnet_png_unfilter(const unsigned char* inflated, long in_stride, int N, int H, int W, int channels, unsigned char* first,
                        unsigned char* all, int* status, void* stream);
 
+/* ---- prediction overlays (csrc/overlay.hip): the drawing of show_pred_ellipses (spnet/utils.py:67-137: cv2.ellipse,
+ *      cv2.putText per frame) for frames that are already in device memory ---------------------------------------------- */
+/* frames: uint8 [N][H][W] (channels 1: grey, replicated to R = G = B) or [N][H][W][3] (channels 3); out: uint8
+ * [N][H][W][3], a different buffer.  H, W 1 .. 4096.  spnet_amd/overlay.py is the host side and documents the rule.
+ *   frame_start int32 [N+1]   commands of frame n are cmd[frame_start[n] .. frame_start[n+1]), painted in that order
+ *   cmd         int32 [n_cmd][12]   kind (0 outline, 1 mask blit), colour r | g << 8 | b << 16, box x0, y0, x1, y1 (pixels,
+ *                             x1 / y1 exclusive; nothing outside box and frame is touched; an empty box paints nothing),
+ *                             data, mask x, mask y, mask width, mask height, 0
+ *   verts       int32 [n_verts][2]  outline: data = index of the first of its 72 vertices (x, y in 1/16 pixel, pixel (x, y)
+ *                             has its centre at (16 x + 8, 16 y + 8)); closed polygon, every edge a segment of half width
+ *                             24/16 pixel with round ends, in exact integer arithmetic; the pixel takes the colour.  Edges
+ *                             must be shorter than 2^13 units per axis (the host gives longer ones an empty box).
+ *   masks       uint8 [mask_bytes]  blit: data = byte offset of a width x height coverage mask whose top-left pixel is at
+ *                             (mask x, mask y), which may lie outside the frame; per channel t = dst * (255 - m) + ink * m
+ *                             + 128, out = ((t >> 8) + t) >> 8.
+ * A command whose data points outside verts / masks is skipped; no byte outside the arrays as sized here is read, none
+ * outside out written.  One launch (per 65,535 frames), one workgroup per 64 x 16 tile; 16-byte accesses on untouched tiles
+ * when W % 16 == 0 and frames / out are 16-byte aligned (no alignment is required).  N == 0: nothing to do, success.
+ * hipErrorInvalidValue (nothing launched) for a size outside these limits, a NULL pointer or a misaligned int32 array. */
+int spnet_draw_overlays(const unsigned char* frames, int N, int H, int W, int channels, const int* frame_start, const int* cmd,
+                        int n_cmd, const int* verts, int n_verts, const unsigned char* masks, long mask_bytes,
+                        unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -272,13 +272,24 @@ def draw_ellipse(img, center, axes, angle, startAngle=0, endAngle=360, color=(0,
 
 
 def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_extra=None, out_csv=None,
-                       show_true=True, verbosity=0, png="host", png_chunk=64):
+                       show_true=True, verbosity=0, png="host", png_chunk=64, draw="host", device_decode=False):
     """Overlay PNGs steelpan_pred_%05d.png and the zooniverse-style CSV (cx,cy,file,rings,a,b,angle)
     from de-normalised true / predicted grids (utils.py:67-137).  png = "host": every overlay is saved by Pillow as it is
     drawn; "device" (additive): the drawn RGB overlays are collected png_chunk at a time, uploaded, encoded on the GPU
-    (spnet_amd.png) and written by a thread pool -- the same pixels, file names and CSV rows, other file bytes."""
+    (spnet_amd.png) and written by a thread pool -- the same pixels, file names and CSV rows, other file bytes.
+    draw = "host": Pillow draws; "device" (additive): the loop only plans (spnet_amd.overlay.plan_overlays), the frames
+    are loaded png_chunk at a time -- by the device decoder with device_decode, else by Pillow and one upload per chunk --
+    and one HIP launch per chunk draws them: the same file names and CSV rows, the same pixels away from outline edges
+    (spnet_amd/overlay.py has the rule)."""
     if png not in ("host", "device"):
         raise ValueError('show_pred_ellipses: png is "host" or "device", got %r' % (png,))
+    if draw not in ("host", "device"):
+        raise ValueError('show_pred_ellipses: draw is "host" or "device", got %r' % (draw,))
+    if draw == "device":
+        return _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk,
+                                          device_decode)
+    if device_decode:
+        raise ValueError('show_pred_ellipses: device_decode loads the frames for draw="device"')
     m = Yt.shape[0]
     num_draw = min(num_draw, m, len(file_list))
     if out_csv is not None:
@@ -326,3 +337,62 @@ def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_ex
             with open(out_csv, "a") as f:
                 f.write(csv_str)
     flush()
+
+
+def _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk, device_decode):
+    """show_pred_ellipses(draw="device"): runs of frames of one size, at most png_chunk long, are loaded, planned, drawn
+    by csrc/overlay.hip and written; the CSV rows of a chunk are appended once its files are written."""
+    import torch
+    from . import overlay
+    if not torch.cuda.is_available():
+        raise RuntimeError('show_pred_ellipses: draw="device" draws on the GPU (no CPU fallback)')
+    num_draw = min(num_draw, Yt.shape[0], len(file_list))
+    if out_csv is not None:
+        open(out_csv, "w").close()
+    png_chunk = max(int(png_chunk), 1)
+
+    def finish(lo, frames):
+        """frames: uint8 device tensor [n,H,W] (grey) or [n,H,W,3] of files lo .. lo+n-1, one size."""
+        n = int(frames.shape[0])
+        plan = overlay.plan_overlays(Yt[lo:lo + n], Yp[lo:lo + n], file_list[lo:lo + n], show_true=show_true,
+                                     size=tuple(int(v) for v in frames.shape[1:3]), with_csv=out_csv is not None)
+        drawn = overlay.draw_overlays_device(frames, plan)
+        paths = [log_dir + '/steelpan_pred_' + str(lo + k).zfill(5) + '.png' for k in range(n)]
+        if png == "device":
+            from .png import write_png_device
+            write_png_device(drawn, paths)
+        else:
+            host = drawn.cpu().numpy()
+            for k in range(n):
+                Image.fromarray(host[k]).save(paths[k])
+        if out_csv is not None:
+            with open(out_csv, "a") as f:
+                f.write(''.join(plan.csv))
+
+    def decode_on_device(names):
+        """uint8 device frames [n,H,W] | [n,H,W,3] equal to Image.open(f).convert("RGB") of every file, or None where the
+        device decoder does not give that for this chunk (mixed sizes or kinds, a palette or 16-bit file): Pillow then."""
+        from .png import read_png_device
+        try:
+            frames, _, fallback = read_png_device(names, channels="all", return_info=True)
+        except ValueError:
+            return None
+        if fallback:
+            return None
+        c = int(frames.shape[3])                    # grey, grey + alpha, RGB, RGBA: convert("RGB") drops the alpha
+        return frames[..., 0] if c <= 2 else frames[..., :3]
+
+    for lo in range(0, num_draw, png_chunk):
+        names = list(file_list[lo:min(lo + png_chunk, num_draw)])
+        frames = decode_on_device(names) if device_decode else None
+        if frames is not None:
+            finish(lo, frames)
+            continue
+        loaded = [np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8) for f in names]
+        k = 0
+        while k < len(loaded):                      # runs of one size: frames of mixed size are chunked by size
+            e = k + 1
+            while e < len(loaded) and loaded[e].shape == loaded[k].shape:
+                e += 1
+            finish(lo + k, torch.from_numpy(np.stack(loaded[k:e])).cuda())
+            k = e

@@ -73,14 +73,16 @@ def _planes_on_device(planes):
     return X
 
 
-def augment_data(path='Train', n_augs=39, seed=0, chunk=256, device_png=False, device_decode=False):
+def augment_data(path='Train', n_augs=39, seed=0, chunk=256, device_png=False, device_decode=False, device_png_lz=False):
     """Writes n_augs warped copies of every PNG + CSV pair of `path`; returns [(prefix, params)] of the files written,
     params = dict(flip, angle, xt, yt) with xt = yt = None where no shift was drawn.  chunk: planes warped per launch.
     device_png: the warped batch is encoded where DeviceWarper leaves it (spnet_amd.png) instead of copied out for Pillow:
-    the same pixels and modes, other file bytes.
+    the same pixels and modes, other file bytes.  device_png_lz: the same (it implies device_png), with the encoder's LZ77
+    stage on.
     device_decode: the originals are decoded on the GPU from the files' bytes (spnet_amd.png.read_png_device) into the
     tensor DeviceWarper warps, instead of by Pillow and uploaded: the same planes, the same files written."""
     import torch
+    device_png = device_png or device_png_lz
     if device_png:
         from spnet_amd.png import write_png_device
     from spnet_amd import augmentation as A
@@ -138,7 +140,7 @@ def augment_data(path='Train', n_augs=39, seed=0, chunk=256, device_png=False, d
         for c, (first, paths) in held.items():          # the warped planes stay in HBM; [n][c][H][W] -> [n][H][W][c]
             idx = torch.tensor(first, device=out.device)[:, None] + torch.arange(c, device=out.device)[None, :]
             frames = out[idx] if c > 1 else out[idx[:, 0]]
-            write_png_device(frames.permute(0, 2, 3, 1).contiguous() if c > 1 else frames, paths)
+            write_png_device(frames.permute(0, 2, 3, 1).contiguous() if c > 1 else frames, paths, lz77=device_png_lz)
         jobs.clear()
         planes.clear()
 
@@ -176,8 +178,10 @@ if __name__ == "__main__":
     parser.add_argument('--seed', type=int, help='seed of the per-(file, augmentation) random streams', default=0)
     parser.add_argument('--device_png', action='store_true',
                         help='(additive) encode the PNG files on the GPU (Huffman-only deflate): same pixels, other file bytes')
+    parser.add_argument('--device_png_lz', action='store_true',
+                        help="(additive) --device_png with the encoder's LZ77 stage: smaller files where pixels repeat")
     parser.add_argument('--device_decode', action='store_true',
                         help='(additive) decode the original PNG files on the GPU (inflate + unfilter): same planes, same output')
     args = parser.parse_args()
     augment_data(path=args.datapath, n_augs=args.naugs, seed=args.seed, device_png=args.device_png,
-                 device_decode=args.device_decode)
+                 device_decode=args.device_decode, device_png_lz=args.device_png_lz)

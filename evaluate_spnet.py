@@ -13,7 +13,7 @@ import spnet.config as cf
 
 def evaluate_network(model=None, weights_file="", datapath="Test/", fraction=1.0, log_dir="", batch_size=32,
                      pred_grid=[6, 6, 2], set_means_ranges=True, device_png=False, device_decode=False,
-                     device_overlay=False):
+                     device_overlay=False, device_png_lz=False):
     np.random.seed(1)
     print("Getting data..., fraction = ", fraction)
     X_test, Y_test, test_file_list, pred_shape = build_dataset(
@@ -56,7 +56,8 @@ def evaluate_network(model=None, weights_file="", datapath="Test/", fraction=1.0
     make_sure_path_exists(log_dir)
     print("    Drawing sample ellipse images...")
     show_pred_ellipses(Yt, Yp, test_file_list, num_draw=m, log_dir=log_dir, out_csv=log_dir + 'hawley_spnet.csv',
-                       png="device" if device_png else "host", draw="device" if device_overlay else "host",
+                       png="device-lz" if device_png_lz else "device" if device_png else "host",
+                       draw="device" if device_overlay else "host",
                        device_decode=bool(device_decode and device_overlay))
     return model
 
@@ -77,6 +78,8 @@ if __name__ == '__main__':
     p.add_argument('--device_png', action='store_true',
                    help="(additive) encode the overlay PNG files on the GPU (Huffman-only deflate): the same pixels, "
                         "other file bytes")
+    p.add_argument('--device_png_lz', action='store_true',
+                   help="(additive) --device_png with the encoder's LZ77 stage: smaller overlay files")
     p.add_argument('--device_overlay', action='store_true',
                    help="(additive) draw the overlays (outlines, ring counts, file name) on the GPU: the same CSV and file "
                         "names, the same pixels away from outline edges; with --device_decode the frames are decoded there "
@@ -87,7 +90,8 @@ if __name__ == '__main__':
             setattr(cf, attr, val)
     model = evaluate_network(weights_file=args.weights, datapath=args.datapath + '/', fraction=args.fraction,
                              log_dir=args.logdir, batch_size=args.batch_size, device_png=args.device_png,
-                             device_decode=args.device_decode, device_overlay=args.device_overlay)
+                             device_decode=args.device_decode, device_overlay=args.device_overlay,
+                             device_png_lz=args.device_png_lz)
     weights2name = "eval_end_weights.hdf5"
     print("Saving model to", weights2name)
     model.save_weights(weights2name)

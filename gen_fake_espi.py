@@ -44,15 +44,17 @@ def split_dirs(n, everything):
 
 
 def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_range=(1, 7), bp_real=None, bp_path=None,
-                host_params=False, chunk=256, device="cuda:0", threads=None, device_png=False):
+                host_params=False, chunk=256, device="cuda:0", threads=None, device_png=False, device_png_lz=False):
     """Writes the data set; returns the label rows of every frame, in frame order.  device_png: the frames are encoded where
-    they are (spnet_amd.png.write_png_device) and only the compressed bytes cross to the host."""
+    they are (spnet_amd.png.write_png_device) and only the compressed bytes cross to the host.  device_png_lz: the same (it
+    implies device_png), with the encoder's LZ77 stage on."""
     import torch
     from spnet_amd import fake_espi as F
     if (bp_real is None) != (bp_path is None):
         raise ValueError("gen_fake_espi: --bp_real and --bp_path go together")
     if not torch.cuda.is_available():
         raise RuntimeError("gen_fake_espi: the frames are generated on the GPU (no CPU fallback)")
+    device_png = device_png or device_png_lz
     n = int(numframes)
     sub = split_dirs(n, everything)
     for root in (datapath,) + ((bp_path,) if bp_path else ()):
@@ -72,7 +74,7 @@ def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_ran
         stems = [os.path.join(root, sub[i], "steelpan_" + str(i).zfill(7) + suffix) for i in range(lo, hi)]
         if device_png:
             from spnet_amd.png import write_png_device
-            write_png_device(frames_dev, [st + ".png" for st in stems], pool=pool)
+            write_png_device(frames_dev, [st + ".png" for st in stems], pool=pool, lz77=device_png_lz)
             return [pool.submit(_write_csv, st, r) for st, r in zip(stems, rows)]
         frames = frames_dev.cpu().numpy()
         return [pool.submit(_write_pair, st, frames[k], rows[k]) for k, st in enumerate(stems)]
@@ -113,7 +115,9 @@ if __name__ == "__main__":
                    help="draw the parameters on the host in the reference's RNG order instead of on the device")
     p.add_argument('--device_png', action='store_true',
                    help="(additive) encode the PNG files on the GPU (Huffman-only deflate): the same pixels, other file bytes")
+    p.add_argument('--device_png_lz', action='store_true',
+                   help="(additive) --device_png with the encoder's LZ77 stage: smaller files where pixels repeat")
     args = p.parse_args()
     gen_dataset(datapath=args.datapath, numframes=args.numframes, everything=args.all, seed=args.seed,
                 count_range=tuple(args.count_range), bp_real=args.bp_real, bp_path=args.bp_path, host_params=args.host_params,
-                device_png=args.device_png)
+                device_png=args.device_png, device_png_lz=args.device_png_lz)

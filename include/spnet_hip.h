@@ -638,6 +638,22 @@ int spnet_png_pack(const unsigned char* src, int N, int H, int W, int channels, 
                    const int* header_bits, const long long* offsets, const uint32_t* adler, unsigned char* out, long out_bytes,
                    void* stream);
 
+/* The LZ77 stage (csrc/png_lz.hip; opt-in, lz77=True of spnet_amd/png.py): the same frames, stream and limits, one workgroup
+ * per frame, tokens (literals and (length 3 .. 258, distance 1 .. 32768) matches) by the fixed rule in that file's header --
+ * a function of the stream alone.  No HBM workspace: the packer recomputes the tokens.
+ *   spnet_png_lz_scan  lhist [N][286] = counts of the literal / length symbols of the frame's tokens (symbol 256, the end of
+ *                      block, counted once), dhist [N][30] = counts of the distance symbols.  Both 4-byte aligned.
+ *   spnet_png_lz_pack  as spnet_png_pack (same out / out_bytes / offsets / adler contract, same zlib header bytes), with both
+ *                      alphabets: lcodes [N][286] and dcodes [N][30] (code | length << 16, lengths 0 .. 15), header [N][72]
+ *                      (real HLIT / HDIST; header_bits [N] <= 2304).  A frame with header_bits[n] < 0 is SKIPPED: its slot
+ *                      is left to spnet_png_pack, which may share words with its neighbours' (both merge with OR).  Slot
+ *                      size: 2 + ceil((header_bits + sum lhist*length + sum dhist*length + the symbols' extra bits) / 8) + 4. */
+int spnet_png_lz_scan(const unsigned char* src, int N, int H, int W, int channels, uint32_t* lhist, uint32_t* dhist,
+                      void* stream);
+int spnet_png_lz_pack(const unsigned char* src, int N, int H, int W, int channels, const uint32_t* lcodes,
+                      const uint32_t* dcodes, const uint32_t* header, const int* header_bits, const long long* offsets,
+                      const uint32_t* adler, unsigned char* out, long out_bytes, void* stream);
+
 /* ---- PNG input (csrc/png_decode.hip, csrc/inflate_core.h): the decoder behind Image.open(...).convert("RGB")
  *      (spnet/utils.py:325-345) for files whose bytes are uploaded as they sit on disk ---------------------------------- */
 /* One wave per file; spnet_amd/png.py is the host side (container, CRCs, classification, host fallback).  status [N]

@@ -17,7 +17,7 @@ default_image_dir = '/home/shawley/datasets/zooniverse_steelpan/'
 
 def predict_network(weights_file="spnet.model", datapath=default_image_dir, fraction=1.0, log_dir='logs/Predicting/',
                     batch_size=16, model=None, X_pred='', u8_frames=False, device_resize=False, device_png=False,
-                    device_decode=False, device_overlay=False):
+                    device_decode=False, device_overlay=False, device_png_lz=False):
     img_file_list = []
     resize = False
     if isinstance(X_pred, str) and X_pred == '':
@@ -72,7 +72,7 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
     Yp = denorm_Y(Y_pred)
     if img_file_list:
         show_pred_ellipses(Yp, Yp, img_file_list, num_draw=m, log_dir=log_dir, out_csv=log_dir + 'hawley_spnet.csv',
-                           show_true=False, png="device" if device_png else "host",
+                           show_true=False, png="device-lz" if device_png_lz else "device" if device_png else "host",
                            draw="device" if device_overlay else "host", device_decode=bool(device_decode and device_overlay))
     return model
 
@@ -100,6 +100,8 @@ if __name__ == '__main__':
     p.add_argument('--device_png', action='store_true',
                    help="(additive) encode the overlay PNG files on the GPU (Huffman-only deflate): the same pixels, "
                         "other file bytes")
+    p.add_argument('--device_png_lz', action='store_true',
+                   help="(additive) --device_png with the encoder's LZ77 stage: smaller overlay files")
     p.add_argument('--device_overlay', action='store_true',
                    help="(additive) draw the overlays (outlines, ring counts, file name) on the GPU: the same CSV and file "
                         "names, the same pixels away from outline edges; with --device_decode the frames are decoded there "
@@ -110,4 +112,5 @@ if __name__ == '__main__':
             setattr(cf, attr, val)
     predict_network(weights_file=args.weights, datapath=args.datapath, fraction=args.fraction, log_dir=args.logdir,
                     batch_size=args.batch_size, u8_frames=args.u8_frames, device_resize=args.device_resize,
-                    device_png=args.device_png, device_decode=args.device_decode, device_overlay=args.device_overlay)
+                    device_png=args.device_png, device_decode=args.device_decode, device_overlay=args.device_overlay,
+                    device_png_lz=args.device_png_lz)

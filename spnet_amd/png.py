@@ -3,7 +3,13 @@ one dynamic-Huffman deflate block of literals, the host supplies what is tiny (c
 the streams as PNG.  Additive and opt-in (--device_png of gen_fake_espi.py, augment_preproc.py, predict_spnet.py and
 evaluate_spnet.py); the default writers are Pillow's.
 
-There is no LZ77 stage: a frame of sensor noise comes out close to Pillow's size, a smooth image several times larger.
+By default there is no LZ77 stage: a frame of sensor noise comes out close to Pillow's size, a smooth image several times
+larger.  lz77=True (--device_png_lz; csrc/png_lz.hip) adds one: spnet_png_lz_scan cuts every frame's stream into literals and
+(length, distance) matches by a fixed rule (a function of the stream alone, written down in that file's header and in
+DESIGN.md) and returns the literal/length and distance histograms; the host builds both codes, the header with real HLIT /
+HDIST and the exact size, and KEEPS, PER FRAME, THE SMALLER of that stream and the literal-only one (equal: literal-only) --
+both sizes are known before anything is packed.  spnet_png_lz_pack writes the frames that took LZ, spnet_png_pack the rest,
+into the same zeroed buffer.  lz77=False writes the bytes it always wrote.
 
 Per batch: spnet_png_hist -> D2H of the histograms -> code lengths / header / exact sizes on the host -> one H2D of the plan
 -> spnet_png_pack -> D2H of the compressed bytes (each stream ends in its Adler-32).  The two D2H copies are the only
@@ -36,6 +42,11 @@ import numpy as np
 NSYM = 257                      # 256 literals + end of block
 EOB = 256
 HEADER_WORDS = 64               # spnet_png_pack's header stride: 2048 bits >= 3 + 14 + 19 * 3 + 258 * 7
+NLL = 286                       # literal / length alphabet of the LZ77 stage
+NDIST = 30                      # distance alphabet
+LZ_HEADER_WORDS = 72            # spnet_png_lz_pack's header stride: 2304 bits >= 3 + 14 + 19 * 3 + 316 * 7
+LENGTH_EXTRA = (0,) * 8 + (1,) * 4 + (2,) * 4 + (3,) * 4 + (4,) * 4 + (5,) * 4 + (0,)        # symbols 257 .. 285
+DIST_EXTRA = tuple(max(0, k // 2 - 1) for k in range(NDIST))
 MAX_THREADS = 16
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 COLOUR_TYPE = {1: 0, 2: 4, 3: 2, 4: 6}       # channels -> PNG colour type, 8 bits per sample
@@ -160,12 +171,10 @@ def _run_length_code(seq):
     return out
 
 
-def block_header(lengths):
-    """(bits as a Python int, bit i of the stream = bit i of the int; bit count) of the dynamic block's header."""
-    lengths = [int(v) for v in lengths]
-    if len(lengths) != NSYM:
-        raise ValueError("png: the literal code has 257 lengths")
-    rle = _run_length_code(lengths + [0])            # + the one distance code, of zero bits
+def _dynamic_header(hlit, hdist, lengths):
+    """(bits as a Python int, bit i of the stream = bit i of the int; bit count) of a dynamic block's header whose
+    257 + hlit literal / length and 1 + hdist distance code lengths are `lengths`, run-length coded as one sequence."""
+    rle = _run_length_code(lengths)
     cl_freq = [0] * 19
     for sym, _, _ in rle:
         cl_freq[sym] += 1
@@ -181,8 +190,8 @@ def block_header(lengths):
 
     put(1, 1)                 # BFINAL
     put(2, 2)                 # BTYPE = 10, dynamic Huffman
-    put(0, 5)                 # HLIT: 257 literal / length codes
-    put(0, 5)                 # HDIST: 1 distance code
+    put(hlit, 5)
+    put(hdist, 5)
     put(hclen - 4, 4)
     for s in _CL_ORDER[:hclen]:
         put(cl_len[s], 3)
@@ -191,6 +200,26 @@ def block_header(lengths):
         if nextra:
             put(extra, nextra)
     return acc, n
+
+
+def block_header(lengths):
+    """The literal-only block's header: HLIT 0 (257 literal / length codes), HDIST 0 (one distance code, of zero bits)."""
+    lengths = [int(v) for v in lengths]
+    if len(lengths) != NSYM:
+        raise ValueError("png: the literal code has 257 lengths")
+    return _dynamic_header(0, 0, lengths + [0])
+
+
+def lz_block_header(ll, dl):
+    """The LZ block's header from the literal / length lengths [286] and the distance lengths [30]: trailing unused symbols
+    are not sent (HLIT, HDIST); no distance symbol used: one distance code of zero bits; one used: its length is 1 (RFC
+    1951 section 3.2.7)."""
+    ll, dl = [int(v) for v in ll], [int(v) for v in dl]
+    if len(ll) != NLL or len(dl) != NDIST:
+        raise ValueError("png: the LZ codes have 286 and 30 lengths")
+    nl = max([NSYM] + [s + 1 for s in range(NSYM, NLL) if ll[s]])
+    nd = max([1] + [s + 1 for s in range(NDIST) if dl[s]])
+    return _dynamic_header(nl - 257, nd - 1, ll[:nl] + dl[:nd])
 
 
 def header_words(lengths):
@@ -218,6 +247,50 @@ def plan_frames(hist):
         bits = int(header_bits[n]) + int((hist[n] * ln[:256]).sum()) + int(ln[EOB])
         offsets[n + 1] = offsets[n] + 2 + (bits + 7) // 8 + 4
     return dict(lengths=lengths, codes=codes, header=header, header_bits=header_bits, offsets=offsets)
+
+
+def plan_frames_lz(hist, lhist, dhist):
+    """The plan of a batch with the LZ77 stage on, from the byte histograms [N][256], the literal / length histograms
+    [N][286] (end of block counted) and the distance histograms [N][30]: the literal-only plan (`literal`: plan_frames'
+    dict), both LZ code sets (lcodes [N][286], dcodes [N][30]: code | length << 16; llengths, dlengths), lz_header
+    [N][72], lz_header_bits [N] int32 (-1 for a frame that stays literal-only: spnet_png_lz_pack skips it), the exact sizes
+    of both streams (lz_sizes, literal_sizes), use_lz [N] (the LZ stream is strictly smaller) and offsets [N + 1] of the
+    chosen streams."""
+    hist = np.asarray(hist).reshape(-1, 256).astype(np.int64)
+    lhist = np.asarray(lhist).reshape(-1, NLL).astype(np.int64)
+    dhist = np.asarray(dhist).reshape(-1, NDIST).astype(np.int64)
+    N = hist.shape[0]
+    if lhist.shape[0] != N or dhist.shape[0] != N:
+        raise ValueError("png: histograms of %d, %d and %d frames" % (N, lhist.shape[0], dhist.shape[0]))
+    literal = plan_frames(hist)
+    literal_sizes = np.diff(literal["offsets"])
+    llengths = np.zeros((N, NLL), np.int64)
+    dlengths = np.zeros((N, NDIST), np.int64)
+    lcodes = np.zeros((N, NLL), np.uint32)
+    dcodes = np.zeros((N, NDIST), np.uint32)
+    header = np.zeros((N, LZ_HEADER_WORDS), np.uint32)
+    header_bits = np.zeros(N, np.int32)
+    lz_sizes = np.zeros(N, np.int64)
+    lextra = np.array(LENGTH_EXTRA, np.int64)
+    dextra = np.array(DIST_EXTRA, np.int64)
+    for n in range(N):
+        ll = np.array(_limited_lengths([int(c) for c in lhist[n]], 15), np.int64)
+        dl = np.array(_limited_lengths([int(c) for c in dhist[n]], 15), np.int64)
+        llengths[n], dlengths[n] = ll, dl
+        lcodes[n] = (canonical_codes(ll) | (ll << 16)).astype(np.uint32)
+        dcodes[n] = (canonical_codes(dl) | (dl << 16)).astype(np.uint32)
+        acc, nbits = lz_block_header(ll, dl)
+        header[n] = np.frombuffer(acc.to_bytes(LZ_HEADER_WORDS * 4, "little"), dtype="<u4")
+        bits = (nbits + int((lhist[n] * ll).sum()) + int((dhist[n] * dl).sum()) + int((lhist[n, NSYM:] * lextra).sum())
+                + int((dhist[n] * dextra).sum()))
+        header_bits[n] = nbits
+        lz_sizes[n] = 2 + (bits + 7) // 8 + 4
+    use_lz = lz_sizes < literal_sizes
+    offsets = np.zeros(N + 1, np.int64)
+    np.cumsum(np.where(use_lz, lz_sizes, literal_sizes), out=offsets[1:])
+    return dict(literal=literal, llengths=llengths, dlengths=dlengths, lcodes=lcodes, dcodes=dcodes, lz_header=header,
+                lz_header_bits=np.where(use_lz, header_bits, -1).astype(np.int32), lz_sizes=lz_sizes,
+                literal_sizes=literal_sizes, use_lz=use_lz, offsets=offsets)
 
 
 # ----------------------------------------------------------------------------- container
@@ -297,14 +370,73 @@ def pack_frames(frames, plan, adler, out=None, base=0):
     return out
 
 
-def zlib_streams_device(frames):
-    """The zlib stream of every frame, as views of one host array."""
+def lz_statistics(frames):
+    """(lhist [N][286], dhist [N][30]) of the frames' tokens (spnet_png_lz_scan), as host uint32 arrays: one launch, one D2H
+    copy."""
+    import torch
+    from . import _lib as L
+    N, H, W, channels = _frames_shape(frames)
+    frames = frames.contiguous()
+    both = torch.empty((N * (NLL + NDIST),), dtype=torch.int32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        L.spnet_png_lz_scan(frames.data_ptr(), N, H, W, channels, both.data_ptr(), both.data_ptr() + 4 * NLL * N,
+                            L.current_stream())
+    host = both.cpu().numpy().view(np.uint32)
+    return host[:N * NLL].reshape(N, NLL), host[N * NLL:].reshape(N, NDIST)
+
+
+def pack_frames_lz(frames, plan, adler, out=None, base=0):
+    """pack_frames for a plan_frames_lz plan: spnet_png_lz_pack writes the frames that took the LZ stream, spnet_png_pack
+    every run of neighbouring frames that stayed literal-only, into the same ZEROED buffer."""
+    import torch
+    from . import _lib as L
+    N, H, W, channels = _frames_shape(frames)
+    frames = frames.contiguous()
+    offsets = plan["offsets"] + int(base)
+    if out is None:
+        out = torch.zeros(((int(offsets[-1]) + 3) // 4 * 4,), dtype=torch.uint8, device=frames.device)
+    lit = plan["literal"]
+    parts = [offsets.astype(np.int64), plan["lcodes"], plan["dcodes"], plan["lz_header"], plan["lz_header_bits"], lit["codes"],
+             lit["header"], lit["header_bits"]]
+    blob = np.concatenate([np.ascontiguousarray(v).reshape(-1).view(np.uint8) for v in parts])        # one upload
+    dev = torch.from_numpy(blob).to(frames.device)
+    at = np.cumsum([0] + [v.nbytes for v in parts[:-1]]) + dev.data_ptr()
+    p_off, p_lc, p_dc, p_lh, p_lb, p_c, p_h, p_b = (int(v) for v in at)
+    use = plan["use_lz"]
+    frame_bytes = H * W * channels
+    with torch.cuda.device(frames.device):
+        if use.any():
+            L.spnet_png_lz_pack(frames.data_ptr(), N, H, W, channels, p_lc, p_dc, p_lh, p_lb, p_off, adler.data_ptr(),
+                                out.data_ptr(), int(out.numel()), L.current_stream())
+        lo = 0
+        while lo < N:
+            if use[lo]:
+                lo += 1
+                continue
+            hi = lo
+            while hi < N and not use[hi]:
+                hi += 1
+            L.spnet_png_pack(frames.data_ptr() + lo * frame_bytes, hi - lo, H, W, channels, p_c + 4 * NSYM * lo,
+                             p_h + 4 * HEADER_WORDS * lo, p_b + 4 * lo, p_off + 8 * lo, adler.data_ptr() + 4 * lo,
+                             out.data_ptr(), int(out.numel()), L.current_stream())
+            lo = hi
+    return out
+
+
+def zlib_streams_device(frames, lz77=False):
+    """The zlib stream of every frame, as views of one host array.  lz77: with the LZ77 stage (per frame the smaller of the
+    LZ stream and the literal-only one)."""
     N = _frames_shape(frames)[0]
     if N == 0:
         return []
     hist, adler = frame_statistics(frames)
-    plan = plan_frames(hist)
-    out = pack_frames(frames, plan, adler).cpu().numpy()
+    if lz77:
+        lhist, dhist = lz_statistics(frames)
+        plan = plan_frames_lz(hist, lhist, dhist)
+        out = pack_frames_lz(frames, plan, adler).cpu().numpy()
+    else:
+        plan = plan_frames(hist)
+        out = pack_frames(frames, plan, adler).cpu().numpy()
     off = plan["offsets"]
     return [out[int(off[n]):int(off[n + 1])] for n in range(N)]
 
@@ -313,10 +445,11 @@ def _pool_size(threads, jobs):
     return max(1, min(MAX_THREADS, int(threads), jobs))
 
 
-def encode_png_device(frames, threads=MAX_THREADS):
-    """PNG files of uint8 device frames [N,H,W] (grey) or [N,H,W,C] (C = 3: RGB), as a list of bytes."""
+def encode_png_device(frames, threads=MAX_THREADS, lz77=False):
+    """PNG files of uint8 device frames [N,H,W] (grey) or [N,H,W,C] (C = 3: RGB), as a list of bytes.  lz77: see
+    zlib_streams_device."""
     N, H, W, channels = _frames_shape(frames)
-    streams = zlib_streams_device(frames)
+    streams = zlib_streams_device(frames, lz77=lz77)
     if not streams:
         return []
     with ThreadPoolExecutor(max_workers=_pool_size(threads, N)) as pool:       # zlib.crc32 runs without the interpreter lock
@@ -330,14 +463,14 @@ def _write_pieces(path, pieces):
     return sum(len(piece) for piece in pieces)
 
 
-def write_png_device(frames, paths, threads=MAX_THREADS, pool=None):
+def write_png_device(frames, paths, threads=MAX_THREADS, pool=None, lz77=False):
     """encode_png_device, written to `paths` by a thread pool of this process (at most 16 threads; nothing is forked).  pool:
     a caller's ThreadPoolExecutor to use instead.  Returns the size of every file."""
     N, H, W, channels = _frames_shape(frames)
     paths = list(paths)
     if len(paths) != N:
         raise ValueError("png: %d frames, %d paths" % (N, len(paths)))
-    streams = zlib_streams_device(frames)
+    streams = zlib_streams_device(frames, lz77=lz77)
     if not streams:
         return []
 

@@ -276,13 +276,14 @@ def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_ex
     """Overlay PNGs steelpan_pred_%05d.png and the zooniverse-style CSV (cx,cy,file,rings,a,b,angle)
     from de-normalised true / predicted grids (utils.py:67-137).  png = "host": every overlay is saved by Pillow as it is
     drawn; "device" (additive): the drawn RGB overlays are collected png_chunk at a time, uploaded, encoded on the GPU
-    (spnet_amd.png) and written by a thread pool -- the same pixels, file names and CSV rows, other file bytes.
+    (spnet_amd.png) and written by a thread pool -- the same pixels, file names and CSV rows, other file bytes; "device-lz":
+    the same with the encoder's LZ77 stage on (smaller files).
     draw = "host": Pillow draws; "device" (additive): the loop only plans (spnet_amd.overlay.plan_overlays), the frames
     are loaded png_chunk at a time -- by the device decoder with device_decode, else by Pillow and one upload per chunk --
     and one HIP launch per chunk draws them: the same file names and CSV rows, the same pixels away from outline edges
     (spnet_amd/overlay.py has the rule)."""
-    if png not in ("host", "device"):
-        raise ValueError('show_pred_ellipses: png is "host" or "device", got %r' % (png,))
+    if png not in ("host", "device", "device-lz"):
+        raise ValueError('show_pred_ellipses: png is "host", "device" or "device-lz", got %r' % (png,))
     if draw not in ("host", "device"):
         raise ValueError('show_pred_ellipses: draw is "host" or "device", got %r' % (draw,))
     if draw == "device":
@@ -303,7 +304,8 @@ def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_ex
             from .png import write_png_device
             if not torch.cuda.is_available():
                 raise RuntimeError('show_pred_ellipses: png="device" encodes on the GPU (no CPU fallback)')
-            write_png_device(torch.from_numpy(np.stack([h[0] for h in held])).cuda(), [h[1] for h in held])
+            write_png_device(torch.from_numpy(np.stack([h[0] for h in held])).cuda(), [h[1] for h in held],
+                             lz77=png == "device-lz")
             held.clear()
 
     for j in range(num_draw):
@@ -358,9 +360,9 @@ def _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, sh
                                      size=tuple(int(v) for v in frames.shape[1:3]), with_csv=out_csv is not None)
         drawn = overlay.draw_overlays_device(frames, plan)
         paths = [log_dir + '/steelpan_pred_' + str(lo + k).zfill(5) + '.png' for k in range(n)]
-        if png == "device":
+        if png != "host":
             from .png import write_png_device
-            write_png_device(drawn, paths)
+            write_png_device(drawn, paths, lz77=png == "device-lz")
         else:
             host = drawn.cpu().numpy()
             for k in range(n):

@@ -513,6 +513,37 @@ int spnet_warp_chain_u8(const unsigned char* src, int n_src, const int* sel, con
  * after 64 turns (bit-identity holds for angles within +-11,520 degrees). */
 int spnet_encode_targets(const double* rows, const int* count, int B, int K, int nx, int ny, int ns, int H, int W,
                          const float* trig, const double* fwd, void* warp_records, float* Y, int* flags, void* stream);
+/* The random parameters of the on-the-fly augmentation of B samples, drawn on the device in one launch
+ * (csrc/augment_params.hip), into the arrays the kernels above read.  sample [B]: int32 sample indices on the device.
+ * Augmentation half (rects != NULL; 12 <= H, W <= 2048): rects [B][6][4] = (r0, r1, c0, c1), vals [B][6], nrect [B] for
+ * spnet_cutout (entries past nrect are zeros); coords [B][2][n_salt + n_pepper], flag [B] for spnet_saltpepper (zeros where
+ * flag is 0); ksize [B] for spnet_gaussian_blur.  mm [n_frames][2]: spnet_minmax of the pristine frames, row = the sample
+ * index clamped into the table.  Warp half (warp_records != NULL; 1 <= Hw, Ww <= 2048, the full frame size): the B 64-byte
+ * records of spnet_warp_chain_u8 and fwd [B][8] of spnet_encode_targets; trig [4097][2] float64 = (cos, sin) of
+ * deg2rad((k - 2048) * (20 / 2048)) as the host's libm gives them.  Either half alone or both; with both a sample's warp and
+ * augmentation share its key.  B == 0: nothing to do, success.  hipErrorInvalidValue (nothing launched): B < 0, a NULL
+ * sample, neither half, sizes outside the ranges above, n_salt or n_pepper < 0, n_frames < 1, a NULL array of a selected
+ * half, warp_records / fwd / trig not 8-byte aligned.
+ * The stream, stateless and counter based -- a sample's values depend on (seed, epoch, sample index) only, not on its
+ * position in the batch, the batch size, the rank or the world size; the reference's distributions, other values:
+ *   mix, u(key, k) = mix(key ^ (k * 0x85ebca6b + 0xc2b2ae35)) and randint(u, lo, hi) as for spnet_fake_espi_params below
+ *   (csrc/counter_rng.h); U(u) = (u >> 8) * 2^-24
+ *   skey = mix(mix(mix(seed ^ 0x3c6ef372) + epoch) ^ sample)                       (uint32)
+ *   key(slot) = mix(skey + slot): slot 0 = the frame's own draws, 1 + r = cutout rectangle r, 7 = warp, 8 = salt / pepper
+ *   slot 0: k 0 cutout count [0, 6]; 1 salt / pepper gate = u >> 31; 2 blur when U < 0.4 and 3 U <= 0.3 (compared in
+ *     double), then 4 ksize = 7 if u >> 31 else 3 (0 without blur); the band-pass mix-up's draws, made by the HOST from the
+ *     same key (augmentation.draw_bandpass_keyed): 5 gate U < bpmix_prob (in double), 6 table row [0, 4 n_real - 1], 7 scale
+ *     = 3 * U in float32
+ *   slot 1 + r: k 0 r0 [0, H - 12]; 1 c0 [0, W - 12]; 2 dr, 3 dc [11, 74]; r1 = min(r0 + dr, H - 1), c1 = min(c0 + dc,
+ *     W - 1); 4 fill = lo + U * (hi - lo) in float32, each operation rounded on its own
+ *   slot 8: point p (salt points first, then pepper): k 2p row [0, H - 2], 2p + 1 column [0, W - 2]
+ *   slot 7: k 0 flip = (u >> 30) - 2; 1 angle index [0, 4096]; 2 shift unless randint [0, 9] is 0; 3, 4 xt, yt =
+ *     rint(40 * (2 U - 1)) in double, half to even (0 when the gate is off)
+ *   matrices: index 2048 gives the identity for both; otherwise (a, b) = trig[k], fwd = rotation_matrix_2d((Ww / 2, Hw / 2),
+ *     angle) and the record's m = invert_affine_cv2(fwd) (spnet_amd/augmentation.py), in double, operation by operation. */
+int spnet_augment_params(unsigned seed, unsigned epoch, const int* sample, int B, int H, int W, int n_salt, int n_pepper,
+                         const float* mm, int n_frames, int* rects, float* vals, int* nrect, int* coords, int* flag,
+                         int* ksize, int Hw, int Ww, const double* trig, void* warp_records, double* fwd, void* stream);
 /* Dropout(0.1) of the stem (spnet/models.py:340); same call with dy regenerates the mask in backward. */
 int spnet_dropout(const float* x, float* y, long n, unsigned seed, float rate, const unsigned* seed_dev,
                   void* stream);   /* seed_dev (or NULL): device uint32 overriding seed (hipGraph replay) */

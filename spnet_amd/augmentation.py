@@ -3,7 +3,9 @@
 Train-time (AugmentOnTheFly, spnet/callbacks.py:272-341): cutout + salt-and-pepper + the reference's
 no-op blur.  The random PARAMETERS are drawn on the host with numpy's global RNG in exactly the
 reference's call order (so a seeded run reproduces the reference's augmented frames bit for bit),
-the PIXEL work runs in HIP kernels on frames that never leave HBM (csrc/augment.hip).
+the PIXEL work runs in HIP kernels on frames that never leave HBM (csrc/augment.hip).  Opt-in (draw_device,
+draw_params_device; AugmentOnTheFly(params="device")): the parameters of a chunk drawn in HBM by one launch
+(csrc/augment_params.hip) from a keyed stream of its own -- the same distributions, other values.
 
 Offline warps (augment_preproc.py:56-100): flip / rotate / translate = one inverse-affine bilinear
 gather kernel plus the reference's host-side metadata arithmetic.  DeviceWarper is the batched, device-resident form: the
@@ -81,6 +83,101 @@ def draw_blur_gate(blur_prob_outer=0.4, blur_prob=0.3):
     return 0
 
 
+# ----------------------------------------------------------------------------- parameter draws on the device
+AUG_ANGLE_MID = 2048              # spnet_augment_params: angle index k in 0..4096, angle = (k - 2048) * (20 / 2048) degrees
+_AUG_TRIG = {}
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def aug_angle(k):
+    """The quantised warp angle of index k, in degrees (float64; k = 2048 is 0)."""
+    return (np.asarray(k, np.float64) - AUG_ANGLE_MID) * (20.0 / 2048.0)
+
+
+def aug_trig_table(device=None):
+    """(cos, sin) of np.deg2rad(aug_angle(k)), k = 0..4096, float64 [4097,2]: what rotation_matrix_2d computes for these
+    angles, so the matrices spnet_augment_params forms from it have warp_minv's / warp_fwd's bits.  device: a cached device
+    tensor instead of the numpy array."""
+    if "host" not in _AUG_TRIG:
+        rad = np.deg2rad(aug_angle(np.arange(2 * AUG_ANGLE_MID + 1)))
+        _AUG_TRIG["host"] = np.stack([np.cos(rad), np.sin(rad)], 1)
+    if device is None:
+        return _AUG_TRIG["host"]
+    key = str(torch.device(device))
+    if key not in _AUG_TRIG:
+        _AUG_TRIG[key] = torch.from_numpy(_AUG_TRIG["host"]).to(device)
+    return _AUG_TRIG[key]
+
+
+def _mix32(x):
+    """The samplers' 32-bit mixer (csrc/counter_rng.h) on uint64 arrays holding uint32 values."""
+    x = np.asarray(x, np.uint64) & _M32
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7feb352d)) & _M32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846ca68b)) & _M32
+    return x ^ (x >> np.uint64(16))
+
+
+def _keyed_draw(key, k):
+    return _mix32(key ^ np.uint64((k * 0x85ebca6b + 0xc2b2ae35) & 0xFFFFFFFF))
+
+
+def draw_bandpass_keyed(seed, epoch, sample_index, n_real, bpmix_prob):
+    """The band-pass mix-up's three draws per sample from the keyed stream of spnet_augment_params (slot 0, draws 5..7: the
+    recipe is in include/spnet_hip.h), for a whole chunk in numpy: spnet_bandpass_apply takes a compacted list whose length
+    the host must know, so these stay on the host.  -> (gate bool [B], table row int32 [B], scale float32 [B])."""
+    idx = np.asarray(sample_index, np.int64).astype(np.uint64) & _M32
+    seed_key = _mix32(_mix32(np.uint64((int(seed) & 0xFFFFFFFF) ^ 0x3c6ef372)) + np.uint64(int(epoch) & 0xFFFFFFFF))
+    k0 = _mix32(_mix32(seed_key ^ idx))                                   # key(slot 0) = mix(skey + 0)
+    gate = (_keyed_draw(k0, 5) >> np.uint64(8)).astype(np.float64) * 2.0 ** -24 < float(bpmix_prob)
+    row = ((_keyed_draw(k0, 6) * np.uint64(max(4 * int(n_real), 1))) >> np.uint64(32)).astype(np.int32)
+    s = np.float32(3) * ((_keyed_draw(k0, 7) >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24))
+    return gate, row, s
+
+
+def _index_device(sample_index, device):
+    """Sample indices, array-like (uploaded) or already an int32 device tensor, as an int32 device tensor."""
+    if isinstance(sample_index, torch.Tensor):
+        if not sample_index.is_cuda or sample_index.dtype != torch.int32 or sample_index.dim() != 1:
+            raise ValueError("draw_device: sample indices as a tensor must be int32 [B] on the device")
+        return sample_index.contiguous()
+    return torch.from_numpy(np.ascontiguousarray(sample_index, dtype=np.int32)).to(device)
+
+
+def draw_params_device(sample_index, seed, epoch, augmenter=None, warper=None):
+    """ONE launch of spnet_augment_params on the current stream for the samples `sample_index` (array-like, or an int32
+    device tensor, which is used as it is): the augmentation half for `augmenter`, the warp half for `warper`, either or
+    both (they then share each sample's key).  Nothing is read back.  -> (augmentation dict or None, warp dict or None) of
+    device tensors, see DeviceAugmenter.draw_device / DeviceWarper.draw_device."""
+    if augmenter is None and warper is None:
+        raise ValueError("draw_params_device: no augmenter and no warper")
+    dev = (augmenter or warper).X.device
+    index = _index_device(sample_index, dev)
+    B = int(index.numel())
+    ap = wp = None
+    a = [0, 0, 0, 0, None, 1] + [None] * 6
+    w = [0, 0, None, None, None]
+    if augmenter is not None:
+        g = augmenter
+        npts = g.n_salt + g.n_pepper
+        ibuf = torch.empty(B * (MAX_RECTS * 4 + 3 + 2 * npts), dtype=torch.int32, device=dev)      # one allocation
+        cut = np.cumsum([0, B * MAX_RECTS * 4, B, B, B])
+        ap = dict(index=index, rects=ibuf[cut[0]:cut[1]], nrect=ibuf[cut[1]:cut[2]], flag=ibuf[cut[2]:cut[3]],
+                  ksize=ibuf[cut[3]:cut[4]], coords=ibuf[cut[4]:], vals=torch.empty(B * MAX_RECTS, device=dev))
+        a = [g.H, g.W, g.n_salt, g.n_pepper, g.mm.data_ptr(), g.N] + \
+            [ap[k].data_ptr() if ap[k].numel() else None for k in ("rects", "vals", "nrect", "coords", "flag", "ksize")]
+    if warper is not None:
+        rec = torch.empty(B * 8, dtype=torch.float64, device=dev)        # 64-byte records, 8-byte aligned
+        fwd = torch.empty((B, 8), dtype=torch.float64, device=dev)
+        wp = dict(index=index, records=rec.view(torch.int32), fwd=fwd, H=warper.H, W=warper.W)
+        w = [warper.H, warper.W, aug_trig_table(dev).data_ptr(), rec.data_ptr() if B else None, fwd.data_ptr() if B else None]
+    if B:
+        with torch.cuda.device(dev):
+            L.spnet_augment_params(int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, index.data_ptr(), B, *a, *w, _stream())
+    return ap, wp
+
+
 class DeviceAugmenter:
     """Keeps the pristine frames [N,H,W,1] in HBM and writes augmented batches into a device buffer."""
 
@@ -100,7 +197,8 @@ class DeviceAugmenter:
         mm = torch.empty(self.N, 2, device=self.X.device)
         scratch = torch.empty(self.N * 32, device=self.X.device)
         L.spnet_minmax(self.X.data_ptr(), self.N, self.H * self.W, mm.data_ptr(), scratch.data_ptr(), _stream())
-        self.mm_host = mm.cpu().numpy()     # min/max of the pristine frames: cutout's fill range
+        self.mm = mm                        # min/max of the pristine frames: cutout's fill range (draw_device reads it)
+        self.mm_host = mm.cpu().numpy()
         self.n_salt, self.n_pepper = saltpepper_counts(self.shape)
         self._upload = None
         self.bpmix_prob = float(bpmix_prob)
@@ -173,14 +271,76 @@ class DeviceAugmenter:
             p.update(bp_sel=bp_sel, bp_row=bp_row, bp_s=bp_s)
         return p
 
+    def draw_device(self, sample_index, seed, epoch, host_index=None):
+        """The parameters of the samples `sample_index` drawn ON THE DEVICE (spnet_augment_params: a keyed stream of its own,
+        every value a function of (seed, epoch, sample index) only; see include/spnet_hip.h) -> a dict of device tensors in
+        draw()'s layout (index, rects, vals, nrect, coords, flag, ksize) that apply() takes without uploading anything.
+        sample_index: array-like, or an int32 device tensor (used as it is).  With a band-pass pool the dict also holds
+        bp_n (a host int) and host arrays bp_sel / bp_row / bp_s: the mix-up's draws come from the same keyed stream but are
+        made on the host, vectorised over the chunk (draw_bandpass_keyed) -- they need the indices on the host, host_index
+        when sample_index is a tensor (else it is copied back)."""
+        p, _ = draw_params_device(sample_index, seed, epoch, augmenter=self)
+        return self._add_bandpass_keyed(p, sample_index, seed, epoch, host_index)
+
+    def _add_bandpass_keyed(self, p, sample_index, seed, epoch, host_index=None):
+        if self.bp is not None:
+            if host_index is None:
+                host_index = sample_index.cpu().numpy() if isinstance(sample_index, torch.Tensor) else sample_index
+            gate, row, s = draw_bandpass_keyed(seed, epoch, host_index, self.bp.pool.n_real, self.bpmix_prob)
+            B = len(gate)
+            sel = np.nonzero(gate)[0]
+            p["bp_n"] = len(sel)
+            for k, v, dt in (("bp_sel", sel, np.int32), ("bp_row", row[sel], np.int32), ("bp_s", s[sel], np.float32)):
+                a = np.zeros(B, dt)                 # fixed length B, as draw() pads them
+                a[:len(sel)] = v
+                p[k] = a
+        return p
+
+    def _apply_device(self, p, out, src=None):
+        """apply() for draw_device's dict: the same kernels on parameters that are already in HBM."""
+        dev = self.X.device
+        B = int(p["index"].numel())
+        self._keep = p
+        self.index_dev = p["index"]
+        if B == 0:
+            return out
+        X = self.X if src is None else src
+        L.spnet_cutout(X.data_ptr(), None if src is not None else p["index"].data_ptr(), out.data_ptr(), B, self.H, self.W,
+                       p["rects"].data_ptr(), p["vals"].data_ptr(), p["nrect"].data_ptr(), _stream())
+        mm = torch.empty(B * (2 + 32), device=dev)
+        self._mm = mm
+        L.spnet_minmax(out.data_ptr(), B, self.H * self.W, mm.data_ptr(), mm[2 * B:].data_ptr(), _stream())
+        L.spnet_saltpepper(out.data_ptr(), B, self.H, self.W, p["coords"].data_ptr(), self.n_salt, self.n_pepper,
+                           p["flag"].data_ptr(), mm.data_ptr(), _stream())
+        if self.real_blur:                  # unconditionally: whether any frame drew a blur is not known here; ksize 0 copies
+            tmp = torch.empty_like(out)
+            L.spnet_gaussian_blur(out.data_ptr(), tmp.data_ptr(), B, self.H, self.W, p["ksize"].data_ptr(), _stream())
+            out.copy_(tmp)
+        if self.bp is not None and p["bp_n"] > 0:
+            n = int(p["bp_n"])
+            if self._upload is None:
+                self._upload = L.AsyncUploader(dev)
+            packed = self._upload("bp", np.concatenate([p["bp_sel"], p["bp_row"], p["bp_s"].view(np.int32)]))
+            ws = torch.empty(L.spnet_bandpass_ws(n, self.H, self.W), device=dev)
+            self._bp_ws, self._bp_up = ws, packed
+            pool = self.bp.pool
+            L.spnet_bandpass_apply(out.data_ptr(), 2, packed[:B].data_ptr(), B, n, self.H, self.W, pool.table.data_ptr(),
+                                   4 * pool.n_real, packed[B:2 * B].data_ptr(), packed[2 * B:].view(torch.float32).data_ptr(),
+                                   out.data_ptr(), 1, None, ws.data_ptr(), _stream())
+        return out
+
     def apply(self, params, out, src=None):
         """out[j] = augmented copy of frame params['index'][j]; out is a device tensor [B,H,W,1].  src (optional, device
-        float32 [B,H,W(,1)], not `out`): the batch's frames are read from src[j] instead (frames that were warped first)."""
+        float32 [B,H,W(,1)], not `out`): the batch's frames are read from src[j] instead (frames that were warped first).
+        params: draw()'s host dict (packed and uploaded) or draw_device()'s device dict (nothing is uploaded)."""
         dev = self.X.device
         X = self.X
         if src is not None:
             if src.dtype != torch.float32 or not src.is_contiguous() or src.numel() != len(params["index"]) * self.H * self.W:
                 raise ValueError("DeviceAugmenter.apply: src must be contiguous float32 [%d,%d,%d]" % (len(params["index"]), self.H, self.W))
+        if isinstance(params["rects"], torch.Tensor):
+            return self._apply_device(params, out, src)
+        if src is not None:
             X = src
             params = dict(params, index=np.arange(len(params["index"]), dtype=np.int32))
         if self._upload is None:
@@ -717,6 +877,8 @@ class DeviceWarper:
     device tensors (rows float64 [N,K,6], count int32 [N]), in HBM as well; warps batches of them with one launch
     (csrc/warp.hip) and computes the matching targets on the host, or on the device (csrc/targets.hip).
       draw(indices, seeds=None) -> params (draw_warp per frame; per-frame seeding as DeviceAugmenter.draw)
+      draw_device(sample_index, seed, epoch) -> params drawn in HBM (records, fwd, index as device tensors), which
+                                   targets_device and apply take as they are: no upload
       targets(params)           -> (Y, rejected), see warp_targets (resets rejected frames' parameters to the identity);
                                    host metadata only: the oracle path
       targets_device(params)    -> (Y, flags) device tensors, see encode_targets_device: params' records are uploaded,
@@ -815,10 +977,25 @@ class DeviceWarper:
         nf = 0 if fwd is None else 16 * B
         return packed[:16 * B], (packed[16 * B:16 * B + nf].view(torch.float64).view(B, 8) if nf else None), packed[16 * B + nf:]
 
+    def draw_device(self, sample_index, seed, epoch):
+        """The warp parameters of the samples `sample_index` (array-like or an int32 device tensor) drawn ON THE DEVICE
+        (spnet_augment_params: flip, a rotation angle quantised to 20/2048 degrees, the shift; a keyed stream of its own,
+        see include/spnet_hip.h) -> dict(index, records, fwd, H, W) of device tensors: the records apply() reads and the
+        forward matrices targets_device() reads, with the bits warp_minv / warp_fwd give for those angles.  Nothing is
+        uploaded or read back.  (With a DeviceAugmenter as well, draw_params_device fills both in one launch.)"""
+        return draw_params_device(sample_index, seed, epoch, warper=self)[1]
+
+    @staticmethod
+    def _on_device(params):
+        return isinstance(params.get("records"), torch.Tensor)
+
     def targets_device(self, params):
         if self.meta_dev is None:
             raise ValueError("DeviceWarper.targets_device: the metadata must be device tensors (rows, count)")
-        rec, fwd, index = self._send(params, warp_fwd(params))
+        if self._on_device(params):         # draw_device's: already in HBM
+            rec, fwd, index = params["records"], params["fwd"], params["index"]
+        else:
+            rec, fwd, index = self._send(params, warp_fwd(params))
         self._sent = (params, rec, index)
         with torch.cuda.device(self.X.device):
             rows, count = self.meta_dev[0].index_select(0, index), self.meta_dev[1].index_select(0, index)
@@ -837,6 +1014,8 @@ class DeviceWarper:
             return out_u8, out_f
         if self._sent is not None and self._sent[0] is params:      # targets_device's upload, rejected records rewritten
             _, rec, index = self._sent
+        elif self._on_device(params):
+            rec, index = params["records"], params["index"]
         else:
             rec, _, index = self._send(params)
         self._sent = None

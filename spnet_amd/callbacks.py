@@ -94,7 +94,7 @@ class AugmentOnTheFly(Callback):
 
     def __init__(self, X, Y, orig_img_shape=(384, 512), aug_every=1, chunk=256, seed=1, real_blur=False,
                  bandpass_real=None, bpmix_prob=0.3, warp=False, warp_files=None, pred_grid=(6, 6, 2), warp_source=None,
-                 warp_targets="host", device_decode=False):
+                 warp_targets="host", device_decode=False, params="host"):
         """real_blur=False reproduces the reference, whose Gaussian blur is a no-op (the result of cv2.GaussianBlur is
         discarded, augmentation.py:66-70); True applies it (train_spnet.py --augment_blur).
         bandpass_real: directory of real *.png frames of the training frames' size -- after the blur, a frame is
@@ -118,7 +118,16 @@ class AugmentOnTheFly(Callback):
         rejected count is summed on the device and read once per epoch.
         device_decode (with warp_files and / or a bandpass_real directory): the full-size frames of the warp, and the grey
         real frames of the mix-up, are decoded on the GPU from the files' bytes (spnet_amd.png) instead of by Pillow and
-        uploaded: the same frames."""
+        uploaded: the same frames.
+        params: "host" (default) = the random parameters are drawn per frame with numpy's / Python's RNGs in the
+        reference's call order, as above.  "device" (train_spnet.py --device_aug_params) = one spnet_augment_params launch
+        per chunk draws them in HBM -- cutout, salt and pepper, blur and, with a warp_source, the warp's flip / angle /
+        shift with its matrices -- from a keyed stream of its own: the reference's distributions (the rotation angle
+        quantised to 20/2048 degrees), other values, each a function of (seed, the model's epoch counter, sample index)
+        only, so a sample's augmentation in an epoch is the same single-process and at any world size.  No per-frame host
+        work and no parameter upload; the band-pass mix-up's gate / row / scale alone are computed on the host (vectorised,
+        from the same keys) and uploaded, because its kernel takes a compacted list.  Not with warp_files: their metadata
+        path computes the targets on the host from host-drawn parameters."""
         super().__init__()
         import torch
         from . import parallel
@@ -128,6 +137,13 @@ class AugmentOnTheFly(Callback):
         self.orig_img_shape = orig_img_shape
         self.chunk = chunk
         self.seed = seed
+        if params not in ("host", "device"):
+            raise ValueError("AugmentOnTheFly: params must be 'host' or 'device', got %r" % (params,))
+        if params == "device" and (warp_files is not None or (warp and warp_source is None)):
+            raise ValueError("AugmentOnTheFly: params='device' draws the warp for a warp_source (device metadata, "
+                             "warp_targets='device'); warp_files is the host-metadata path, whose targets are computed on "
+                             "the host from host-drawn parameters -- use params='host' with warp_files")
+        self.params = params
         parallel.init_distributed()          # this rank's GPU (no-op if the model already did it)
         dev = parallel.local_device()
         self.X_orig = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X)).to(dev)
@@ -176,17 +192,26 @@ class AugmentOnTheFly(Callback):
         self._y_upload = None
         self.label_seconds = 0.0              # host time of the last epoch's draws' targets (tools/warp_time.py)
 
-    def _augment_chunk(self, idx, seeds, out):
+    def _augment_chunk(self, idx, seeds, out, epoch=None, idx_dev=None):
         """out[j] = augmented frame idx[j] (device [B,h,w,1]); with warp: warped first, and -> (Y [B,576] device, number
-        of rejected frames -- 0 with warp_targets="device", which counts them in self._counts instead), else None."""
+        of rejected frames -- 0 with warp_targets="device", which counts them in self._counts instead), else None.
+        params="device": idx_dev holds idx as an int32 device tensor and the chunk's parameters are drawn there from
+        (self.seed, epoch, sample index) in one launch; seeds is not used."""
         import torch
         from . import _lib as L
         aug, wr = self.augmenter, self.warper
+        on_device = self.params == "device"
         if wr is None:
-            aug.apply(aug.draw(idx, seeds=seeds), out)
+            p = aug.draw_device(idx_dev, self.seed, epoch, host_index=idx) if on_device else aug.draw(idx, seeds=seeds)
+            aug.apply(p, out)
             return None
-        wp = wr.new_params(idx)
-        p = aug.draw(idx, seeds=seeds, before=lambda j, i: wr.draw_into(wp, j))
+        if on_device:
+            from .augmentation import draw_params_device
+            p, wp = draw_params_device(idx_dev, self.seed, epoch, augmenter=aug, warper=wr)
+            aug._add_bandpass_keyed(p, idx_dev, self.seed, epoch, idx)
+        else:
+            wp = wr.new_params(idx)
+            p = aug.draw(idx, seeds=seeds, before=lambda j, i: wr.draw_into(wp, j))
         device_targets = self.warp_targets == "device"
         t0 = time.time()
         if device_targets:
@@ -239,11 +264,19 @@ class AugmentOnTheFly(Callback):
             return self._augment_shard(np.asarray(shard), getattr(self.model, "_epochs_seen", epoch))
         n = self.X_orig.shape[0]
         self.rejected, self.label_seconds = 0, 0.0
+        on_device = self.params == "device"
+        if on_device:                       # the key's epoch is the counter _augment_shard takes: the same draws at any world size
+            import torch
+            key_epoch = getattr(self.model, "_epochs_seen", epoch)
+            every = torch.arange(n, dtype=torch.int32, device=self.X_aug.device)
         for lo in range(0, n, self.chunk):
             hi = min(n, lo + self.chunk)
             if (lo // self.chunk) % 16 == 0 or hi == n:
                 print("   Augmenting on the fly: ", hi, "/", n, "\r", sep="", end="")
-            res = self._augment_chunk(list(range(lo, hi)), None, self.X_aug[lo:hi])
+            if on_device:
+                res = self._augment_chunk(np.arange(lo, hi), None, self.X_aug[lo:hi], key_epoch, every[lo:hi])
+            else:
+                res = self._augment_chunk(list(range(lo, hi)), None, self.X_aug[lo:hi])
             if res is not None:
                 self.Y_aug[lo:hi].copy_(res[0])
                 self.rejected += res[1]
@@ -259,13 +292,20 @@ class AugmentOnTheFly(Callback):
         from . import parallel
         tmp = None
         self.rejected, self.label_seconds = 0, 0.0
+        on_device = self.params == "device"
+        if on_device:                       # the shard's indices go up once; the keyed stream needs no per-sample seeds
+            every = torch.from_numpy(np.ascontiguousarray(shard, dtype=np.int32)).to(self.X_aug.device)
         for lo in range(0, len(shard), self.chunk):
             idx = shard[lo:lo + self.chunk]
             if tmp is None or tmp.shape[0] != len(idx):
                 tmp = torch.empty((len(idx),) + tuple(self.X_aug.shape[1:]), device=self.X_aug.device)
-            seeds = [parallel.sample_seed(self.seed, epoch, i) for i in idx]
-            res = self._augment_chunk(list(idx), seeds, tmp)
-            where = torch.as_tensor(idx, dtype=torch.int64, device=self.X_aug.device)
+            if on_device:
+                res = self._augment_chunk(idx, None, tmp, epoch, every[lo:lo + self.chunk])
+                where = every[lo:lo + self.chunk].to(torch.int64)
+            else:
+                seeds = [parallel.sample_seed(self.seed, epoch, i) for i in idx]
+                res = self._augment_chunk(list(idx), seeds, tmp)
+                where = torch.as_tensor(idx, dtype=torch.int64, device=self.X_aug.device)
             self.X_aug.index_copy_(0, where, tmp)
             if res is not None:
                 self.Y_aug.index_copy_(0, where, res[0])

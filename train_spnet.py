@@ -58,7 +58,7 @@ def fake_stream_data(n_train, n_val, global_batch, pred_grid, seed, warp=False):
 def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch_size=32, epochs=30, pred_grid=[6, 6, 2],
                   noaugment=False, log_dir=".", lr_max=4e-5, freeze_fac=0.7, frozen_epochs=4, random_seed=1,
                   augment_blur=False, bp_real=None, bpmix_prob=0.3, warp=False, fake_stream=None, fake_val=None,
-                  device_decode=False):
+                  device_decode=False, device_aug_params=False):
     np.random.seed(random_seed)
     if device_decode and (noaugment or not ((warp and not fake_stream) or bp_real)):
         raise ValueError("--device_decode decodes the files of --warp (on a data set on disk) and of --bp_real on the GPU: "
@@ -103,7 +103,8 @@ def train_network(weights_file="weights.hdf5", datapath=".", fraction=1.0, batch
                              device_decode=bool(device_decode))
         callback_list.append(callbacks.AugmentOnTheFly(X_train, Y_train, aug_every=1, seed=random_seed,
                                                        real_blur=augment_blur, bandpass_real=bp_real,
-                                                       bpmix_prob=bpmix_prob, pred_grid=pred_grid, **warp_args))
+                                                       bpmix_prob=bpmix_prob, pred_grid=pred_grid,
+                                                       params="device" if device_aug_params else "host", **warp_args))
 
     fit_args = dict(batch_size=batch_size, shuffle=True, verbose=1, validation_data=(X_val, Y_val), callbacks=callback_list)
     if frozen_epochs > 0 and freeze_fac > 0.0:        # warm-up phase with the first layers frozen
@@ -158,6 +159,11 @@ if __name__ == '__main__':
                    help="(additive; needs --warp on a data set on disk, or --bp_real) decode the full-size frames of the warp "
                         "and the grey real frames of --bp_real on the GPU from the PNG files' bytes instead of with "
                         "Pillow: the same frames")
+    p.add_argument('--device_aug_params', action='store_true',
+                   help="(additive) draw the random parameters of the on-the-fly augmentation -- and, with --fake_stream "
+                        "--warp, of the warp -- on the GPU, one launch per chunk, from a keyed stream of its own (the same "
+                        "distributions, other values than the reference's RNG order; a sample's draws depend on the seed, "
+                        "the epoch and the sample only).  Not with --warp on a data set on disk")
     p.add_argument('--fake_stream', type=int, default=None, metavar='N',
                    help="train on N fresh fake-ESPI frames per epoch, generated on the GPU (rounded down to a multiple of "
                         "the global batch); no Train/ or Val/ directory is read")
@@ -181,7 +187,8 @@ if __name__ == '__main__':
                           log_dir=log_dir, lr_max=args.lrmax, freeze_fac=args.freeze_fac,
                           frozen_epochs=args.frozen_epochs, random_seed=args.random_seed,
                           augment_blur=args.augment_blur, bp_real=args.bp_real, bpmix_prob=args.bpmix_prob, warp=args.warp,
-                          fake_stream=args.fake_stream, fake_val=args.fake_val, device_decode=args.device_decode)
+                          fake_stream=args.fake_stream, fake_val=args.fake_val, device_decode=args.device_decode,
+                          device_aug_params=args.device_aug_params)
 
     if int(os.environ.get("RANK", "0")) == 0:
         print("\n----------------------------\nStarting model evaluation...")

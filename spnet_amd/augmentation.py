@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .fake_espi import _cached_table
 
 MAX_RECTS = 6
 
@@ -98,15 +99,10 @@ def aug_trig_table(device=None):
     """(cos, sin) of np.deg2rad(aug_angle(k)), k = 0..4096, float64 [4097,2]: what rotation_matrix_2d computes for these
     angles, so the matrices spnet_augment_params forms from it have warp_minv's / warp_fwd's bits.  device: a cached device
     tensor instead of the numpy array."""
-    if "host" not in _AUG_TRIG:
+    def make():
         rad = np.deg2rad(aug_angle(np.arange(2 * AUG_ANGLE_MID + 1)))
-        _AUG_TRIG["host"] = np.stack([np.cos(rad), np.sin(rad)], 1)
-    if device is None:
-        return _AUG_TRIG["host"]
-    key = str(torch.device(device))
-    if key not in _AUG_TRIG:
-        _AUG_TRIG[key] = torch.from_numpy(_AUG_TRIG["host"]).to(device)
-    return _AUG_TRIG[key]
+        return np.stack([np.cos(rad), np.sin(rad)], 1)
+    return _cached_table(_AUG_TRIG, make, device)
 
 
 def _mix32(x):
@@ -811,15 +807,10 @@ def trig_2deg_table(device=None):
     """(cos, sin) of 2 * deg2rad(k) for the whole degrees k = 0..359 as float32 [360,2], computed in float64 as
     _encode_targets computes them: the table spnet_encode_targets reads for whole-degree angles (fake_espi.trig2_table's
     idiom).  device: a cached device tensor instead of the numpy array."""
-    if "host" not in _TRIG_2DEG:
+    def make():
         t = 2 * np.deg2rad(np.arange(360, dtype=np.float64))
-        _TRIG_2DEG["host"] = np.stack([np.cos(t), np.sin(t)], 1).astype(np.float32)
-    if device is None:
-        return _TRIG_2DEG["host"]
-    key = str(torch.device(device))
-    if key not in _TRIG_2DEG:
-        _TRIG_2DEG[key] = torch.from_numpy(_TRIG_2DEG["host"]).to(device)
-    return _TRIG_2DEG[key]
+        return np.stack([np.cos(t), np.sin(t)], 1).astype(np.float32)
+    return _cached_table(_TRIG_2DEG, make, device)
 
 
 def warp_fwd(params):

@@ -9,6 +9,7 @@
 //
 // Frames are [N][H][W] fp32 (single channel, values in [-1,1]).
 #include "common.h"
+#include "counter_rng.h"
 
 #define MAX_RECTS 6
 
@@ -135,17 +136,13 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const float* __restric
 
 // Dropout(0.1) of the stem (spnet/models.py:340): y = x * keep/(1-rate) with a counter-based hash RNG
 // so that the mask is a pure function of (seed, element index) and can be regenerated in backward.
-__device__ __forceinline__ uint32_t hash_u32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
-}
 __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x,
                                                       float* __restrict__ y, long n, uint32_t seed,
                                                       uint32_t thresh, float scale,
                                                       const uint32_t* __restrict__ seed_dev) {
   if (seed_dev) seed = seed_dev[0];   // per-step seed read from device memory (hipGraph replay)
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const uint32_t h = hash_u32((uint32_t)i * 0x9e3779b9U + seed);
+    const uint32_t h = rng_mix((uint32_t)i * 0x9e3779b9U + seed);
     y[i] = (h >= thresh) ? x[i] * scale : 0.f;
   }
 }

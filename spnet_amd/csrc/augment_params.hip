@@ -22,8 +22,6 @@
 #define AUGP_SLOT_POINTS 8
 #define AUGP_ANGLE_MID 2048   // angle index k in 0 .. 4096, angle = (k - 2048) * (20 / 2048) degrees
 
-__device__ __forceinline__ float augp_u01(unsigned h) { return (float)(h >> 8) * (1.f / 16777216.f); }
-
 __global__ __launch_bounds__(256) void augment_params_kernel(unsigned seed, unsigned epoch, const int* __restrict__ sample,
                                                              int B, int H, int W, int n_salt, int n_pepper,
                                                              const float* __restrict__ mm, int n_frames,
@@ -43,7 +41,7 @@ __global__ __launch_bounds__(256) void augment_params_kernel(unsigned seed, unsi
     const int n = rng_randint(rng_draw(k0, 0), 0, AUGP_MAX_RECTS);
     const int sp = (int)(rng_draw(k0, 1) >> 31);
     int ks = 0;
-    if ((double)augp_u01(rng_draw(k0, 2)) < 0.4 && (double)augp_u01(rng_draw(k0, 3)) <= 0.3)
+    if ((double)rng_u01(rng_draw(k0, 2)) < 0.4 && (double)rng_u01(rng_draw(k0, 3)) <= 0.3)
       ks = (rng_draw(k0, 4) >> 31) ? 7 : 3;
     // the fill range is the pristine frame's (the table row of the SAMPLE; an index outside the table reads its nearest row)
     const int row = min(max(s, 0), n_frames - 1);
@@ -56,7 +54,7 @@ __global__ __launch_bounds__(256) void augment_params_kernel(unsigned seed, unsi
       const int r0 = rng_randint(rng_draw(kr, 0), 0, H - 12), c0 = rng_randint(rng_draw(kr, 1), 0, W - 12);
       const int dr = rng_randint(rng_draw(kr, 2), 11, 74), dc = rng_randint(rng_draw(kr, 3), 11, 74);
       const int r1 = min(r0 + dr, H - 1), c1 = min(c0 + dc, W - 1);
-      const float fill = lo + augp_u01(rng_draw(kr, 4)) * (hi - lo);
+      const float fill = lo + rng_u01(rng_draw(kr, 4)) * (hi - lo);
       if (r < n) {
         if ((lane >> 2) == r) rv = (lane & 3) == 0 ? r0 : (lane & 3) == 1 ? r1 : (lane & 3) == 2 ? c0 : c1;
         if (lane == r) fv = fill;
@@ -87,8 +85,8 @@ __global__ __launch_bounds__(256) void augment_params_kernel(unsigned seed, unsi
     const int k = rng_randint(rng_draw(kw, 1), 0, 2 * AUGP_ANGLE_MID);
     int xt = 0, yt = 0;
     if (rng_randint(rng_draw(kw, 2), 0, 9) != 0) {
-      const double ux = (double)(rng_draw(kw, 3) >> 8) * (1.0 / 16777216.0);
-      const double uy = (double)(rng_draw(kw, 4) >> 8) * (1.0 / 16777216.0);
+      const double ux = rng_u01_double(rng_draw(kw, 3));
+      const double uy = rng_u01_double(rng_draw(kw, 4));
       xt = (int)rint(40.0 * (2.0 * ux - 1.0));
       yt = (int)rint(40.0 * (2.0 * uy - 1.0));
     }

@@ -12,15 +12,8 @@
 // Frames are statistically, not bitwise, those of the OpenCV rasteriser (outline distance is the first-order
 // distance |F-1|/|grad F| to the implicit ellipse / the band's normal distance |dy|/sqrt(1+y'^2)).
 #include "common.h"
-
-#define ESPI_MAX_NODES 7
-#define ESPI_NODE_STRIDE 8    // cx, cy, a, b, angle_deg, rings, start (0/1), valid
-#define ESPI_WAVE_STRIDE 5    // amp, wavelength, thickness, slope, spacing
-
-__device__ __forceinline__ unsigned espi_hash(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
+#include "counter_rng.h"
+#include "espi_layout.h"
 
 __global__ __launch_bounds__(256) void fake_espi_kernel(const float* __restrict__ waves,
                                                         const float* __restrict__ nodes,
@@ -75,8 +68,8 @@ __global__ __launch_bounds__(256) void fake_espi_kernel(const float* __restrict_
   }
   if (noise) {
     const unsigned pix = ((unsigned)f * (unsigned)H + (unsigned)y) * (unsigned)W + (unsigned)x;
-    const unsigned h1 = espi_hash(pix * 0x9e3779b9u + seed), h2 = espi_hash(h1 ^ 0x85ebca6bu), h3 = espi_hash(h2 + 0xc2b2ae35u);
-    const float u1 = ((float)(h1 >> 8) + 1.f) * (1.f / 16777217.f), u2 = (float)(h2 >> 8) * (1.f / 16777216.f);
+    const unsigned h1 = rng_mix(pix * 0x9e3779b9u + seed), h2 = rng_mix(h1 ^ 0x85ebca6bu), h3 = rng_mix(h2 + 0xc2b2ae35u);
+    const float u1 = ((float)(h1 >> 8) + 1.f) * (1.f / 16777217.f), u2 = rng_u01(h2);
     const float n = 40.f + 40.f * sqrtf(-2.f * __logf(u1)) * __cosf(6.283185307179586f * u2);
     val = fminf(val + fminf(fmaxf(rintf(n), 0.f), 255.f), 255.f);      // cv2.randn into uint8 saturates; cv2.add too
     if (h3 & 0x10000u) val = 0.f;                                      // np.random.choice([0,1]) mask

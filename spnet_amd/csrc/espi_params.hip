@@ -17,29 +17,16 @@
 // the square root is taken in double and rounded to float, which is the correctly rounded float root (53 >= 2 * 24 + 2
 // bits: the double rounding is harmless).
 #include "common.h"
+#include "counter_rng.h"
+#include "espi_layout.h"
 #pragma clang fp contract(off)
 
-#define ESPI_MAX_NODES 7
-#define ESPI_NODE_STRIDE 8    // cx, cy, a, b, angle_deg, rings, start (0/1), valid
-#define ESPI_WAVE_STRIDE 5    // amp, wavelength, thickness, slope, spacing
 #define ESPI_MAX_TRIES 2000   // candidates per antinode: try 0 (the first draw) and 1999 retries
 #define ESPI_MIN_LINE_WIDTH 4
 
-__device__ __forceinline__ unsigned espi_hash(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
 // key of one (frame, slot, try): slot 0 = the frame's own draws, slot j + 1 = antinode j
 __device__ __forceinline__ unsigned espi_key(unsigned frame_key, int slot, int t) {
-  return espi_hash(frame_key + (((unsigned)slot << 12) | (unsigned)t));
-}
-__device__ __forceinline__ unsigned espi_draw(unsigned key, unsigned k) {
-  return espi_hash(key ^ (k * 0x85ebca6bu + 0xc2b2ae35u));
-}
-// integer in [lo, hi] by multiply-shift; an empty range gives lo
-__device__ __forceinline__ int espi_randint(unsigned u, int lo, int hi) {
-  const int n = max(hi - lo + 1, 1);
-  return lo + (int)(((unsigned long long)u * (unsigned long long)(unsigned)n) >> 32);
+  return rng_mix(frame_key + (((unsigned)slot << 12) | (unsigned)t));
 }
 __device__ __forceinline__ float espi_sqrt_rn(float v) { return (float)sqrt((double)v); }
 
@@ -56,18 +43,18 @@ __global__ __launch_bounds__(256) void fake_espi_params_kernel(long first_frame,
   const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (f >= N) return;                                   // the whole wave leaves together
   const unsigned long long g = (unsigned long long)(first_frame + f);
-  const unsigned fkey = espi_hash(espi_hash(espi_hash(seed ^ 0x9e3779b9u) + (unsigned)g) ^ (unsigned)(g >> 32));
+  const unsigned fkey = rng_mix(rng_mix(rng_mix(seed ^ 0x9e3779b9u) + (unsigned)g) ^ (unsigned)(g >> 32));
 
   // ---- the wave train and the antinode count (slot 0; every lane computes the same values)
   const unsigned k0 = espi_key(fkey, 0, 0);
-  const int amp = espi_randint(espi_draw(k0, 0), 10, 200);
-  const int wavelength = espi_randint(espi_draw(k0, 1), 100, W / 2);
-  const int thick = espi_randint(espi_draw(k0, 2), 15, 40);
-  const float u01 = (float)(espi_draw(k0, 3) >> 8) * (1.f / 16777216.f);
+  const int amp = rng_randint(rng_draw(k0, 0), 10, 200);
+  const int wavelength = rng_randint(rng_draw(k0, 1), 100, W / 2);
+  const int thick = rng_randint(rng_draw(k0, 2), 15, 40);
+  const float u01 = rng_u01(rng_draw(k0, 3));
   const float slope = 3.f * (u01 - 0.5f);
   const int steep = (int)fabsf(1.5f * slope);
-  const int spacing = espi_randint(espi_draw(k0, 4), thick + thick * steep, H / 3);
-  const int count = espi_randint(espi_draw(k0, 5), count_lo, count_hi);
+  const int spacing = rng_randint(rng_draw(k0, 4), thick + thick * steep, H / 3);
+  const int count = rng_randint(rng_draw(k0, 5), count_lo, count_hi);
   if (lane < ESPI_WAVE_STRIDE) {
     const float v = lane == 0 ? (float)amp : lane == 1 ? (float)wavelength : lane == 2 ? (float)thick
                   : lane == 3 ? slope : (float)spacing;
@@ -85,28 +72,28 @@ __global__ __launch_bounds__(256) void fake_espi_params_kernel(long first_frame,
   for (int j = 0; j < ESPI_MAX_NODES; ++j) {
     int accepted_t = j < count ? -1 : -2;
     if (j < count) {
-      const int start = (int)(espi_draw(espi_key(fkey, j + 1, 0), 6) >> 31);
+      const int start = (int)(rng_draw(espi_key(fkey, j + 1, 0), 6) >> 31);
       int carry = 0x7fffffff;                           // running minimum of the ring count over the tries so far
 #pragma unroll 1
       for (int r = 0; r < (ESPI_MAX_TRIES + 63) / 64; ++r) {
         const int t = 64 * r + lane;
         const unsigned key = espi_key(fkey, j + 1, t);
         const bool first = (t == 0);
-        const int a1 = first ? espi_randint(espi_draw(key, 0), 15, (2 * W) / 7) : espi_randint(espi_draw(key, 0), 25, W / 3);
-        const int a2 = first ? espi_randint(espi_draw(key, 1), 15, (2 * H) / 7) : espi_randint(espi_draw(key, 1), 25, H / 3);
+        const int a1 = first ? rng_randint(rng_draw(key, 0), 15, (2 * W) / 7) : rng_randint(rng_draw(key, 0), 25, W / 3);
+        const int a2 = first ? rng_randint(rng_draw(key, 1), 15, (2 * H) / 7) : rng_randint(rng_draw(key, 1), 25, H / 3);
         const int a = max(a1, a2), b = min(a1, a2);
         // ring count: drawn with the first candidate, then min(rings, b / 4) at every retry (b / rings >= 4)
         int rmin = b / ESPI_MIN_LINE_WIDTH;
-        if (first) rmin = min(rmin, espi_randint(espi_draw(key, 2), 1, min(b / 8, 11)));
+        if (first) rmin = min(rmin, rng_randint(rng_draw(key, 2), 1, min(b / 8, 11)));
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
           const int o = __shfl_up(rmin, off, 64);
           if (lane >= off) rmin = min(rmin, o);
         }
         const int rings = min(carry, rmin);
-        const int cx = espi_randint(espi_draw(key, 3), a, W - a);
-        const int cy = espi_randint(espi_draw(key, 4), b, H - b);
-        const int ang = espi_randint(espi_draw(key, 5), 1, first ? 179 : 180);
+        const int cx = rng_randint(rng_draw(key, 3), a, W - a);
+        const int cy = rng_randint(rng_draw(key, 4), b, H - b);
+        const int ang = rng_randint(rng_draw(key, 5), 1, first ? 179 : 180);
         const float c2 = trig2[2 * ang], s2 = trig2[2 * ang + 1];
         const float fa2 = (float)a * (float)a, fb2 = (float)b * (float)b;
         const float dx = espi_sqrt_rn(fa2 * c2 + fb2 * s2);

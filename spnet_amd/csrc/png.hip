@@ -19,6 +19,7 @@
 //                    stored.  OR is commutative, so the bytes do not depend on the order in which threads arrive.  Nothing
 //                    waits on another workgroup.  Every write is checked against the end of the frame's slot.
 #include "common.h"
+#include "deflate_bits.h"
 
 namespace {
 
@@ -28,14 +29,6 @@ constexpr int PNG_SPT = 16;                 // symbols per thread per tile: one 
 constexpr int PNG_TILE = PNG_T * PNG_SPT;
 constexpr int PNG_NSYM = 257;               // 256 literals + end of block
 constexpr int PNG_HDR_WORDS = 64;           // 2048 bits: 3 + 14 + 19 * 3 + 258 * 7 = 1880 is the longest header
-constexpr unsigned ADLER_MOD = 65521u;
-constexpr long PNG_MAX_STREAM = (1L << 27); // 15 bits per symbol stay inside 31-bit counts
-
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(PNG_T) void png_hist_kernel(const unsigned char* __restrict__ src, int H, int rb,
                                                          uint32_t* __restrict__ hist, uint32_t* __restrict__ adler) {
@@ -49,7 +42,8 @@ __global__ __launch_bounds__(PNG_T) void png_hist_kernel(const unsigned char* __
   const long nsrc = (long)H * rb, L = nsrc + H;
   const unsigned char* p = src + n * nsrc;
   unsigned* h = s_h[wave];
-  // pixel byte j sits in row j / rb, at stream index j + row + 1; the row is carried, not divided out again
+  // pixel byte j sits in row j / rb, at stream index j + row + 1; the row is carried, not divided out again (written out:
+  // RowCursor gives this kernel other code)
   long row = tid / rb;
   int col = tid % rb;
   const int qstep = PNG_T / rb, rstep = PNG_T % rb;
@@ -91,15 +85,6 @@ struct PackArgs {
   int H, rb;
 };
 
-// nb (1..32) bits of v at bit position pos of the output, which fills every byte from its least significant bit (the
-// buffer is little-endian words, so bit pos of the stream is bit pos % 32 of word pos / 32).  Dropped past `limit`.
-__device__ __forceinline__ void or_bits(uint32_t* out, unsigned long long pos, unsigned long long limit, uint32_t v, int nb) {
-  if (pos + (unsigned)nb > limit) return;
-  const unsigned sh = (unsigned)(pos & 31);
-  atomicOr(out + (pos >> 5), v << sh);
-  if (sh + (unsigned)nb > 32u) atomicOr(out + (pos >> 5) + 1, v >> (32u - sh));
-}
-
 __global__ __launch_bounds__(PNG_T) void png_pack_kernel(const PackArgs a) {
   __shared__ uint32_t s_code[PNG_NSYM];                   // length << 16 | code, bit-reversed: first code bit in bit 0
   __shared__ __align__(16) unsigned char s_sym[PNG_TILE];
@@ -113,45 +98,26 @@ __global__ __launch_bounds__(PNG_T) void png_pack_kernel(const PackArgs a) {
 
   for (int s = tid; s < PNG_NSYM; s += PNG_T) {
     const uint32_t c = a.codes[n * PNG_NSYM + s];
-    const unsigned len = (c >> 16) & 15u;
-    const unsigned code = c & ((1u << len) - 1u);
-    s_code[s] = (len << 16) | (len ? (__brev(code) >> (32u - len)) : 0u);
+    s_code[s] = code_table_entry(c);
   }
 
-  // zlib header (deflate, 32 KiB window, no preset dictionary, level 0: 0x78 0x01), then the block header's bits
   const int hb = min(max(a.header_bits[n], 0), PNG_HDR_WORDS * 32);
-  const unsigned long long base = ((unsigned long long)o0 + 2ull) * 8ull;
-  if (tid == PNG_HDR_WORDS) or_bits(out, (unsigned long long)o0 * 8ull, limit, 0x78u, 8);
-  if (tid == PNG_HDR_WORDS + 1) or_bits(out, (unsigned long long)o0 * 8ull + 8ull, limit, 0x01u, 8);
-  if (tid < PNG_HDR_WORDS) {
-    const int nb = min(hb - 32 * tid, 32);
-    if (nb > 0) {
-      uint32_t w = a.header[n * PNG_HDR_WORDS + tid];
-      if (nb < 32) w &= (1u << nb) - 1u;
-      or_bits(out, base + 32ull * tid, limit, w, nb);
-    }
-  }
+  // bit position of the tile's first symbol
+  unsigned long long carry = write_stream_head<PNG_HDR_WORDS>(out, o0, limit, a.header + n * PNG_HDR_WORDS, hb, tid);
 
   const int rb = a.rb, rb1 = rb + 1;
   const long nsrc = (long)a.H * rb, L = nsrc + a.H;
   const unsigned char* p = a.src + n * nsrc;
   // stream index tid + 1024 m of the m-th staging step: row / column carried across steps and tiles
-  long row = tid / rb1;
-  int col = tid % rb1;
-  const int qstep = PNG_T / rb1, rstep = PNG_T % rb1;
-  unsigned long long carry = base + (unsigned)hb;                          // bit position of the tile's first symbol
+  RowCursor<PNG_T> c(tid, rb1);
   __syncthreads();
 
   for (long tile = 0; tile < L; tile += PNG_TILE) {
 #pragma unroll
     for (int k = 0; k < PNG_SPT; ++k) {
       const long i = tile + (long)k * PNG_T + tid;
-      unsigned char d = 0;
-      if (i < L && col > 0) d = p[row * rb + (col - 1)];
-      s_sym[k * PNG_T + tid] = d;
-      row += qstep;
-      col += rstep;
-      if (col >= rb1) { col -= rb1; ++row; }
+      s_sym[k * PNG_T + tid] = stream_byte(p, rb, c, i < L);
+      c.step();
     }
     __syncthreads();
 
@@ -213,11 +179,6 @@ __global__ __launch_bounds__(PNG_T) void png_pack_kernel(const PackArgs a) {
     const int k = tid - 64;
     or_bits(out, tail + 8ull * k, limit, (a.adler[n] >> (24 - 8 * k)) & 255u, 8);
   }
-}
-
-bool png_shape_ok(int N, int H, int W, int channels) {
-  if (N < 0 || H < 1 || W < 1 || channels < 1 || channels > 4) return false;
-  return (long)H * ((long)W * channels + 1) <= PNG_MAX_STREAM;
 }
 
 }  // namespace

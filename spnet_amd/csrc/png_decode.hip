@@ -19,6 +19,7 @@
 //                       segment sums).  Average / Paeth: serial along the row, one lane per channel (the chains of the bpp
 //                       channels are independent).
 #include "common.h"
+#include "deflate_bits.h"
 #include "inflate_core.h"
 
 namespace {
@@ -28,15 +29,7 @@ constexpr int PD_WINDOW = 32768;
 constexpr int PD_WMASK = PD_WINDOW - 1;
 constexpr int PD_STAGE = 1024;              // compressed bytes staged at a time (+ 4 so that in32 reads whole words)
 constexpr int PD_FLUSH = 16384;             // flush once this much is unflushed: 16384 + 258 < 32768 - 258
-constexpr unsigned PD_ADLER_MOD = 65521u;
-constexpr long PD_MAX_STREAM = (1L << 27);
 constexpr int PD_MAX_ROW = 32768;           // W * channels of spnet_png_unfilter: two rows in LDS
-
-__device__ __forceinline__ unsigned pd_wave_sum(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off, 64);
-  return v;
-}
 
 struct LdsIO {
   const unsigned char* src;     // the file's zlib stream
@@ -88,10 +81,10 @@ struct LdsIO {
       sa += d;
       sb += (unsigned long long)d * (unsigned)(n - i);
     }
-    const unsigned ta = pd_wave_sum((unsigned)(sa % PD_ADLER_MOD));        // 64 values below 2^16
-    const unsigned tb = pd_wave_sum((unsigned)(sb % PD_ADLER_MOD));
-    b = (unsigned)((b + (unsigned long long)n * a + tb) % PD_ADLER_MOD);
-    a = (a + ta) % PD_ADLER_MOD;
+    const unsigned ta = wave_sum_u32((unsigned)(sa % ADLER_MOD));           // 64 values below 2^16
+    const unsigned tb = wave_sum_u32((unsigned)(sb % ADLER_MOD));
+    b = (unsigned)((b + (unsigned long long)n * a + tb) % ADLER_MOD);
+    a = (a + ta) % ADLER_MOD;
     flushed = op;
     __syncthreads();
   }
@@ -205,7 +198,7 @@ __global__ __launch_bounds__(PD_T) void png_unfilter_kernel(const unsigned char*
 
 extern "C" int spnet_png_inflate(const unsigned char* blob, long blob_bytes, const long long* offsets, int N, long L,
                                  long out_stride, unsigned char* out, int* status, void* stream) {
-  if (N < 0 || L < 1 || L > PD_MAX_STREAM || out_stride < L || blob_bytes < 0) return (int)hipErrorInvalidValue;
+  if (N < 0 || L < 1 || L > PNG_MAX_STREAM || out_stride < L || blob_bytes < 0) return (int)hipErrorInvalidValue;
   if (!blob || !offsets || !out || !status) return (int)hipErrorInvalidValue;
   if (((uintptr_t)offsets & 7) || ((uintptr_t)status & 3)) return (int)hipErrorInvalidValue;
   if (N == 0) return 0;
@@ -218,7 +211,7 @@ extern "C" int spnet_png_unfilter(const unsigned char* inflated, long in_stride,
                                   unsigned char* first, unsigned char* all, int* status, void* stream) {
   if (N < 0 || H < 1 || W < 1 || channels < 1 || channels > 4) return (int)hipErrorInvalidValue;
   const long rb = (long)W * channels, L = (long)H * (rb + 1);
-  if (rb > PD_MAX_ROW || L > PD_MAX_STREAM || in_stride < L) return (int)hipErrorInvalidValue;
+  if (rb > PD_MAX_ROW || L > PNG_MAX_STREAM || in_stride < L) return (int)hipErrorInvalidValue;
   if (!inflated || !status || (!first && !all) || ((uintptr_t)status & 3)) return (int)hipErrorInvalidValue;
   if (N == 0) return 0;
   const int rbp = (int)((rb + 15) / 16 * 16);

@@ -39,6 +39,7 @@
 // Registers: both instantiations compile to exactly 128 VGPRs for gfx950, the ceiling for 1024 threads, with no scratch
 // (the packer spills some SGPRs); there is no headroom, so anything added to the walk's st[16] / ex[16] arrays goes to scratch.
 #include "common.h"
+#include "deflate_bits.h"
 
 namespace {
 
@@ -58,7 +59,6 @@ constexpr int LZ_WINDOW = 32768;
 constexpr int LZ_MAX_LEN = 258;
 constexpr int LZ_NEAR = 1024;
 constexpr int LZ_PIXEL_MULTIPLES = 8;
-constexpr long LZ_MAX_STREAM = (1L << 27);
 
 struct LzArgs {
   const unsigned char* src;
@@ -74,13 +74,6 @@ struct LzArgs {
   uint32_t* dhist;
   int H, rb, channels;
 };
-
-__device__ __forceinline__ void lz_or_bits(uint32_t* out, unsigned long long pos, unsigned long long limit, uint32_t v, int nb) {
-  if (pos + (unsigned)nb > limit) return;
-  const unsigned sh = (unsigned)(pos & 31);
-  atomicOr(out + (pos >> 5), v << sh);
-  if (sh + (unsigned)nb > 32u) atomicOr(out + (pos >> 5) + 1, v >> (32u - sh));
-}
 
 // RFC 1951 section 3.2.5: symbol, number of extra bits and their value of a length 3 .. 258 / a distance 1 .. 32768
 __device__ __forceinline__ void lz_length_symbol(int len, unsigned& sym, unsigned& eb, unsigned& ev) {
@@ -127,23 +120,10 @@ __global__ __launch_bounds__(LZ_T) void png_lz_kernel(const LzArgs a) {
     limit = (unsigned long long)o1 * 8ull;
     for (int s = tid; s < LZ_NSYM; s += LZ_T) {
       const uint32_t c = (s < LZ_NLL) ? a.lcodes[n * LZ_NLL + s] : a.dcodes[n * LZ_ND + (s - LZ_NLL)];
-      const unsigned len = (c >> 16) & 15u;
-      const unsigned code = c & ((1u << len) - 1u);
-      s_tab[s] = (len << 16) | (len ? (__brev(code) >> (32u - len)) : 0u);
+      s_tab[s] = code_table_entry(c);
     }
     const int hb = min(a.header_bits[n], LZ_HDR_WORDS * 32);
-    const unsigned long long base = ((unsigned long long)o0 + 2ull) * 8ull;
-    if (tid == LZ_HDR_WORDS) lz_or_bits(out, (unsigned long long)o0 * 8ull, limit, 0x78u, 8);
-    if (tid == LZ_HDR_WORDS + 1) lz_or_bits(out, (unsigned long long)o0 * 8ull + 8ull, limit, 0x01u, 8);
-    if (tid < LZ_HDR_WORDS) {
-      const int nb = min(hb - 32 * tid, 32);
-      if (nb > 0) {
-        uint32_t w = a.header[n * LZ_HDR_WORDS + tid];
-        if (nb < 32) w &= (1u << nb) - 1u;
-        lz_or_bits(out, base + 32ull * tid, limit, w, nb);
-      }
-    }
-    carry = base + (unsigned)hb;
+    carry = write_stream_head<LZ_HDR_WORDS>(out, o0, limit, a.header + n * LZ_HDR_WORDS, hb, tid);
   } else {
     for (int s = tid; s < LZ_NSYM; s += LZ_T) s_tab[s] = 0u;
   }
@@ -152,9 +132,7 @@ __global__ __launch_bounds__(LZ_T) void png_lz_kernel(const LzArgs a) {
   const int rb = a.rb, rb1 = rb + 1, ch = a.channels;
   const long nsrc = (long)a.H * rb, L = nsrc + a.H;
   const unsigned char* src = a.src + n * nsrc;
-  long row = tid / rb1;                                   // stream index tid + 1024 m of the m-th staging step
-  int col = tid % rb1;
-  const int qstep = LZ_T / rb1, rstep = LZ_T % rb1;
+  RowCursor<LZ_T> cur(tid, rb1);                          // stream index tid + 1024 m of the m-th staging step
   const int wbase = wave * LZ_SEG;
   __syncthreads();
 
@@ -165,12 +143,8 @@ __global__ __launch_bounds__(LZ_T) void png_lz_kernel(const LzArgs a) {
 #pragma unroll
     for (int k = 0; k < LZ_TILE / LZ_T; ++k) {
       const long i = tile + (long)k * LZ_T + tid;
-      unsigned char d = 0;
-      if (i < L && col > 0) d = src[row * rb + (col - 1)];
-      s_ring[sbase + k * LZ_T + tid] = d;
-      row += qstep;
-      col += rstep;
-      if (col >= rb1) { col -= rb1; ++row; }
+      s_ring[sbase + k * LZ_T + tid] = stream_byte(src, rb, cur, i < L);
+      cur.step();
     }
     if (tid < 2) {
       const long i = tile + LZ_TILE + tid;
@@ -344,6 +318,7 @@ __global__ __launch_bounds__(LZ_T) void png_lz_kernel(const LzArgs a) {
         fields(o, step, f0, n0, f1, n1);
         bits += n0 + n1;
       });
+      // (scan, accumulator and tail are written out as in png.hip: as shared functions they change this kernel's code)
       unsigned incl = bits;
 #pragma unroll
       for (int off = 1; off < 64; off <<= 1) {
@@ -398,25 +373,20 @@ __global__ __launch_bounds__(LZ_T) void png_lz_kernel(const LzArgs a) {
   } else {
     // end of block, zero bits up to the next byte (the buffer arrives zeroed), Adler-32 most significant byte first
     const uint32_t eob = s_tab[256];
-    if (tid == 0 && (eob >> 16)) lz_or_bits(out, carry, limit, eob & 0xffffu, (int)(eob >> 16));
+    if (tid == 0 && (eob >> 16)) or_bits(out, carry, limit, eob & 0xffffu, (int)(eob >> 16));
     const unsigned long long tail = ((carry + (eob >> 16) + 7ull) >> 3) * 8ull;
     if (tid >= 64 && tid < 68) {
       const int k = tid - 64;
-      lz_or_bits(out, tail + 8ull * k, limit, (a.adler[n] >> (24 - 8 * k)) & 255u, 8);
+      or_bits(out, tail + 8ull * k, limit, (a.adler[n] >> (24 - 8 * k)) & 255u, 8);
     }
   }
-}
-
-bool lz_shape_ok(int N, int H, int W, int channels) {
-  if (N < 0 || H < 1 || W < 1 || channels < 1 || channels > 4) return false;
-  return (long)H * ((long)W * channels + 1) <= LZ_MAX_STREAM;
 }
 
 }  // namespace
 
 extern "C" int spnet_png_lz_scan(const unsigned char* src, int N, int H, int W, int channels, uint32_t* lhist, uint32_t* dhist,
                                  void* stream) {
-  if (!lz_shape_ok(N, H, W, channels) || !src || !lhist || !dhist) return (int)hipErrorInvalidValue;
+  if (!png_shape_ok(N, H, W, channels) || !src || !lhist || !dhist) return (int)hipErrorInvalidValue;
   if (((uintptr_t)lhist | (uintptr_t)dhist) & 3) return (int)hipErrorInvalidValue;
   if (N == 0) return 0;
   LzArgs a = {};
@@ -429,7 +399,7 @@ extern "C" int spnet_png_lz_pack(const unsigned char* src, int N, int H, int W, 
                                  const uint32_t* dcodes, const uint32_t* header, const int* header_bits,
                                  const long long* offsets, const uint32_t* adler, unsigned char* out, long out_bytes,
                                  void* stream) {
-  if (!lz_shape_ok(N, H, W, channels) || !src || !lcodes || !dcodes || !header || !header_bits || !offsets || !adler || !out)
+  if (!png_shape_ok(N, H, W, channels) || !src || !lcodes || !dcodes || !header || !header_bits || !offsets || !adler || !out)
     return (int)hipErrorInvalidValue;
   if (out_bytes < 0 || (out_bytes & 3)) return (int)hipErrorInvalidValue;            // whole 32-bit words
   if (((uintptr_t)lcodes | (uintptr_t)dcodes | (uintptr_t)header | (uintptr_t)header_bits | (uintptr_t)adler |

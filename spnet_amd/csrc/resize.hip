@@ -16,6 +16,7 @@
 // rows; the accumulators carry over.  Tables are clamped to the staged ranges: a table that is not lanczos_taps' of the
 // size pair gives wrong or unwritten pixels, never an out-of-range access.
 #include "common.h"
+#include "u8_tile.h"
 
 // Diagnostic builds only (tools/resize_time.py --knockouts builds and times them through tools/build_variant_lib.sh and
 // SPNET_HIP_LIB): knock-outs that say where the launch's time goes.  The results are wrong by design; the product
@@ -67,39 +68,6 @@ __device__ __forceinline__ unsigned mac(unsigned acc, unsigned pixel, int k) { r
 __device__ __forceinline__ unsigned finish(unsigned acc) {
   const int v = (int)(acc + (1u << (PREC - 1)));
   return (unsigned)(min(max(v, 0), (256 << PREC) - 1) >> PREC);
-}
-
-__device__ __forceinline__ void put4(unsigned char* p, unsigned v0, unsigned v1, unsigned v2, unsigned v3) {
-  *reinterpret_cast<unsigned*>(p) = v0 | (v1 << 8) | (v2 << 16) | (v3 << 24);
-}
-__device__ __forceinline__ void put4(float* p, unsigned v0, unsigned v1, unsigned v2, unsigned v3) {
-  if (KO & 16) { *reinterpret_cast<float4*>(p) = make_float4((float)v0, (float)v1, (float)v2, (float)v3); return; }
-  *reinterpret_cast<float4*>(p) = make_float4(spnet_u8_to_input_f(v0), spnet_u8_to_input_f(v1), spnet_u8_to_input_f(v2),
-                                              spnet_u8_to_input_f(v3));
-}
-__device__ __forceinline__ void put1(unsigned char* p, unsigned v) { *p = (unsigned char)v; }
-__device__ __forceinline__ void put1(float* p, unsigned v) { *p = spnet_u8_to_input_f(v); }
-
-// nro rows of tw bytes (LDS, pitch pm) -> out[row0 + row * OW + 0 .. tw): groups of 4 elements that start where
-// (address / sizeof(T)) % 4 == 0 are one vector store, the clipped groups at a row's ends go element by element
-template <class T>
-__device__ __forceinline__ void store_tile(T* __restrict__ out, const unsigned char* __restrict__ so, int pm, long row0, int OW,
-                                           int nro, int tw, int nq, int tid) {
-  const long sh = (long)(((uintptr_t)out / sizeof(T)) & 3);
-  for (int i = tid; i < nro * nq; i += 256) {
-    const int row = i / nq, q = i - row * nq;
-    const long e0 = row0 + (long)row * OW;                                // the row's first element
-    const long e = ((((e0 + sh) >> 2) + q) << 2) - sh;
-    const int rel = (int)(e - e0);                                        // -3 .. tw + 3
-    if (rel >= tw) continue;
-    const unsigned char* p = so + (size_t)row * pm;
-    if (rel >= 0 && rel + 4 <= tw) {
-      put4(out + e, p[rel], p[rel + 1], p[rel + 2], p[rel + 3]);
-    } else {
-      for (int k = 0; k < 4; ++k)
-        if (rel + k >= 0 && rel + k < tw) put1(out + e + k, p[rel + k]);
-    }
-  }
 }
 
 template <int XT>
@@ -237,7 +205,7 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(const ResizeArgs a) {
   const long row0 = ((long)n * a.OH + r0) * a.OW + c0;                    // the tile's first element
   if ((KO & 2) && a.N > 0 && so[tid] != 77) return;                       // (keeps the work above alive)
   if (a.out_u8) store_tile<unsigned char>(a.out_u8, so, a.pm, row0, a.OW, nro, tw, a.TWD + 1, tid);
-  if (a.out_f) store_tile<float>(a.out_f, so, a.pm, row0, a.OW, nro, tw, a.TWD + 1, tid);
+  if (a.out_f) store_tile<float, (KO & 16) != 0>(a.out_f, so, a.pm, row0, a.OW, nro, tw, a.TWD + 1, tid);
 }
 
 }  // namespace

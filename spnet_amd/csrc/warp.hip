@@ -18,6 +18,7 @@
 //   store   the tile goes through LDS so that lanes own ALIGNED groups of 4 elements in memory: one dword of out_u8 and /
 //           or one float4 of out_f per lane (rows of any W start at any alignment)
 #include "common.h"
+#include "u8_tile.h"
 
 // Diagnostic builds only (tools/warp_time.py --knockouts through tools/build_variant_lib.sh and SPNET_HIP_LIB): where the
 // launch's time goes.  The results are wrong by design; the product library is built without the macro.
@@ -54,40 +55,6 @@ struct WarpArgs {
 
 __device__ __forceinline__ int term(double v) {          // cvRound, saturated
   return (int)fmin(fmax(rint(v), -(double)TERM_LIM), (double)TERM_LIM);
-}
-
-__device__ __forceinline__ void put4(unsigned char* p, unsigned v0, unsigned v1, unsigned v2, unsigned v3) {
-  *reinterpret_cast<unsigned*>(p) = v0 | (v1 << 8) | (v2 << 16) | (v3 << 24);
-}
-__device__ __forceinline__ void put4(float* p, unsigned v0, unsigned v1, unsigned v2, unsigned v3) {
-  *reinterpret_cast<float4*>(p) = make_float4(spnet_u8_to_input_f(v0), spnet_u8_to_input_f(v1), spnet_u8_to_input_f(v2),
-                                              spnet_u8_to_input_f(v3));
-}
-__device__ __forceinline__ void put1(unsigned char* p, unsigned v) { *p = (unsigned char)v; }
-__device__ __forceinline__ void put1(float* p, unsigned v) { *p = spnet_u8_to_input_f(v); }
-
-// nro rows of tw bytes (LDS, pitch OP) -> out[row0 + row * W + 0 .. tw): groups of 4 elements that start where
-// (address / sizeof(T)) % 4 == 0 are one vector store, the clipped groups at a row's ends go element by element
-// (the store of resize.hip)
-template <class T>
-__device__ __forceinline__ void store_tile(T* __restrict__ out, const unsigned char* __restrict__ so, long row0, int W, int nro,
-                                           int tw, int tid) {
-  const long sh = (long)(((uintptr_t)out / sizeof(T)) & 3);
-  const int nq = TWD + 1;
-  for (int i = tid; i < nro * nq; i += 256) {
-    const int row = i / nq, q = i - row * nq;
-    const long e0 = row0 + (long)row * W;
-    const long e = ((((e0 + sh) >> 2) + q) << 2) - sh;
-    const int rel = (int)(e - e0);                                        // -3 .. tw + 3
-    if (rel >= tw) continue;
-    const unsigned char* p = so + row * OP;
-    if (rel >= 0 && rel + 4 <= tw) {
-      put4(out + e, p[rel], p[rel + 1], p[rel + 2], p[rel + 3]);
-    } else {
-      for (int k = 0; k < 4; ++k)
-        if (rel + k >= 0 && rel + k < tw) put1(out + e + k, p[rel + k]);
-    }
-  }
 }
 
 __global__ __launch_bounds__(256) void warp_chain_u8_kernel(const WarpArgs a) {
@@ -226,8 +193,8 @@ __global__ __launch_bounds__(256) void warp_chain_u8_kernel(const WarpArgs a) {
   // ---- store: a lane owns 4 elements that share an aligned dword (out_u8) / float4 (out_f) IN MEMORY
   const long row0 = ((long)n * H + r0) * W + c0;
   if ((KO & 2) && a.N > 0 && s_out[tid] != 77) return;                    // (keeps the work above alive)
-  if (a.out_u8) store_tile<unsigned char>(a.out_u8, s_out, row0, W, nro, tw, tid);
-  if (a.out_f) store_tile<float>(a.out_f, s_out, row0, W, nro, tw, tid);
+  if (a.out_u8) store_tile<unsigned char>(a.out_u8, s_out, OP, row0, W, nro, tw, TWD + 1, tid);
+  if (a.out_f) store_tile<float>(a.out_f, s_out, OP, row0, W, nro, tw, TWD + 1, tid);
 }
 
 }  // namespace

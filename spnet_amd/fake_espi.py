@@ -139,6 +139,20 @@ def bandpass_seeds(n, seed, first=0):
     return [((s * 2654435761) ^ 0x5BD1E995) % (2 ** 32) for s in frame_seeds(n, seed, first)]
 
 
+def _cached_table(cache, make, device):
+    """A constant table computed once on the host (make() -> numpy array, in float64 arithmetic) and uploaded once per
+    device: the numpy array for device None, else the cached device tensor.  `cache` is the table's own dict."""
+    if "host" not in cache:
+        cache["host"] = make()
+    if device is None:
+        return cache["host"]
+    import torch
+    key = str(torch.device(device))
+    if key not in cache:
+        cache[key] = torch.from_numpy(cache["host"]).to(device)
+    return cache[key]
+
+
 _TRIG2 = {}
 
 
@@ -146,16 +160,10 @@ def trig2_table(device=None):
     """(cos^2, sin^2) of the whole degrees 0..180 as float32 [181,2], computed in float64: the table the device sampler's
     box test reads (spnet_fake_espi_params; no sinf / cosf on the device, so a host restatement has the same bits).
     device: a cached device tensor instead of the numpy array."""
-    if "host" not in _TRIG2:
+    def make():
         rad = np.radians(np.arange(181, dtype=np.float64))
-        _TRIG2["host"] = np.stack([np.cos(rad) ** 2, np.sin(rad) ** 2], 1).astype(np.float32)
-    if device is None:
-        return _TRIG2["host"]
-    import torch
-    key = str(torch.device(device))
-    if key not in _TRIG2:
-        _TRIG2[key] = torch.from_numpy(_TRIG2["host"]).to(device)
-    return _TRIG2[key]
+        return np.stack([np.cos(rad) ** 2, np.sin(rad) ** 2], 1).astype(np.float32)
+    return _cached_table(_TRIG2, make, device)
 
 
 def draw_params_device(n, seed=0, device="cuda:0", count_range=(1, 7), first_frame=0, want_tries=False):

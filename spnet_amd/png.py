@@ -222,10 +222,27 @@ def lz_block_header(ll, dl):
     return _dynamic_header(nl - 257, nd - 1, ll[:nl] + dl[:nd])
 
 
+def _header_row(header, words):
+    """A (bits as a Python int, bit count) header as a kernel reads it: uint32 [words] (bit i in bit i % 32 of word i // 32)
+    and the bit count."""
+    acc, n = header
+    return np.frombuffer(acc.to_bytes(words * 4, "little"), dtype="<u4").astype(np.uint32), n
+
+
 def header_words(lengths):
-    """The header as spnet_png_pack reads it: uint32 [64] (bit i in bit i % 32 of word i // 32) and its bit count."""
-    acc, n = block_header(lengths)
-    return np.frombuffer(acc.to_bytes(HEADER_WORDS * 4, "little"), dtype="<u4").astype(np.uint32), n
+    """The header as spnet_png_pack reads it: uint32 [64] and its bit count."""
+    return _header_row(block_header(lengths), HEADER_WORDS)
+
+
+def _code_set(counts):
+    """(lengths int64, codes uint32 as the kernels read them: canonical code | length << 16) of a symbol histogram."""
+    ln = np.array(_limited_lengths([int(c) for c in counts], 15), dtype=np.int64)
+    return ln, (canonical_codes(ln) | (ln << 16)).astype(np.uint32)
+
+
+def _zlib_size(bits):
+    """Bytes of a zlib stream whose one deflate block has `bits` bits: 2 of header, the block, 4 of Adler-32."""
+    return 2 + (int(bits) + 7) // 8 + 4
 
 
 def plan_frames(hist):
@@ -240,12 +257,11 @@ def plan_frames(hist):
     header_bits = np.zeros(N, np.int32)
     offsets = np.zeros(N + 1, np.int64)
     for n in range(N):
-        ln = huffman_code_lengths(hist[n])
+        ln, codes[n] = _code_set(list(hist[n]) + [1])                    # the end of block, once
         lengths[n] = ln
-        codes[n] = (canonical_codes(ln) | (ln << 16)).astype(np.uint32)
         header[n], header_bits[n] = header_words(ln)
         bits = int(header_bits[n]) + int((hist[n] * ln[:256]).sum()) + int(ln[EOB])
-        offsets[n + 1] = offsets[n] + 2 + (bits + 7) // 8 + 4
+        offsets[n + 1] = offsets[n] + _zlib_size(bits)
     return dict(lengths=lengths, codes=codes, header=header, header_bits=header_bits, offsets=offsets)
 
 
@@ -274,17 +290,13 @@ def plan_frames_lz(hist, lhist, dhist):
     lextra = np.array(LENGTH_EXTRA, np.int64)
     dextra = np.array(DIST_EXTRA, np.int64)
     for n in range(N):
-        ll = np.array(_limited_lengths([int(c) for c in lhist[n]], 15), np.int64)
-        dl = np.array(_limited_lengths([int(c) for c in dhist[n]], 15), np.int64)
+        ll, lcodes[n] = _code_set(lhist[n])
+        dl, dcodes[n] = _code_set(dhist[n])
         llengths[n], dlengths[n] = ll, dl
-        lcodes[n] = (canonical_codes(ll) | (ll << 16)).astype(np.uint32)
-        dcodes[n] = (canonical_codes(dl) | (dl << 16)).astype(np.uint32)
-        acc, nbits = lz_block_header(ll, dl)
-        header[n] = np.frombuffer(acc.to_bytes(LZ_HEADER_WORDS * 4, "little"), dtype="<u4")
-        bits = (nbits + int((lhist[n] * ll).sum()) + int((dhist[n] * dl).sum()) + int((lhist[n, NSYM:] * lextra).sum())
-                + int((dhist[n] * dextra).sum()))
-        header_bits[n] = nbits
-        lz_sizes[n] = 2 + (bits + 7) // 8 + 4
+        header[n], header_bits[n] = _header_row(lz_block_header(ll, dl), LZ_HEADER_WORDS)
+        bits = (int(header_bits[n]) + int((lhist[n] * ll).sum()) + int((dhist[n] * dl).sum())
+                + int((lhist[n, NSYM:] * lextra).sum()) + int((dhist[n] * dextra).sum()))
+        lz_sizes[n] = _zlib_size(bits)
     use_lz = lz_sizes < literal_sizes
     offsets = np.zeros(N + 1, np.int64)
     np.cumsum(np.where(use_lz, lz_sizes, literal_sizes), out=offsets[1:])
@@ -346,6 +358,16 @@ def frame_statistics(frames):
     return hist.cpu().numpy().view(np.uint32), adler
 
 
+def _upload(arrays, device):
+    """The arrays as ONE host-to-device copy, in their order (64-bit arrays first keep every one aligned): (the device
+    tensor that owns the bytes, the device pointer of every array)."""
+    import torch
+    parts = [np.ascontiguousarray(v).reshape(-1).view(np.uint8) for v in arrays]
+    dev = torch.from_numpy(np.concatenate(parts)).to(device)
+    at = np.cumsum([0] + [v.nbytes for v in parts[:-1]]) + dev.data_ptr()
+    return dev, [int(v) for v in at]
+
+
 def pack_frames(frames, plan, adler, out=None, base=0):
     """Runs spnet_png_pack: the zlib streams of `frames` into `out` (a ZEROED uint8 device tensor whose size is a multiple of
     4; None: allocated exactly, rounded up to a whole word) from byte `base` on.  Returns out."""
@@ -353,20 +375,14 @@ def pack_frames(frames, plan, adler, out=None, base=0):
     from . import _lib as L
     N, H, W, channels = _frames_shape(frames)
     frames = frames.contiguous()
-    offsets = plan["offsets"] + int(base)
+    offsets = (plan["offsets"] + int(base)).astype(np.int64)
     if out is None:
         out = torch.zeros(((int(offsets[-1]) + 3) // 4 * 4,), dtype=torch.uint8, device=frames.device)
-    # one upload: offsets (64-bit) first, then the 32-bit arrays
-    blob = np.concatenate([offsets.astype(np.int64).view(np.uint8), plan["codes"].reshape(-1).view(np.uint8),
-                           plan["header"].reshape(-1).view(np.uint8), plan["header_bits"].view(np.uint8)])
-    dev = torch.from_numpy(blob).to(frames.device)
-    p = dev.data_ptr()
-    p_codes = p + 8 * (N + 1)
-    p_header = p_codes + 4 * NSYM * N
-    p_bits = p_header + 4 * HEADER_WORDS * N
+    dev, (p_off, p_codes, p_header, p_bits) = _upload([offsets, plan["codes"], plan["header"], plan["header_bits"]],
+                                                      frames.device)
     with torch.cuda.device(frames.device):
-        L.spnet_png_pack(frames.data_ptr(), N, H, W, channels, p_codes, p_header, p_bits, p, adler.data_ptr(), out.data_ptr(),
-                         int(out.numel()), L.current_stream())
+        L.spnet_png_pack(frames.data_ptr(), N, H, W, channels, p_codes, p_header, p_bits, p_off, adler.data_ptr(),
+                         out.data_ptr(), int(out.numel()), L.current_stream())
     return out
 
 
@@ -392,16 +408,13 @@ def pack_frames_lz(frames, plan, adler, out=None, base=0):
     from . import _lib as L
     N, H, W, channels = _frames_shape(frames)
     frames = frames.contiguous()
-    offsets = plan["offsets"] + int(base)
+    offsets = (plan["offsets"] + int(base)).astype(np.int64)
     if out is None:
         out = torch.zeros(((int(offsets[-1]) + 3) // 4 * 4,), dtype=torch.uint8, device=frames.device)
     lit = plan["literal"]
-    parts = [offsets.astype(np.int64), plan["lcodes"], plan["dcodes"], plan["lz_header"], plan["lz_header_bits"], lit["codes"],
-             lit["header"], lit["header_bits"]]
-    blob = np.concatenate([np.ascontiguousarray(v).reshape(-1).view(np.uint8) for v in parts])        # one upload
-    dev = torch.from_numpy(blob).to(frames.device)
-    at = np.cumsum([0] + [v.nbytes for v in parts[:-1]]) + dev.data_ptr()
-    p_off, p_lc, p_dc, p_lh, p_lb, p_c, p_h, p_b = (int(v) for v in at)
+    dev, (p_off, p_lc, p_dc, p_lh, p_lb, p_c, p_h, p_b) = _upload(
+        [offsets, plan["lcodes"], plan["dcodes"], plan["lz_header"], plan["lz_header_bits"], lit["codes"], lit["header"],
+         lit["header_bits"]], frames.device)
     use = plan["use_lz"]
     frame_bytes = H * W * channels
     with torch.cuda.device(frames.device):

@@ -17,7 +17,7 @@ def trig2_table():
 
 
 def mix(x):
-    """espi_hash on uint32 arrays (or Python ints)."""
+    """The device mixer (rng_mix of csrc/counter_rng.h), restated, on uint32 arrays (or Python ints)."""
     if isinstance(x, int):
         x &= _M32
         x ^= x >> 16

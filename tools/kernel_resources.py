@@ -11,12 +11,27 @@ flt = sys.argv[2] if len(sys.argv) > 2 else ""
 inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I", os.path.dirname(src), "-I", inc,
                     "-c", src, "-o", "/tmp/_kr.o", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+
+
+def kernel_name(mangled):
+    """The demangled name without its parameter list: `(anonymous namespace)::` and template arguments are kept."""
+    d = subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.strip()
+    if not d.endswith(")"):
+        return d
+    depth = 0
+    for i in range(len(d) - 1, -1, -1):          # the parameter list is the last balanced (...) group
+        depth += (d[i] == ")") - (d[i] == "(")
+        if depth == 0:
+            return d[:i].removeprefix("void ")
+    return d
+
+
 cur = None
 rows = {}
 for line in r.stderr.splitlines():
     m = re.search(r"remark:\s+Function Name: (\S+)", line)
     if m:
-        cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
+        cur = kernel_name(m.group(1))
         rows[cur] = {}
         continue
     m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]|TotalSGPRs): (\d+)", line)

@@ -13,7 +13,8 @@ import spnet.config as cf
 
 def evaluate_network(model=None, weights_file="", datapath="Test/", fraction=1.0, log_dir="", batch_size=32,
                      pred_grid=[6, 6, 2], set_means_ranges=True, device_png=False, device_decode=False,
-                     device_overlay=False, device_png_lz=False):
+                     device_overlay=False, device_png_lz=False, device_jpeg=False, jpeg_quality=90, movie=None,
+                     movie_fps=5.0):
     np.random.seed(1)
     print("Getting data..., fraction = ", fraction)
     X_test, Y_test, test_file_list, pred_shape = build_dataset(
@@ -56,7 +57,9 @@ def evaluate_network(model=None, weights_file="", datapath="Test/", fraction=1.0
     make_sure_path_exists(log_dir)
     print("    Drawing sample ellipse images...")
     show_pred_ellipses(Yt, Yp, test_file_list, num_draw=m, log_dir=log_dir, out_csv=log_dir + 'hawley_spnet.csv',
-                       png="device-lz" if device_png_lz else "device" if device_png else "host",
+                       png="device-jpeg" if device_jpeg else "device-lz" if device_png_lz else "device" if device_png
+                       else "host",
+                       jpeg_quality=jpeg_quality, movie=movie, movie_fps=movie_fps,
                        draw="device" if device_overlay else "host",
                        device_decode=bool(device_decode and device_overlay))
     return model
@@ -84,14 +87,26 @@ if __name__ == '__main__':
                    help="(additive) draw the overlays (outlines, ring counts, file name) on the GPU: the same CSV and file "
                         "names, the same pixels away from outline edges; with --device_decode the frames are decoded there "
                         "too, with --device_png encoded there")
+    p.add_argument('--device_jpeg', action='store_true',
+                   help="(additive) write the overlays as steelpan_pred_NNNNN.jpg, baseline JPEG encoded on the GPU (lossy; "
+                        "not with --device_png / --device_png_lz)")
+    p.add_argument('--jpeg_quality', type=int, default=90, help="quality 1 .. 100 of --device_jpeg and --movie")
+    p.add_argument('--movie', default=None, metavar='PATH',
+                   help="(additive) also append every overlay, in order, to a Motion-JPEG AVI at PATH (encoded on the GPU)")
+    p.add_argument('--movie_fps', type=float, default=5.0, help="frames per second of --movie")
     args = p.parse_args()
+    if args.device_jpeg and (args.device_png or args.device_png_lz):
+        p.error("--device_jpeg writes .jpg files: not with --device_png / --device_png_lz")
+    if not 1 <= args.jpeg_quality <= 100:
+        p.error("--jpeg_quality is 1 .. 100")
     for attr, val in (("model_type", args.model_type), ("loss_type", args.loss_type)):
         if val is not None:
             setattr(cf, attr, val)
     model = evaluate_network(weights_file=args.weights, datapath=args.datapath + '/', fraction=args.fraction,
                              log_dir=args.logdir, batch_size=args.batch_size, device_png=args.device_png,
                              device_decode=args.device_decode, device_overlay=args.device_overlay,
-                             device_png_lz=args.device_png_lz)
+                             device_png_lz=args.device_png_lz, device_jpeg=args.device_jpeg, jpeg_quality=args.jpeg_quality,
+                             movie=args.movie, movie_fps=args.movie_fps)
     weights2name = "eval_end_weights.hdf5"
     print("Saving model to", weights2name)
     model.save_weights(weights2name)

@@ -733,6 +733,59 @@ int spnet_draw_overlays(const unsigned char* frames, int N, int H, int W, int ch
                         int n_cmd, const int* verts, int n_verts, const unsigned char* masks, long mask_bytes,
                         unsigned char* out, void* stream);
 
+/* ---- JPEG output (csrc/jpeg.hip): a lossy writer for the overlays show_pred_ellipses leaves behind (spnet/utils.py:132) and
+ *      the frames of the README's "Making a movie", for frames that are already in device memory ------------------------- */
+/* src: N uint8 frames [N][H][W][channels], no alignment asked.  channels 1: one component (grey); channels 3: RGB, coded as
+ * YCbCr 4:4:4 in interleaved MCUs of Y, Cb, Cr.  Baseline sequential DCT, 8 bit.  1 <= H, W <= 65,535 (SOF0's limit; no
+ * smaller bound on W) and N * intervals <= 2^31 - 1.  spnet_amd/jpeg.py is the host side (quantisation tables, header
+ * segments, offsets, EOI, the AVI container).  N == 0: nothing to do, success.  hipErrorInvalidValue (nothing launched) for a
+ * shape outside these limits, channels other than 1 or 3, a NULL pointer, qtables not 2-byte, sizes not 4-byte or offsets not
+ * 8-byte aligned.
+ *
+ * RESTART INTERVALS.  An MCU is one 8 x 8 block of every component; a frame has ceil(W/8) * ceil(H/8) of them in raster order
+ * (H and W are padded to the 8-grid by replicating the last row and column).  The scan is cut into intervals of
+ *     Ri = spnet_jpeg_restart_interval(W, channels) = min(ceil(W / 8), 64)
+ * MCUs -- one MCU row, capped at 64 (a wave owns an interval, a lane an MCU); the last interval may be shorter, and when
+ * ceil(W/8) > 64 intervals run across row ends.  spnet_jpeg_intervals(H, W, channels) = ceil(MCUs / Ri) is their number
+ * (both queries: -1 outside the limits).  An interval starts with all DC predictors 0, ends with 1-bits up to a byte
+ * boundary, and every 0xFF byte of it is followed by 0x00.  Interval i < intervals - 1 is followed by the marker FF D0+(i mod
+ * 8); nothing follows the last one.
+ *
+ * ARITHMETIC, integers only (>> is an arithmetic shift, / a truncating division of non-negative numbers):
+ *   colour   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *            Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16          (8421375 = 128 * 2^16 + 2^15 - 1)
+ *            Cr = ( 32768 R - 27439 G -  5329 B + 8421375) >> 16          each clamped to 0 .. 255; grey: the sample itself
+ *   kernel   K[u][x] = rint(2^12 a(u) cos((2x + 1) u pi / 16)), a(0) = sqrt(1/8), a(u > 0) = 1/2: rows 1448 x 8; 2009 1703
+ *            1138 400 -400 ..; 1892 784 -784 -1892 -1892 ..; 1703 -400 -2009 -1138 1138 ..; 1448 -1448 -1448 1448 ..; 1138
+ *            -2009 400 1703 -1703 ..; 784 -1892 1892 -784 -784 ..; 400 -1138 1703 -2009 2009 ..   (sum of |row| <= 11584)
+ *   rows     p[y][u] = (sum_x K[u][x] (s[y][x] - 128) + 2^8) >> 9        |sum| <= 11584 * 128 < 2^21; 3 fractional bits
+ *   columns  q[v][u] = sum_y K[v][y] p[y][u]                             |p| <= 2896, |q| <= 11584 * 2896 < 2^25; 15 fractional bits
+ *   quantise c = sign(q) * ((|q| + (Q << 14)) / (Q << 15))               half away from zero; Q = qtables entry v * 8 + u
+ *            computed as ((|q| >> 14) + Q) / 2Q -- the same number, since the dropped 14 bits cannot carry a multiple of
+ *            2Q * 2^14 -- with the division as (n * ceil(2^24 / 2Q)) >> 24, exact for every n < 2^14 and Q 1 .. 255.
+ *   coding   T.81 F.1.2 with the Annex K tables K.3 - K.6: DC difference to the component's previous block in the interval,
+ *            size category, (run, size) symbols, ZRL for 16 zeros, EOB unless coefficient 63 is non-zero; bits fill bytes from
+ *            the most significant bit.
+ * A frame's bytes are a function of its pixels and qtables alone: not of N, of the frame's place in the batch or of the order
+ * threads run in.
+ *   spnet_jpeg_scan  qtables uint16 [2][64]: luminance then chrominance, natural order (row v, column u), entries clamped to
+ *                    1 .. 255 (channels 1 reads the first table only, but both must be there).  sizes uint32 [N][intervals]:
+ *                    the exact bytes of every interval's entropy-coded data, stuffing and final padding included, markers
+ *                    excluded.
+ *   spnet_jpeg_pack  the same inputs, sizes as spnet_jpeg_scan wrote them (still in device memory) and offsets [N + 1]
+ *                    (64-bit).  Writes frame n's whole scan -- interval 0, RST0, interval 1, ... -- at out + offsets[n]; the
+ *                    host sizes the slot exactly (sum of the frame's sizes + 2 * (intervals - 1)).  Frame n may write bytes
+ *                    offsets[n] .. offsets[n+1] - 1 only and anything that does not fit is dropped, as is a frame whose slot
+ *                    is not inside [0, out_bytes).  Every byte has one writer (plain byte stores, no merging): out need not
+ *                    be zeroed or aligned, and bytes outside the slots are not changed.  The coefficients are RECOMPUTED;
+ *                    there is no workspace. */
+long spnet_jpeg_restart_interval(int W, int channels);
+long spnet_jpeg_intervals(int H, int W, int channels);
+int spnet_jpeg_scan(const unsigned char* src, int N, int H, int W, int channels, const uint16_t* qtables, uint32_t* sizes,
+                    void* stream);
+int spnet_jpeg_pack(const unsigned char* src, int N, int H, int W, int channels, const uint16_t* qtables, const uint32_t* sizes,
+                    const long long* offsets, unsigned char* out, long out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,8 @@ default_image_dir = '/home/shawley/datasets/zooniverse_steelpan/'
 
 def predict_network(weights_file="spnet.model", datapath=default_image_dir, fraction=1.0, log_dir='logs/Predicting/',
                     batch_size=16, model=None, X_pred='', u8_frames=False, device_resize=False, device_png=False,
-                    device_decode=False, device_overlay=False, device_png_lz=False):
+                    device_decode=False, device_overlay=False, device_png_lz=False, device_jpeg=False, jpeg_quality=90,
+                    movie=None, movie_fps=5.0):
     img_file_list = []
     resize = False
     if isinstance(X_pred, str) and X_pred == '':
@@ -72,7 +73,8 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
     Yp = denorm_Y(Y_pred)
     if img_file_list:
         show_pred_ellipses(Yp, Yp, img_file_list, num_draw=m, log_dir=log_dir, out_csv=log_dir + 'hawley_spnet.csv',
-                           show_true=False, png="device-lz" if device_png_lz else "device" if device_png else "host",
+                           show_true=False, png="device-jpeg" if device_jpeg else "device-lz" if device_png_lz else
+                           "device" if device_png else "host", jpeg_quality=jpeg_quality, movie=movie, movie_fps=movie_fps,
                            draw="device" if device_overlay else "host", device_decode=bool(device_decode and device_overlay))
     return model
 
@@ -106,11 +108,23 @@ if __name__ == '__main__':
                    help="(additive) draw the overlays (outlines, ring counts, file name) on the GPU: the same CSV and file "
                         "names, the same pixels away from outline edges; with --device_decode the frames are decoded there "
                         "too, with --device_png encoded there")
+    p.add_argument('--device_jpeg', action='store_true',
+                   help="(additive) write the overlays as steelpan_pred_NNNNN.jpg, baseline JPEG encoded on the GPU (lossy; "
+                        "not with --device_png / --device_png_lz)")
+    p.add_argument('--jpeg_quality', type=int, default=90, help="quality 1 .. 100 of --device_jpeg and --movie")
+    p.add_argument('--movie', default=None, metavar='PATH',
+                   help="(additive) also append every overlay, in order, to a Motion-JPEG AVI at PATH (encoded on the GPU)")
+    p.add_argument('--movie_fps', type=float, default=5.0, help="frames per second of --movie")
     args = p.parse_args()
+    if args.device_jpeg and (args.device_png or args.device_png_lz):
+        p.error("--device_jpeg writes .jpg files: not with --device_png / --device_png_lz")
+    if not 1 <= args.jpeg_quality <= 100:
+        p.error("--jpeg_quality is 1 .. 100")
     for attr, val in (("model_type", args.model_type), ("loss_type", args.loss_type)):
         if val is not None:
             setattr(cf, attr, val)
     predict_network(weights_file=args.weights, datapath=args.datapath, fraction=args.fraction, log_dir=args.logdir,
                     batch_size=args.batch_size, u8_frames=args.u8_frames, device_resize=args.device_resize,
                     device_png=args.device_png, device_decode=args.device_decode, device_overlay=args.device_overlay,
-                    device_png_lz=args.device_png_lz)
+                    device_png_lz=args.device_png_lz, device_jpeg=args.device_jpeg, jpeg_quality=args.jpeg_quality,
+                    movie=args.movie, movie_fps=args.movie_fps)

@@ -272,40 +272,83 @@ def draw_ellipse(img, center, axes, angle, startAngle=0, endAngle=360, color=(0,
 
 
 def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_extra=None, out_csv=None,
-                       show_true=True, verbosity=0, png="host", png_chunk=64, draw="host", device_decode=False):
+                       show_true=True, verbosity=0, png="host", png_chunk=64, draw="host", device_decode=False,
+                       jpeg_quality=90, movie=None, movie_fps=5.0):
     """Overlay PNGs steelpan_pred_%05d.png and the zooniverse-style CSV (cx,cy,file,rings,a,b,angle)
     from de-normalised true / predicted grids (utils.py:67-137).  png = "host": every overlay is saved by Pillow as it is
     drawn; "device" (additive): the drawn RGB overlays are collected png_chunk at a time, uploaded, encoded on the GPU
     (spnet_amd.png) and written by a thread pool -- the same pixels, file names and CSV rows, other file bytes; "device-lz":
-    the same with the encoder's LZ77 stage on (smaller files).
+    the same with the encoder's LZ77 stage on (smaller files); "device-jpeg" (additive): steelpan_pred_%05d.jpg instead,
+    baseline JPEG of quality jpeg_quality encoded on the GPU (spnet_amd.jpeg) -- lossy, the same file numbers and CSV rows.
+    movie (additive): an spnet_amd.jpeg.MjpegWriter, or a path (a Motion-JPEG AVI of movie_fps frames per second and
+    quality jpeg_quality is written there and closed at the end): every drawn frame is also appended to it, in j order,
+    whatever png is.
     draw = "host": Pillow draws; "device" (additive): the loop only plans (spnet_amd.overlay.plan_overlays), the frames
     are loaded png_chunk at a time -- by the device decoder with device_decode, else by Pillow and one upload per chunk --
     and one HIP launch per chunk draws them: the same file names and CSV rows, the same pixels away from outline edges
     (spnet_amd/overlay.py has the rule)."""
-    if png not in ("host", "device", "device-lz"):
-        raise ValueError('show_pred_ellipses: png is "host", "device" or "device-lz", got %r' % (png,))
+    if png not in ("host", "device", "device-lz", "device-jpeg"):
+        raise ValueError('show_pred_ellipses: png is "host", "device", "device-lz" or "device-jpeg", got %r' % (png,))
     if draw not in ("host", "device"):
         raise ValueError('show_pred_ellipses: draw is "host" or "device", got %r' % (draw,))
-    if draw == "device":
-        return _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk,
-                                          device_decode)
-    if device_decode:
+    if draw == "host" and device_decode:
         raise ValueError('show_pred_ellipses: device_decode loads the frames for draw="device"')
+    sink = _OverlaySink(png, jpeg_quality, movie, movie_fps)
+    try:
+        if draw == "device":
+            return _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk,
+                                              device_decode, sink)
+        return _show_pred_ellipses_host(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk, sink)
+    finally:
+        sink.close()
+
+
+class _OverlaySink:
+    """Where drawn overlays that are in device memory go: the files of png = "device" / "device-lz" / "device-jpeg" and the
+    movie.  A movie given as a path is opened at the first frames (their size is the movie's) and closed by close()."""
+
+    def __init__(self, png, jpeg_quality, movie, movie_fps):
+        self.png, self.quality, self.fps = png, jpeg_quality, movie_fps
+        self.extension = ".jpg" if png == "device-jpeg" else ".png"
+        self.movie = None if isinstance(movie, (str, os.PathLike)) else movie
+        self.movie_path = movie if self.movie is None else None
+        self.wants_device_frames = png != "host" or movie is not None
+
+    def write(self, frames, paths):
+        """frames: uint8 device tensor [n,H,W,3]; paths: the files of png != "host"."""
+        if self.png == "device-jpeg":
+            from .jpeg import write_jpeg_device
+            write_jpeg_device(frames, paths, quality=self.quality)
+        elif self.png != "host":
+            from .png import write_png_device
+            write_png_device(frames, paths, lz77=self.png == "device-lz")
+        if self.movie is None and self.movie_path is not None:
+            from .jpeg import MjpegWriter
+            self.movie = MjpegWriter(self.movie_path, int(frames.shape[2]), int(frames.shape[1]), fps=self.fps,
+                                     channels=3, quality=self.quality)
+        if self.movie is not None:
+            self.movie.add(frames)
+
+    def close(self):
+        if self.movie_path is not None and self.movie is not None:
+            self.movie.close()
+
+
+def _show_pred_ellipses_host(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk, sink):
+    """show_pred_ellipses(draw="host"): Pillow draws."""
     m = Yt.shape[0]
     num_draw = min(num_draw, m, len(file_list))
     if out_csv is not None:
         open(out_csv, "w").close()
     n_pred = int(Yt[0].size / cf.vars_per_pred)
-    held = []                                   # png == "device": (overlay as uint8 [H,W,3], its file), frames of one size
+    held = []                # png != "host" or a movie: (overlay as uint8 [H,W,3], its file), frames of one size
 
     def flush():
         if held:
             import torch
-            from .png import write_png_device
             if not torch.cuda.is_available():
-                raise RuntimeError('show_pred_ellipses: png="device" encodes on the GPU (no CPU fallback)')
-            write_png_device(torch.from_numpy(np.stack([h[0] for h in held])).cuda(), [h[1] for h in held],
-                             lz77=png == "device-lz")
+                raise RuntimeError('show_pred_ellipses: png="device..." and movie= encode on the GPU (no CPU fallback)')
+            sink.write(torch.from_numpy(np.stack([h[0] for h in held])).cuda(), [h[1] for h in held])
             held.clear()
 
     for j in range(num_draw):
@@ -330,18 +373,19 @@ def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_ex
         d.text((5, orig_img_dims[1] - 14), os.path.basename(in_filename), fill=(255, 255, 255))
         if png == "host":
             img.save(log_dir + '/steelpan_pred_' + str(j).zfill(5) + '.png')
-        else:
+        if sink.wants_device_frames:
             frame = np.asarray(img, dtype=np.uint8)
             if held and (held[0][0].shape != frame.shape or len(held) >= png_chunk):
                 flush()
-            held.append((frame, log_dir + '/steelpan_pred_' + str(j).zfill(5) + '.png'))
+            held.append((frame, log_dir + '/steelpan_pred_' + str(j).zfill(5) + sink.extension))
         if out_csv is not None:
             with open(out_csv, "a") as f:
                 f.write(csv_str)
     flush()
 
 
-def _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk, device_decode):
+def _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk, device_decode,
+                               sink):
     """show_pred_ellipses(draw="device"): runs of frames of one size, at most png_chunk long, are loaded, planned, drawn
     by csrc/overlay.hip and written; the CSV rows of a chunk are appended once its files are written."""
     import torch
@@ -359,11 +403,9 @@ def _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, sh
         plan = overlay.plan_overlays(Yt[lo:lo + n], Yp[lo:lo + n], file_list[lo:lo + n], show_true=show_true,
                                      size=tuple(int(v) for v in frames.shape[1:3]), with_csv=out_csv is not None)
         drawn = overlay.draw_overlays_device(frames, plan)
-        paths = [log_dir + '/steelpan_pred_' + str(lo + k).zfill(5) + '.png' for k in range(n)]
-        if png != "host":
-            from .png import write_png_device
-            write_png_device(drawn, paths, lz77=png == "device-lz")
-        else:
+        paths = [log_dir + '/steelpan_pred_' + str(lo + k).zfill(5) + sink.extension for k in range(n)]
+        sink.write(drawn, paths)
+        if png == "host":
             host = drawn.cpu().numpy()
             for k in range(n):
                 Image.fromarray(host[k]).save(paths[k])

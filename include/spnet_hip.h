@@ -786,6 +786,79 @@ int spnet_jpeg_scan(const unsigned char* src, int N, int H, int W, int channels,
 int spnet_jpeg_pack(const unsigned char* src, int N, int H, int W, int channels, const uint16_t* qtables, const uint32_t* sizes,
                     const long long* offsets, unsigned char* out, long out_bytes, void* stream);
 
+/* ---- JPEG input (csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h): the decoder behind Image.open(f).convert("RGB")
+ *      (spnet/utils.py:325-345) for baseline JPEG files and the frames of a Motion-JPEG movie whose entropy-coded bytes sit
+ *      in device memory --------------------------------------------------------------------------------------------------- */
+/* Baseline sequential DCT (SOF0), 8 bit, one scan; one component, or three (YCbCr) with luma sampled 1x1, 2x1 or 2x2 and
+ * chroma 1x1.  spnet_amd/jpeg.py is the host side (marker walk, classification, table building, host fallback).  N == 0:
+ * nothing to do, success.  hipErrorInvalidValue (nothing launched) for a NULL pointer, a misaligned array (int32 / uint32
+ * arrays 4 bytes, quant 2, coef 16) or a size outside the limits below.
+ *
+ * TABLES the host builds (all int32 unless said otherwise):
+ *   intervals [n_intervals][8]  first byte, end byte (positions in blob; the interval's entropy-coded data WITHOUT the RST
+ *                               marker behind it), file, first MCU, MCUs, 0, 0, 0.  A file without restart markers is one
+ *                               interval.  The 64 intervals of a workgroup (64 i .. 64 i + 63) must belong to files of ONE
+ *                               table set -- the host pads each set's run with empty intervals (MCUs 0) -- or they get
+ *                               status 6.
+ *   files [n_files][16]         components (1 | 3), hs, vs (luma sampling; 1 1 | 2 1 | 2 2), MCU columns, MCU rows, table
+ *                               set, first block of the file in the workspace, 0, (DC table | AC table << 4) of each
+ *                               component (table 0 | 1), quantisation table of each component (index into quant), 0, 0
+ *   tables uint32 [n_sets][904] a set is DC 0, AC 0, DC 1, AC 1; a table is look uint16 [256] (length << 8 | symbol of every
+ *                               code of up to 8 bits, indexed by the next 8 bits; 0: longer, or none), maxcode int32 [17]
+ *                               (largest code of each length 1 .. 16, -1: none), valoff int32 [17] (index of the length's
+ *                               first symbol minus its first code), vals uint8 [256].  A table the file lacks is all
+ *                               zeros / -1: using it is status 1.
+ *   quant uint16 [n_quant][64]  natural order (row v, column u)
+ *   coef int16 [total_blocks][64]  the workspace, natural order, ZEROED by the caller; a file's blocks are component after
+ *                               component, each in raster order of its block grid (MCU columns * h by MCU rows * v)
+ * blob_bytes < 2^31 - 1024, total_blocks < 2^25.
+ *
+ * ENTROPY DECODING (T.81 F.2.2), one lane per interval: bits are read most significant first; FF 00 is the data byte FF; an
+ * FF followed by anything else ends the data.  MCUs in raster order, inside an MCU the hs * vs luma blocks row by row, then
+ * Cb, then Cr.  Per block: a DC category s (<= 11), s bits EXTENDed (v if its top bit is set, else v - 2^s + 1) added to the
+ * component's predictor (0 at the interval's start); then (run, s) symbols: 0/0 ends the block, 15/0 skips 16 coefficients,
+ * else (s <= 10) k += run and coefficient k of the zigzag sequence is the next s bits EXTENDed.  status [n_files] (written
+ * for every file: 0 first, then the largest code of the file's intervals) holds jpegdec::Status:
+ *   1 a bit pattern that is no code   2 k past 63   3 a category above 11 (DC) / 10 (AC)   4 bits missing before the
+ *   interval's MCUs are done   5 a whole byte or more left over after them   6 a table entry outside the arrays above
+ * and that interval stops there.  No byte outside [first byte, end byte) is read for an interval, no coefficient outside the
+ * blocks of its own MCUs written, every loop is bounded by a count that does not depend on the data; the other files of the
+ * launch are not affected.
+ *
+ * PIXELS, integers only (>> is an arithmetic shift):
+ *   dequantise  c[v][u] * quant[v][u]
+ *   IDCT        libjpeg's jidctint.c ("islow"), CONST_BITS 13, PASS1_BITS 2, the same butterfly twice: with the constants
+ *               FIX(0.298631336) = 2446, 0.390180644: 3196, 0.541196100: 4433, 0.765366865: 6270, 0.899976223: 7373,
+ *               1.175875602: 9633, 1.501321110: 12299, 1.847759065: 15137, 1.961570560: 16069, 2.053119869: 16819,
+ *               2.562915447: 20995, 3.072711026: 25172,
+ *                 even: z1 = (x2 + x6) 4433; t2 = z1 - 15137 x6; t3 = z1 + 6270 x2; t0 = (x0 + x4) << 13; t1 = (x0 - x4) << 13;
+ *                       t10 = t0 + t3; t13 = t0 - t3; t11 = t1 + t2; t12 = t1 - t2
+ *                 odd:  z1 = x7 + x1; z2 = x5 + x3; z3 = x7 + x3; z4 = x5 + x1; z5 = 9633 (z3 + z4);
+ *                       z3 = z5 - 16069 z3; z4 = z5 - 3196 z4;
+ *                       o0 = 2446 x7 - 7373 z1 + z3; o1 = 16819 x5 - 20995 z2 + z4; o2 = 25172 x3 - 20995 z2 + z3;
+ *                       o3 = 12299 x1 - 7373 z1 + z4
+ *                 out:  t10 +- o3 -> 0, 7; t11 +- o2 -> 1, 6; t12 +- o1 -> 2, 5; t13 +- o0 -> 3, 4; each (s + 2^(n-1)) >> n
+ *               down every column with n = 11, then along every row with n = 18; sample = clamp(result + 128, 0, 255).
+ *               Sums are formed modulo 2^32.  (libjpeg masks into a table where this clamps: the same on every stream an
+ *               encoder writes.)
+ *   upsampling  libjpeg's "fancy" triangle filter over the chroma component's TRUE samples (ceil(W / hs) by ceil(H / vs)),
+ *               neighbours beyond an edge replaced by the edge sample.  2x1: pixel x takes i = x >> 1 and j = i - 1 (x
+ *               even) or i + 1 (x odd): (3 s[i] + s[j] + 1 + (x & 1)) >> 2.  2x2: rows r = y >> 1 and rn = r - 1 (y even) or
+ *               r + 1 (y odd) first, t[i] = 3 s[r][i] + s[rn][i]; then (3 t[i] + t[j] + 8 - (x & 1)) >> 4.
+ *   colour      Cb' = Cb - 128, Cr' = Cr - 128; R = Y + ((91881 Cr' + 32768) >> 16), G = Y + ((-22554 Cb' - 46802 Cr' +
+ *               32768) >> 16), B = Y + ((116130 Cb' + 32768) >> 16), each clamped to 0 .. 255.  One component: the sample.
+ *   spnet_jpeg_pixels  H, W (1 .. 65,535): the size of EVERY file of the launch (a file whose MCU grid does not fit it gets
+ *               status 6); files whose status is non-zero are skipped.  first (may be NULL): uint8 [N][H][W], channel 0 of
+ *               what convert("RGB") gives (Y of a grey file, R of a colour file); all (may be NULL): uint8 [N][H][W]
+ *               [channels], channels = the files' component count (another count: status 6); at least one.  No byte outside
+ *               them is written, none of a skipped file's frame. */
+int spnet_jpeg_entropy(const unsigned char* blob, long blob_bytes, const int* intervals, int n_intervals, const int* files,
+                       int n_files, const uint32_t* tables, int n_sets, int16_t* coef, long total_blocks, int* status,
+                       void* stream);
+int spnet_jpeg_pixels(const int16_t* coef, long total_blocks, const int* files, int n_files, const uint16_t* quant,
+                      int n_quant, int H, int W, int channels, unsigned char* first, unsigned char* all, int* status,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,10 +18,32 @@ default_image_dir = '/home/shawley/datasets/zooniverse_steelpan/'
 def predict_network(weights_file="spnet.model", datapath=default_image_dir, fraction=1.0, log_dir='logs/Predicting/',
                     batch_size=16, model=None, X_pred='', u8_frames=False, device_resize=False, device_png=False,
                     device_decode=False, device_overlay=False, device_png_lz=False, device_jpeg=False, jpeg_quality=90,
-                    movie=None, movie_fps=5.0):
+                    movie=None, movie_fps=5.0, movie_in=None):
     img_file_list = []
     resize = False
-    if isinstance(X_pred, str) and X_pred == '':
+    frames = None
+    if movie_in is not None:
+        # (additive) the frames of a Motion-JPEG AVI, decoded on the GPU; they stay there up to the encoders
+        import os
+        from spnet_amd.jpeg import MjpegReader
+        if cf.model_type == 'simple':
+            raise ValueError("movie_in is for grayscale input (model_type 'big' / 'monolithic')")
+        force_dim = None if cf.model_type == 'big' else 331
+        reader = MjpegReader(movie_in)
+        total_load = int(len(reader) * fraction)
+        if batch_size is not None:
+            total_load = nearest_multiple(total_load, batch_size)
+        print(f"Getting data from {movie_in}: {len(reader)} frames of {reader.size[0]}x{reader.size[1]} at {reader.fps} "
+              f"frames per second, going to load total_load = {total_load}")
+        frames = reader.read_device(range(total_load), channels="all")
+        frames = frames[..., 0] if int(frames.shape[3]) == 1 else frames        # [N,H,W] grey | [N,H,W,3]
+        stem = os.path.splitext(os.path.basename(movie_in))[0]
+        img_file_list = ["%s_%05d" % (stem, k) for k in range(total_load)]
+        resize = force_dim is not None
+        X_pred, _ = build_X(total_load, img_file_list, force_dim=force_dim, grayscale=True, as_uint8=True,
+                            frames=frames if frames.dim() == 3 else frames[..., 0])
+        device_decode = device_overlay = True
+    elif isinstance(X_pred, str) and X_pred == '':
         print(f"Getting data from {datapath}, fraction = {fraction}.")
         if cf.model_type == 'simple':
             grayscale, force_dim = False, 224
@@ -30,6 +52,8 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
         else:
             grayscale, force_dim = True, 331
         img_file_list = sorted(glob.glob(datapath + '/*.png')) or sorted(glob.glob(datapath + '/*.bmp'))
+        if not img_file_list:       # (additive) a directory without PNG and BMP files: its JPEG files
+            img_file_list = sorted(glob.glob(datapath + '/*.jpg') + glob.glob(datapath + '/*.jpeg'))
         total_files = len(img_file_list)
         total_load = int(total_files * fraction)
         if batch_size is not None:
@@ -37,7 +61,8 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
         print("      Total files = ", total_files, ", going to load total_load = ", total_load)
         # device_resize: the files' own grey levels travel, the GPU resizes them to force_dim (implies u8 frames; the
         # 'big' layout has nothing to resize)
-        # device_decode: the files' bytes travel, the GPU inflates and unfilters them (implies device_resize)
+        # device_decode: the files' bytes travel, the GPU decodes them -- PNG: inflate and unfilter, JPEG: Huffman, IDCT,
+        # colour -- (implies device_resize)
         if device_decode and not grayscale:
             raise ValueError("device_decode is for grayscale input (model_type 'big' / 'monolithic')")
         resize = (bool(device_resize) or bool(device_decode)) and grayscale and force_dim is not None
@@ -75,7 +100,8 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
         show_pred_ellipses(Yp, Yp, img_file_list, num_draw=m, log_dir=log_dir, out_csv=log_dir + 'hawley_spnet.csv',
                            show_true=False, png="device-jpeg" if device_jpeg else "device-lz" if device_png_lz else
                            "device" if device_png else "host", jpeg_quality=jpeg_quality, movie=movie, movie_fps=movie_fps,
-                           draw="device" if device_overlay else "host", device_decode=bool(device_decode and device_overlay))
+                           draw="device" if device_overlay else "host", device_decode=bool(device_decode and device_overlay),
+                           frames=frames)
     return model
 
 
@@ -97,8 +123,11 @@ if __name__ == '__main__':
                    help="(additive, implies --u8_frames) load the frames at their own size and resize them to the "
                         "network's on the GPU, bit-identical to the PIL resize of the default path")
     p.add_argument('--device_decode', action='store_true',
-                   help="(additive, implies --device_resize) upload the PNG files as they are and decode them on the GPU "
-                        "(inflate + unfilter; formats the device does not take are decoded by Pillow): same predictions")
+                   help="(additive, implies --device_resize) upload the PNG / JPEG files as they are and decode them on the GPU "
+                        "(formats the device does not take are decoded by Pillow): same predictions")
+    p.add_argument('--movie_in', default=None, metavar='PATH.avi',
+                   help="(additive, instead of -d; implies --device_decode and --device_overlay) predict on the frames of a "
+                        "Motion-JPEG AVI, decoded on the GPU; they are named <stem>_NNNNN in the CSV and on the overlays")
     p.add_argument('--device_png', action='store_true',
                    help="(additive) encode the overlay PNG files on the GPU (Huffman-only deflate): the same pixels, "
                         "other file bytes")
@@ -127,4 +156,4 @@ if __name__ == '__main__':
                     batch_size=args.batch_size, u8_frames=args.u8_frames, device_resize=args.device_resize,
                     device_png=args.device_png, device_decode=args.device_decode, device_overlay=args.device_overlay,
                     device_png_lz=args.device_png_lz, device_jpeg=args.device_jpeg, jpeg_quality=args.jpeg_quality,
-                    movie=args.movie, movie_fps=args.movie_fps)
+                    movie=args.movie, movie_fps=args.movie_fps, movie_in=args.movie_in)

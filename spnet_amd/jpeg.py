@@ -18,6 +18,13 @@ the coefficients: no HBM workspace) -> D2H of the scans.  The host wraps each sc
 DRI, SOS; the same for every frame of a batch) and the trailer (EOI).
 
 MjpegWriter streams such files into a plain RIFF AVI (hdrl / movi of 00dc chunks / idx1; 32-bit sizes, below 2 GiB).
+
+Reading (csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h; additive and opt-in: --device_decode, --movie_in): parse_jpeg walks
+the markers and finds the restart intervals, plan_decode builds what the kernels read, decode_jpeg_device /
+read_jpeg_device have the contract of their PNG namesakes (one size per call, host fallback through png._host_frame, one
+pinned upload, one status download), read_frames_device routes a list of PNG and JPEG files by signature, MjpegReader
+walks a RIFF AVI.  Baseline JPEG, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0; the pixels are Pillow's, sample for sample (DESIGN.md
+section 5f).
 """
 import struct
 from concurrent.futures import ThreadPoolExecutor
@@ -365,3 +372,542 @@ class MjpegWriter:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+# ----------------------------------------------------------------------------- reading: container
+# What the device decoder (csrc/jpeg_decode.hip) takes: baseline sequential DCT (SOF0), 8 bit, ONE scan over all components,
+# one component (grey) or three that Pillow reads as YCbCr (JFIF, or no Adobe segment saying otherwise), luma sampled 1x1,
+# 2x1 or 2x2 and chroma 1x1, quantisation tables of 8-bit entries, at most two Huffman tables per class.  Everything else
+# (progressive, extended, arithmetic, 12 bit, CMYK / Adobe transforms, several scans, fill bytes, restart markers out of
+# sequence) is left to Pillow.  A frame without a DHT segment (common in Motion-JPEG) uses the Annex K tables, as
+# libjpeg-turbo does.
+STATUS_NAMES = ("ok", "bit pattern that is no code", "coefficient index past 63", "magnitude category too large",
+                "bits missing before the interval's MCUs are done", "bytes left over after the interval's MCUs",
+                "table entry outside the launch's arrays")
+TABLE_WORDS = 4 * 226           # one Huffman table set in device form: DC 0, AC 0, DC 1, AC 1 (jpeg_decode_core.h)
+MAX_BLOB = (1 << 31) - 1024     # spnet_jpeg_entropy: 32-bit byte positions
+MAX_PIXELS = 1 << 28            # H * W of one frame
+_SOF_OTHER = frozenset(range(0xC1, 0xD0)) - {0xC4, 0xC8, 0xCC}
+_EMPTY_TABLE = ((0,) * 16, ())
+
+
+class JpegInfo:
+    """What parse_jpeg found.  width, height, components (1 | 3), hs, vs (luma sampling factors), quant {id: uint16 [64] in
+    natural order}, comp_quant / comp_dc / comp_ac (per component: table ids), huffman {(class, id): (BITS, HUFFVAL)},
+    restart (MCUs per interval, 0: none), bounds (int64 [n + 1][2]: the byte range of every restart interval's entropy-coded
+    data in `data`), data (the file), host_reason: None for a file the device decodes, else why the host has to (str)."""
+    __slots__ = ("width", "height", "components", "hs", "vs", "quant", "comp_quant", "comp_dc", "comp_ac", "huffman",
+                 "restart", "bounds", "data", "host_reason")
+
+    def __init__(self):
+        self.width = self.height = self.components = self.hs = self.vs = None
+        self.quant, self.huffman = {}, {}
+        self.comp_quant = self.comp_dc = self.comp_ac = ()
+        self.restart = 0
+        self.bounds = None
+        self.data = b""
+        self.host_reason = None
+
+    @property
+    def device(self):
+        return self.host_reason is None
+
+    @property
+    def mcu_grid(self):
+        """(MCU columns, MCU rows)."""
+        return (self.width + 8 * self.hs - 1) // (8 * self.hs), (self.height + 8 * self.vs - 1) // (8 * self.vs)
+
+    @property
+    def blocks(self):
+        """8 x 8 blocks of all components: the file's share of the coefficient workspace."""
+        mw, mh = self.mcu_grid
+        return mw * mh * (self.hs * self.vs + (2 if self.components == 3 else 0))
+
+
+def parse_jpeg(data):
+    """The marker walk: SOI, APPn / COM (skipped, but for what JFIF and Adobe say about colour), DQT, SOF0, DHT, DRI, SOS,
+    the restart markers (one vectorised scan), EOI.  Raises nothing: a file the device cannot take, a damaged container
+    included, comes back with host_reason set and is left to the host decoder, which decides what it is."""
+    info = JpegInfo()
+    info.data = data
+    buf = np.frombuffer(data, np.uint8)
+    n = int(buf.size)
+
+    def no(reason):
+        info.host_reason = reason
+        return info
+
+    if n < 4 or buf[0] != 0xFF or buf[1] != 0xD8:
+        return no("no JPEG signature")
+    pos = 2
+    jfif = False
+    adobe = None
+    frame = None                 # [(id, h, v, tq)]
+    have_dht = False
+    while True:
+        if pos + 4 > n:
+            return no("the file ends in its headers")
+        if buf[pos] != 0xFF:
+            return no("no marker where one is due")
+        m = int(buf[pos + 1])
+        if m == 0xFF:            # fill byte
+            pos += 1
+            continue
+        if m == 0xD8 or m == 0xD9 or 0xD0 <= m <= 0xD7 or m == 0x01:
+            return no("marker FF %02X in the headers" % m)
+        length = int(buf[pos + 2]) << 8 | int(buf[pos + 3])
+        if length < 2 or pos + 2 + length > n:
+            return no("segment FF %02X runs past the end of the file" % m)
+        body = buf[pos + 4:pos + 2 + length]
+        pos += 2 + length
+        if m == 0xE0:
+            jfif = jfif or (body.size >= 5 and bytes(body[:5]) == b"JFIF\x00")
+        elif m == 0xEE:
+            if body.size >= 12 and bytes(body[:5]) == b"Adobe":
+                adobe = int(body[11])
+        elif m == 0xDB:
+            k = 0
+            while k < body.size:
+                pq, tq = int(body[k]) >> 4, int(body[k]) & 15
+                if pq != 0:
+                    return no("quantisation table of 16-bit entries")
+                if tq > 3 or k + 65 > body.size:
+                    return no("damaged DQT")
+                table = np.zeros(64, np.uint16)
+                table[np.array(ZIGZAG)] = body[k + 1:k + 65]
+                info.quant[tq] = table
+                k += 65
+        elif m == 0xC0:
+            if frame is not None:
+                return no("a second frame header")
+            if body.size < 6:
+                return no("damaged SOF0")
+            precision, info.height, info.width, nc = (int(body[0]), int(body[1]) << 8 | int(body[2]),
+                                                       int(body[3]) << 8 | int(body[4]), int(body[5]))
+            if precision != 8:
+                return no("%d-bit samples" % precision)
+            if body.size != 6 + 3 * nc:
+                return no("damaged SOF0")
+            if nc not in (1, 3):
+                return no("%d components" % nc)
+            if info.width < 1 or info.height < 1:
+                return no("empty image (or a DNL-defined height)")
+            frame = [(int(body[6 + 3 * c]), int(body[7 + 3 * c]) >> 4, int(body[7 + 3 * c]) & 15, int(body[8 + 3 * c]))
+                     for c in range(nc)]
+            info.components = nc
+        elif m in _SOF_OTHER:
+            return no("not baseline (SOF%d)" % (m - 0xC0))
+        elif m == 0xC4:
+            have_dht = True
+            k = 0
+            while k < body.size:
+                if k + 17 > body.size:
+                    return no("damaged DHT")
+                tc, th = int(body[k]) >> 4, int(body[k]) & 15
+                bits = tuple(int(v) for v in body[k + 1:k + 17])
+                count = sum(bits)
+                if tc > 1 or th > 1 or count > 256 or k + 17 + count > body.size:
+                    return no("damaged DHT, or a table id above 1")
+                if _oversubscribed(bits):
+                    return no("over-subscribed Huffman code")
+                info.huffman[(tc, th)] = (bits, tuple(int(v) for v in body[k + 17:k + 17 + count]))
+                k += 17 + count
+        elif m == 0xDD:
+            if body.size != 2:
+                return no("damaged DRI")
+            info.restart = int(body[0]) << 8 | int(body[1])
+        elif m == 0xCC:
+            return no("arithmetic coding")
+        elif m == 0xDA:
+            break
+        # every other segment (APPn, COM, ...) is skipped
+    if frame is None:
+        return no("SOS before SOF0")
+    nc = info.components
+    if body.size != 4 + 2 * nc or int(body[0]) != nc:
+        return no("a scan that does not hold every component (several scans)")
+    if (int(body[1 + 2 * nc]), int(body[2 + 2 * nc]), int(body[3 + 2 * nc])) != (0, 63, 0):
+        return no("spectral selection / successive approximation")
+    dc, ac = [], []
+    for c in range(nc):
+        if int(body[1 + 2 * c]) != frame[c][0]:
+            return no("scan components out of frame order")
+        td, ta = int(body[2 + 2 * c]) >> 4, int(body[2 + 2 * c]) & 15
+        if td > 1 or ta > 1:
+            return no("Huffman table id above 1")
+        dc.append(td)
+        ac.append(ta)
+    info.comp_dc, info.comp_ac = tuple(dc), tuple(ac)
+    info.comp_quant = tuple(f[3] for f in frame)
+    if any(t not in info.quant for t in info.comp_quant):
+        return no("a quantisation table that was never defined")
+    if not have_dht:
+        info.huffman = {(cls, dest): tab for cls, dest, tab in HUFFMAN_TABLES}
+    if any((0, t) not in info.huffman for t in dc) or any((1, t) not in info.huffman for t in ac):
+        return no("a Huffman table that was never defined")
+    if nc == 1:
+        info.hs = info.vs = 1            # a single component is not interleaved: its sampling factors do not matter
+    else:
+        ids = tuple(f[0] for f in frame)
+        # as libjpeg decides: JFIF says YCbCr; else Adobe's transform flag; else the ids (R G B means RGB)
+        if jfif:
+            ycc = True
+        elif adobe is not None:
+            ycc = adobe == 1
+        else:
+            ycc = ids != (82, 71, 66)
+        if adobe is not None and adobe != 1:
+            ycc = False
+        if not ycc:
+            return no("three components that are not YCbCr")
+        info.hs, info.vs = frame[0][1], frame[0][2]
+        if (info.hs, info.vs) not in ((1, 1), (2, 1), (2, 2)) or any(f[1:3] != (1, 1) for f in frame[1:]):
+            return no("sampling factors %s" % ",".join("%dx%d" % f[1:3] for f in frame))
+    if info.width * info.height > MAX_PIXELS:
+        return no("larger than the device decoder's budget")
+    # ---- the scan: every FF that is not followed by 00 is a marker
+    scan = buf[pos:]
+    at = np.flatnonzero((scan[:-1] == 0xFF) & (scan[1:] != 0)) + pos if scan.size > 1 else np.zeros(0, np.int64)
+    kinds = buf[at + 1] if at.size else np.zeros(0, np.uint8)
+    other = np.flatnonzero((kinds < 0xD0) | (kinds > 0xD7))
+    if other.size == 0:
+        return no("no EOI")
+    last = int(other[0])
+    if int(kinds[last]) != 0xD9:
+        return no("marker FF %02X in the scan (fill bytes, several scans, DNL)" % int(kinds[last]))
+    rst_at, rst_kind = at[:last], kinds[:last]
+    mw, mh = info.mcu_grid
+    mcus = mw * mh
+    want = (mcus + info.restart - 1) // info.restart - 1 if info.restart else 0
+    if rst_at.size != want or not np.array_equal(rst_kind, 0xD0 + (np.arange(want) & 7)):
+        return no("restart markers out of sequence")
+    if want and np.any(np.diff(rst_at) < 2):
+        return no("restart markers out of sequence")
+    bounds = np.empty((want + 1, 2), np.int64)
+    bounds[:, 0] = np.concatenate(([pos], rst_at + 2))
+    bounds[:, 1] = np.concatenate((rst_at, [int(at[last])]))
+    info.bounds = bounds
+    return info
+
+
+def _oversubscribed(bits):
+    """More codes of some length than that length has left (T.81 Annex C builds codes by counting up)."""
+    code = 0
+    for length in range(16):
+        code += bits[length]
+        if code > 1 << (length + 1):
+            return True
+        code <<= 1
+    return False
+
+
+def device_table(table):
+    """One Huffman table (BITS, HUFFVAL) in the device's form, 226 uint32 words (jpeg_decode_core.h): look[256] as uint16
+    (length << 8 | symbol for every code of up to 8 bits, indexed by the next 8 bits; 0: longer, or no code), maxcode[17]
+    (int32, the largest code of each length 1 .. 16, -1: none; [0] unused), valoff[17] (int32: index of the length's first
+    symbol minus its first code), vals[256] (uint8)."""
+    bits, vals = table
+    look = np.zeros(256, np.uint16)
+    maxcode = np.full(17, -1, np.int32)
+    valoff = np.zeros(17, np.int32)
+    symbols = np.zeros(256, np.uint8)
+    symbols[:len(vals)] = vals
+    code, k = 0, 0
+    for length in range(1, 17):
+        count = bits[length - 1]
+        if count:
+            valoff[length] = k - code
+            if length <= 8:
+                for j in range(count):
+                    lo = (code + j) << (8 - length)
+                    look[lo:lo + (1 << (8 - length))] = length << 8 | int(symbols[k + j])
+            code += count
+            k += count
+            maxcode[length] = code - 1
+        code <<= 1
+    return np.concatenate([look.view(np.uint32), maxcode.view(np.uint32), valoff.view(np.uint32), symbols.view(np.uint32)])
+
+
+def plan_decode(infos):
+    """The arrays one launch pair reads, for files that are all info.device (host numpy arrays):
+      blob       uint8: the files' entropy-coded bytes, interval after interval (markers left out)
+      intervals  int32 [n][8]: first byte, end byte (positions in blob), file, first MCU, MCUs, 0, 0, 0 -- grouped by table
+                 set, every group padded with empty intervals to a multiple of 64 (a workgroup holds ONE set in LDS)
+      files      int32 [N][16]: components, hs, vs, MCU columns, MCU rows, table set, first block (in the workspace), 0,
+                 (DC table | AC table << 4) x 3, quantisation table x 3, 0, 0
+      tables     uint32 [sets][TABLE_WORDS], deduplicated
+      quant      uint16 [q][64], natural order, deduplicated
+      blocks     8 x 8 blocks of the workspace"""
+    sets, quants = {}, {}
+    files = np.zeros((len(infos), 16), np.int32)
+    per_set = {}
+    pieces = []
+    at = 0
+    block = 0
+    for f, info in enumerate(infos):
+        key = tuple(info.huffman.get(k, _EMPTY_TABLE) for k in ((0, 0), (1, 0), (0, 1), (1, 1)))
+        s = sets.setdefault(key, len(sets))
+        mw, mh = info.mcu_grid
+        files[f, :7] = (info.components, info.hs, info.vs, mw, mh, s, block)
+        block += info.blocks
+        for c in range(info.components):
+            q = quants.setdefault(info.quant[info.comp_quant[c]].tobytes(), len(quants))
+            files[f, 8 + c] = info.comp_dc[c] | info.comp_ac[c] << 4
+            files[f, 11 + c] = q
+        ri = info.restart or mw * mh
+        raw = np.frombuffer(info.data, np.uint8)
+        rows = per_set.setdefault(s, [])
+        for i, (lo, hi) in enumerate(info.bounds):
+            lo, hi = int(lo), int(hi)
+            pieces.append(raw[lo:hi])
+            rows.append((at, at + hi - lo, f, i * ri, min(ri, mw * mh - i * ri), 0, 0, 0))
+            at += hi - lo
+    intervals = []
+    for s in sorted(per_set):
+        rows = per_set[s]
+        f0 = rows[0][2]
+        rows += [(0, 0, f0, 0, 0, 0, 0, 0)] * (-len(rows) % 64)
+        intervals += rows
+    tables = np.stack([np.concatenate([device_table(t) for t in key]) for key in sets]) if sets else \
+        np.zeros((0, TABLE_WORDS), np.uint32)
+    quant = np.stack([np.frombuffer(q, np.uint16) for q in quants]) if quants else np.zeros((0, 64), np.uint16)
+    blob = np.concatenate(pieces) if pieces else np.zeros(0, np.uint8)
+    return dict(blob=blob, intervals=np.array(intervals, np.int32).reshape(-1, 8), files=files, tables=tables,
+                quant=quant, blocks=block)
+
+
+# ----------------------------------------------------------------------------- reading: device
+def _decode_parsed(infos, sources, device, channels, return_info):
+    import os
+    import torch
+    from . import _lib as L
+    from .png import _host_frame
+    if channels not in ("first", "all"):
+        raise ValueError('jpeg: channels is "first" or "all", got %r' % (channels,))
+    if not torch.cuda.is_available():
+        raise RuntimeError("jpeg: decode_jpeg_device decodes on the GPU (there is no CPU decoder here)")
+    device = torch.device("cuda" if device is None else device)
+    N = len(infos)
+    status = np.zeros(N, np.int32)
+    host = [k for k in range(N) if not infos[k].device]
+    host_frames = {k: _host_frame(sources[k], channels) for k in host}          # raises what the default path raises
+
+    def shape_of(k):
+        if k in host_frames:
+            return host_frames[k].shape
+        return (infos[k].height, infos[k].width) + ((infos[k].components,) if channels == "all" else ())
+
+    if N == 0:
+        out = torch.empty((0, 0, 0) if channels == "first" else (0, 0, 0, 0), dtype=torch.uint8, device=device)
+        return (out, status, []) if return_info else out
+    shape = shape_of(0)
+    for k in range(1, N):
+        if shape_of(k) != shape:
+            name = sources[k] if isinstance(sources[k], (str, os.PathLike)) else "file %d" % k
+            raise ValueError("jpeg: %s is %s, the files before it are %s (one call decodes files of one size)"
+                             % (name, "x".join(str(v) for v in shape_of(k)), "x".join(str(v) for v in shape)))
+    out = torch.empty((N,) + tuple(shape), dtype=torch.uint8, device=device)
+    H, W = int(shape[0]), int(shape[1])
+    idx = [k for k in range(N) if infos[k].device]
+    plan = plan_decode([infos[k] for k in idx]) if idx else None
+    if plan is not None and (plan["blob"].size > MAX_BLOB or plan["blocks"] * 64 > (1 << 31) - 1):
+        raise ValueError("jpeg: %d files of %d x %d are more than one call decodes; pass fewer" % (len(idx), W, H))
+    if plan is not None:
+        n = len(idx)
+        C = int(shape[2]) if channels == "all" else 1
+        # one pinned upload: the tables first (every piece padded to 16 bytes), the bytes last
+        parts = [plan["intervals"].view(np.uint8).ravel(), plan["files"].view(np.uint8).ravel(),
+                 plan["tables"].view(np.uint8).ravel(), plan["quant"].view(np.uint8).ravel(), plan["blob"]]
+        starts, total = [], 0
+        for p in parts:
+            starts.append(total)
+            total += (p.size + 15) // 16 * 16
+        staging = torch.empty((max(total, 16),), dtype=torch.uint8).pin_memory()
+        buf = staging.numpy()
+        for s, p in zip(starts, parts):
+            buf[s:s + p.size] = p
+        dev = staging.to(device, non_blocking=True)
+        base = dev.data_ptr()
+        whole = n == N
+        got = out if whole else torch.empty((n,) + tuple(shape), dtype=torch.uint8, device=device)
+        coef = torch.zeros((max(plan["blocks"], 1), 64), dtype=torch.int16, device=device)
+        st = torch.empty((n,), dtype=torch.int32, device=device)
+        with torch.cuda.device(device):
+            L.spnet_jpeg_entropy(base + starts[4], int(plan["blob"].size), base + starts[0], int(plan["intervals"].shape[0]),
+                                 base + starts[1], n, base + starts[2], int(plan["tables"].shape[0]), coef.data_ptr(),
+                                 int(plan["blocks"]), st.data_ptr(), L.current_stream())
+            L.spnet_jpeg_pixels(coef.data_ptr(), int(plan["blocks"]), base + starts[1], n, base + starts[3],
+                                int(plan["quant"].shape[0]), H, W, C, got.data_ptr() if channels == "first" else 0,
+                                got.data_ptr() if channels == "all" else 0, st.data_ptr(), L.current_stream())
+        status[idx] = st.cpu().numpy()           # the D2H copy of the status: the only synchronisation
+        del staging
+        if not whole:
+            out[torch.as_tensor(idx, device=device)] = got
+    failed = [k for k in range(N) if status[k] != 0]
+    for k in failed:
+        host_frames[k] = _host_frame(sources[k], channels)      # a corrupt file raises here what it raises today
+        if host_frames[k].shape != tuple(shape):
+            raise ValueError("jpeg: file %d decodes to %s on the host, %s was expected" % (k, host_frames[k].shape, shape))
+    fallback = sorted(host_frames)
+    if fallback:
+        up = torch.from_numpy(np.stack([host_frames[k] for k in fallback])).to(device)
+        out[torch.as_tensor(fallback, device=device)] = up
+    return (out, status, fallback) if return_info else out
+
+
+def decode_jpeg_device(datas, device=None, channels="first", return_info=False, threads=MAX_THREADS):
+    """JPEG files (a list of bytes) -> a uint8 DEVICE tensor [N,H,W] holding channel 0 of every pixel (what
+    utils._load_one(..., as_uint8=True) keeps: the grey level, or R), or [N,H,W,C] with channels="all".  The entropy-coded
+    bytes are uploaded as they are and decoded on the GPU (Huffman, dequantisation, IDCT, upsampling, colour).  Files the
+    device does not take (see parse_jpeg) and files it rejects (status != 0) are decoded by the default path's Pillow call
+    and uploaded into their place, so the pixels are the default path's in every case and a corrupt file raises what it
+    raises there.  All files of a call have one size (ValueError otherwise).  return_info: also the status array
+    (jpeg_decode_core.h's codes, STATUS_NAMES) and the sorted indices of the files the host decoded."""
+    datas = list(datas)
+    if not datas:
+        return _decode_parsed([], [], device, channels, return_info)
+    with ThreadPoolExecutor(max_workers=_pool_size(threads, len(datas))) as pool:
+        infos = list(pool.map(parse_jpeg, datas))
+    return _decode_parsed(infos, datas, device, channels, return_info)
+
+
+def _read_file(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def read_jpeg_device(paths, threads=MAX_THREADS, device=None, channels="first", return_info=False):
+    """decode_jpeg_device of files on disk, read and parsed by a thread pool of this process (at most 16 threads; nothing
+    is forked)."""
+    paths = list(paths)
+    if not paths:
+        return _decode_parsed([], [], device, channels, return_info)
+    with ThreadPoolExecutor(max_workers=_pool_size(threads, len(paths))) as pool:
+        infos = list(pool.map(lambda p: parse_jpeg(_read_file(p)), paths))
+    return _decode_parsed(infos, paths, device, channels, return_info)
+
+
+def _is_jpeg(path):
+    with open(path, "rb") as f:
+        return f.read(2) == b"\xff\xd8"
+
+
+def read_frames_device(paths, threads=MAX_THREADS, device=None, channels="first", return_info=False):
+    """Frames of PNG and JPEG files, routed by signature: files that begin FF D8 go to read_jpeg_device, every other file
+    to png.read_png_device, unchanged; the results land in one tensor in input order.  A list without JPEG files is ONE
+    call of read_png_device with the same arguments.  With return_info the status of a JPEG file is offset by 100 (PNG and
+    JPEG codes share one array)."""
+    from . import png
+    paths = list(paths)
+    jpg = [k for k, p in enumerate(paths) if _is_jpeg(p)]
+    if not jpg:
+        return png.read_png_device(paths, threads=threads, device=device, channels=channels, return_info=return_info)
+    if len(jpg) == len(paths):
+        got = read_jpeg_device(paths, threads=threads, device=device, channels=channels, return_info=return_info)
+        if return_info:
+            return got[0], np.where(got[1] != 0, got[1] + 100, 0).astype(np.int32), got[2]
+        return got
+    import torch
+    other = [k for k in range(len(paths)) if k not in set(jpg)]
+    a, sa, fa = read_jpeg_device([paths[k] for k in jpg], threads=threads, device=device, channels=channels,
+                                 return_info=True)
+    b, sb, fb = png.read_png_device([paths[k] for k in other], threads=threads, device=device, channels=channels,
+                                    return_info=True)
+    if a.shape[1:] != b.shape[1:]:
+        raise ValueError("jpeg: the JPEG files are %s, the other files %s (one call decodes files of one size)"
+                         % ("x".join(str(int(v)) for v in a.shape[1:]), "x".join(str(int(v)) for v in b.shape[1:])))
+    out = torch.empty((len(paths),) + tuple(a.shape[1:]), dtype=torch.uint8, device=a.device)
+    out[torch.as_tensor(jpg, device=a.device)] = a
+    out[torch.as_tensor(other, device=a.device)] = b
+    if not return_info:
+        return out
+    status = np.zeros(len(paths), np.int32)
+    status[jpg] = np.where(sa != 0, sa + 100, 0)
+    status[other] = sb
+    return out, status, sorted([jpg[k] for k in fa] + [other[k] for k in fb])
+
+
+# ----------------------------------------------------------------------------- Motion-JPEG in a RIFF AVI: reading
+class MjpegReader:
+    """The frames of a Motion-JPEG RIFF AVI (every file MjpegWriter writes; no OpenDML, the first video stream only): avih
+    and strh give size, frame count and rate; the frames are the 00dc / 00db chunks of LIST movi in file order (found by
+    walking movi, so idx1 is not needed; chunks are padded to even length; LIST rec groups are entered).  ValueError for a
+    file that is not a RIFF AVI or whose video stream's handler / compression is not MJPG."""
+
+    def __init__(self, path):
+        self.path = path
+        with open(path, "rb") as f:
+            data = f.read()
+        self._data = data
+        n = len(data)
+        if n < 12 or data[:4] != b"RIFF" or data[8:12] != b"AVI ":
+            raise ValueError("mjpeg: %s is not a RIFF AVI" % (path,))
+        self.width = self.height = None
+        self.rate, self.scale = 0, 1
+        self._usec = 0
+        self._chunks = []                 # (position of the payload, length)
+        handler = None
+        seen_strh = False
+
+        def walk(lo, hi, depth):
+            nonlocal handler, seen_strh
+            pos = lo
+            while pos + 8 <= hi:
+                tag = data[pos:pos + 4]
+                size, = struct.unpack("<I", data[pos + 4:pos + 8])
+                end = pos + 8 + size
+                if end > hi:
+                    if tag == b"LIST" and data[pos + 8:pos + 12] == b"movi":
+                        end = hi                        # a movie cut short: take the chunks that are whole
+                    else:
+                        break
+                if tag == b"LIST":
+                    if depth < 4 and end >= pos + 12:
+                        walk(pos + 12, end, depth + 1)
+                elif tag == b"avih" and size >= 40:
+                    v = struct.unpack("<10I", data[pos + 8:pos + 48])
+                    self._usec, self.width, self.height = v[0], v[8], v[9]
+                elif tag == b"strh" and size >= 36 and not seen_strh and data[pos + 8:pos + 12] == b"vids":
+                    seen_strh = True
+                    handler = data[pos + 12:pos + 16]
+                    self.scale, self.rate = struct.unpack("<II", data[pos + 28:pos + 36])
+                elif tag == b"strf" and seen_strh and size >= 20 and handler is not None and len(handler) == 4:
+                    handler = handler + data[pos + 24:pos + 28]          # biCompression
+                elif tag in (b"00dc", b"00db"):
+                    self._chunks.append((pos + 8, size))
+                pos = end + (size & 1 if end != hi else 0)
+
+        walk(12, n, 0)
+        if handler is None:
+            raise ValueError("mjpeg: %s has no video stream" % (path,))
+        if handler[:4].upper() != b"MJPG" and handler[4:8].upper() != b"MJPG":
+            raise ValueError("mjpeg: the video stream of %s is %r, not MJPG (Motion-JPEG is the only codec read here)"
+                             % (path, handler[:4].decode("latin-1")))
+        self._chunks = [c for c in self._chunks if c[1] > 0]             # (an empty chunk is a dropped frame)
+
+    def __len__(self):
+        return len(self._chunks)
+
+    @property
+    def size(self):
+        """(width, height) as avih states them."""
+        return self.width, self.height
+
+    @property
+    def fps(self):
+        if self.rate and self.scale:
+            return self.rate / self.scale
+        return 1e6 / self._usec if self._usec else 0.0
+
+    def frame_bytes(self, i):
+        """Frame i as the JPEG file it is."""
+        at, length = self._chunks[range(len(self._chunks))[i]]
+        return self._data[at:at + length]
+
+    def read_device(self, indices=None, channels="first", device=None, return_info=False):
+        """decode_jpeg_device of the frames `indices` (a slice, an iterable of indices, None: all), in that order."""
+        if indices is None:
+            indices = slice(None)
+        picks = range(len(self))[indices] if isinstance(indices, slice) else [range(len(self))[int(i)] for i in indices]
+        return decode_jpeg_device([self.frame_bytes(i) for i in picks], device=device, channels=channels,
+                                  return_info=return_info)

@@ -159,23 +159,34 @@ def _load_one(force_dim, grayscale, filename, as_uint8=False):
 
 
 def build_X(total_load, img_file_list, force_dim=224, grayscale=False, as_uint8=False, device_resize=False,
-            device_decode=False):
+            device_decode=False, frames=None):
     """PNG -> X float32 [N,H,W,C] scaled to [-1,1]; channel 0 only when grayscale (utils.py:325-421).
     as_uint8 (additive, grayscale only): keep the decoded grey levels, uint8 [N,H,W,1]; Model.predict applies the
     same scaling on the device (bit-identical), and the frames cross PCIe as bytes.
     device_resize (additive, with as_uint8): the grey levels are kept at the files' own size and force_dim is left to
     Model.predict(X, resize=True), which resizes on the device exactly as PIL does here (spnet_amd/resize.py).
     device_decode (additive, with as_uint8; implies device_resize): the files' bytes are uploaded as they are and decoded
-    on the GPU (spnet_amd.png.read_png_device); X is then a uint8 DEVICE tensor [N,h,w,1] at the files' own size, with
-    the same grey levels."""
+    on the GPU (spnet_amd.jpeg.read_frames_device: PNG files by spnet_amd.png.read_png_device, JPEG files by
+    read_jpeg_device); X is then a uint8 DEVICE tensor [N,h,w,1] at the files' own size, with the same grey levels.
+    frames (additive, with as_uint8): uint8 frames that are already in device memory, [N,h,w] or [N,h,w,1] (the frames of
+    a movie, spnet_amd.jpeg.MjpegReader.read_device): X is the first total_load of them as [N,h,w,1]; no file is opened."""
     print("      Reading images and assigning as input X...")
     if as_uint8 and not grayscale:
         raise ValueError("as_uint8 is for grayscale input (model_type 'big' / 'monolithic')")
+    if frames is not None:
+        if not as_uint8:
+            raise ValueError("frames needs as_uint8=True (they are 8-bit grey levels)")
+        if frames.dim() not in (3, 4) or (frames.dim() == 4 and int(frames.shape[3]) != 1) or int(frames.shape[0]) < total_load:
+            raise ValueError("frames are at least %d grey frames [N,h,w] or [N,h,w,1], got %s"
+                             % (total_load, tuple(frames.shape)))
+        X = frames[0:total_load]
+        X = X.unsqueeze(-1) if X.dim() == 3 else X
+        return X, tuple(int(v) for v in X.shape[1:])
     if device_decode:
         if not as_uint8:
             raise ValueError("device_decode needs as_uint8=True (the device decodes to 8-bit grey levels)")
-        from .png import read_png_device
-        X = read_png_device(list(img_file_list[0:total_load])).unsqueeze(-1)
+        from .jpeg import read_frames_device
+        X = read_frames_device(list(img_file_list[0:total_load])).unsqueeze(-1)
         return X, tuple(int(v) for v in X.shape[1:])
     if device_resize:
         if not as_uint8:
@@ -273,7 +284,7 @@ def draw_ellipse(img, center, axes, angle, startAngle=0, endAngle=360, color=(0,
 
 def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_extra=None, out_csv=None,
                        show_true=True, verbosity=0, png="host", png_chunk=64, draw="host", device_decode=False,
-                       jpeg_quality=90, movie=None, movie_fps=5.0):
+                       jpeg_quality=90, movie=None, movie_fps=5.0, frames=None):
     """Overlay PNGs steelpan_pred_%05d.png and the zooniverse-style CSV (cx,cy,file,rings,a,b,angle)
     from de-normalised true / predicted grids (utils.py:67-137).  png = "host": every overlay is saved by Pillow as it is
     drawn; "device" (additive): the drawn RGB overlays are collected png_chunk at a time, uploaded, encoded on the GPU
@@ -286,18 +297,23 @@ def show_pred_ellipses(Yt, Yp, file_list, num_draw=40, log_dir='./logs/', ind_ex
     draw = "host": Pillow draws; "device" (additive): the loop only plans (spnet_amd.overlay.plan_overlays), the frames
     are loaded png_chunk at a time -- by the device decoder with device_decode, else by Pillow and one upload per chunk --
     and one HIP launch per chunk draws them: the same file names and CSV rows, the same pixels away from outline edges
-    (spnet_amd/overlay.py has the rule)."""
+    (spnet_amd/overlay.py has the rule).
+    frames (additive, with draw="device"): the frames themselves, a uint8 device tensor [N,H,W] (grey) or [N,H,W,3] in the
+    order of file_list (the frames of a movie, spnet_amd.jpeg.MjpegReader.read_device); file_list then only names them and
+    no file is opened."""
     if png not in ("host", "device", "device-lz", "device-jpeg"):
         raise ValueError('show_pred_ellipses: png is "host", "device", "device-lz" or "device-jpeg", got %r' % (png,))
     if draw not in ("host", "device"):
         raise ValueError('show_pred_ellipses: draw is "host" or "device", got %r' % (draw,))
     if draw == "host" and device_decode:
         raise ValueError('show_pred_ellipses: device_decode loads the frames for draw="device"')
+    if draw == "host" and frames is not None:
+        raise ValueError('show_pred_ellipses: frames= are device frames for draw="device"')
     sink = _OverlaySink(png, jpeg_quality, movie, movie_fps)
     try:
         if draw == "device":
             return _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk,
-                                              device_decode, sink)
+                                              device_decode, sink, frames)
         return _show_pred_ellipses_host(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk, sink)
     finally:
         sink.close()
@@ -385,7 +401,7 @@ def _show_pred_ellipses_host(Yt, Yp, file_list, num_draw, log_dir, out_csv, show
 
 
 def _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, show_true, png, png_chunk, device_decode,
-                               sink):
+                               sink, given=None):
     """show_pred_ellipses(draw="device"): runs of frames of one size, at most png_chunk long, are loaded, planned, drawn
     by csrc/overlay.hip and written; the CSV rows of a chunk are appended once its files are written."""
     import torch
@@ -393,6 +409,8 @@ def _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, sh
     if not torch.cuda.is_available():
         raise RuntimeError('show_pred_ellipses: draw="device" draws on the GPU (no CPU fallback)')
     num_draw = min(num_draw, Yt.shape[0], len(file_list))
+    if given is not None:
+        num_draw = min(num_draw, int(given.shape[0]))
     if out_csv is not None:
         open(out_csv, "w").close()
     png_chunk = max(int(png_chunk), 1)
@@ -416,9 +434,9 @@ def _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, sh
     def decode_on_device(names):
         """uint8 device frames [n,H,W] | [n,H,W,3] equal to Image.open(f).convert("RGB") of every file, or None where the
         device decoder does not give that for this chunk (mixed sizes or kinds, a palette or 16-bit file): Pillow then."""
-        from .png import read_png_device
+        from .jpeg import read_frames_device
         try:
-            frames, _, fallback = read_png_device(names, channels="all", return_info=True)
+            frames, _, fallback = read_frames_device(names, channels="all", return_info=True)
         except ValueError:
             return None
         if fallback:
@@ -428,6 +446,9 @@ def _show_pred_ellipses_device(Yt, Yp, file_list, num_draw, log_dir, out_csv, sh
 
     for lo in range(0, num_draw, png_chunk):
         names = list(file_list[lo:min(lo + png_chunk, num_draw)])
+        if given is not None:
+            finish(lo, given[lo:lo + len(names)])
+            continue
         frames = decode_on_device(names) if device_decode else None
         if frames is not None:
             finish(lo, frames)

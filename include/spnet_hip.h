@@ -333,7 +333,9 @@ int spnet_maxpool3x3s2_valid_bwd(const float* dy, const uint32_t* idx4, float* d
 int spnet_avgpool3x3s1_same(const float* in, float* out, int B, int H, int W, int C, int backward, void* stream);
 /* Patch matrix of a KH x KW / stride s / 'same' | 'valid' convolution and its adjoint: backward = 0: out = col
  * [B*OH*OW][KH*KW*C] from in = x; backward = 1: out = dx [B][H][W][C] from in = dcol.  The convolution itself is
- * spnet_gemm_f32 on col and the flattened HWIO kernel (1x1 convs skip the patch matrix). */
+ * spnet_gemm_f32 on col and the flattened HWIO kernel (1x1 convs skip the patch matrix).  C % 4 == 0, stride 1 | 2;
+ * a shape without output (B, H or W < 1; VALID with H < KH or W < KW, at either stride) or a NULL tensor is
+ * hipErrorInvalidValue (spnet_patches_ld and spnet_conv_gemm_f32 alike). */
 int spnet_patches(const float* in, float* out, int B, int H, int W, int C, int KH, int KW, int stride, int same, int backward,
                   void* stream);
 /* The forward gather of an input whose pixels are ldx floats apart (a column block of a wider tensor). */
@@ -354,7 +356,12 @@ int spnet_conv_gemm_f32(const float* x, long ldx, const float* Wk, float* y, int
  * spnet_grad_bnsums_rows(pixels, max_rows).  spnet_patches_bwd_bnsums = spnet_patches(backward = 1) + mask + sums (the
  * consumer is a k x k convolution); spnet_copy_cols_bnsums = one branch of a Concatenate backward (strided column block
  * -> dense) + mask + sums.  The layer's BatchNorm backward then runs spnet_bn_bwd_from_partials with no activation
- * (keras InceptionResNetV2 conv2d_bn chains; call site spnet/models.py:357-359). */
+ * (keras InceptionResNetV2 conv2d_bn chains; call site spnet/models.py:357-359).
+ * `rows` may be any count from 1 to spnet_grad_bnsums_rows(pixels, rows) (anything else: hipErrorInvalidValue).  Pixel
+ * r = (b*H + h)*W + w (row r of the column block) belongs to partial row (r / 32) % rows: a row takes 32 consecutive
+ * pixels, then strides by rows * 32; partial[p][0][c] = sum g, partial[p][1][c] = sum g * xhat over those pixels.
+ * A shape without output (B, H or W < 1; a VALID window longer than the image, at either stride), a NULL tensor, a row
+ * stride below C, or M >= 2^31 is hipErrorInvalidValue, and nothing is launched. */
 long spnet_grad_bnsums_rows(long npix, int max_rows);
 int spnet_patches_bwd_bnsums(const float* dcol, float* dx, int B, int H, int W, int C, int KH, int KW, int stride, int same,
                              const float* y, const float* yp, const float* mean, const float* invstd, int relu,
@@ -377,7 +384,8 @@ int spnet_copy_cols_batched(const void* jobs, int njobs, long max_elems, void* s
 /* inception_resnet_block: y = x + scale*up (+ ReLU); backward: dx = g*(y>0 if relu), dup = scale*dx. */
 int spnet_resadd(const float* x, const float* up, float* y, long n, float scale, int relu, void* stream);
 int spnet_resadd_bwd(const float* y, const float* g, float* dx, float* dup, long n, float scale, int relu, void* stream);
-/* dst[r*ldd + c] (+)= src[r*lds + c] for c < cols: Concatenate's channel blocks and gradient accumulation. */
+/* dst[r*ldd + c] (+)= src[r*lds + c] for c < cols: Concatenate's channel blocks and gradient accumulation.  cols, lds, ldd
+ * multiples of 4; lds >= cols and ldd >= cols (overlapping rows are refused). */
 int spnet_copy_cols(const float* src, int lds, float* dst, int ldd, long rows, int cols, int accumulate, void* stream);
 
 /* ---- small-channel direct 3x3 convs: stem conv2d_1..3 (models.py:321,330,335), block1_conv1 ---- */
@@ -618,7 +626,8 @@ long spnet_dense_conv7_ws(int B, int H, int W);
 int spnet_dense_conv7(int op, const float* a, const float* b, float* out, int B, int H, int W, float* workspace,
                       long ws_floats, void* stream);
 /* Column sums (sum, sum of squares) of x [M][C] (row stride ldx) as partial[spnet_dense_rows(M)][2][C] rows, the input of
- * spnet_bn_finalize_fwd: the batch statistics of a dense block's input channels. */
+ * spnet_bn_finalize_fwd: the batch statistics of a dense block's input channels.  Partial row p holds the rows (pixels)
+ * 64p .. 64p+63 of x (the last one fewer when M % 64 != 0); spnet_dense_rows(M) = ceil(M / 64). */
 long spnet_dense_rows(long M);
 int spnet_dense_colsums_ld(const float* x, long ldx, long M, int C, float* partial, void* stream);
 /* Affine of one consumer BatchNorm over channels [0, c) as coef = [scale | 0 | shift] (cld floats each, zero from c on):
@@ -631,7 +640,8 @@ int spnet_dense_coeffs(int c, int cld, const float* gamma, const float* beta, co
 int spnet_dense_apply_ld(const float* x, long ldx, long M, int C, const float* coef, int cld, int relu, float* y, long ldy,
                          void* stream);
 /* Consumer backward: g = dz * [scale*x + shift > 0] (relu) | dz; G[:, :c] += gamma*g; partial[spnet_dense_rows(M)][2][c]
- * = (sum g, sum g*x^).  spnet_dense_consumer_fin: dbeta = sum g, dgamma = sum g*x^, u += gamma*dbeta, v += gamma*dgamma. */
+ * = (sum g, sum g*x^), partial row p over the pixels 64p .. 64p+63 (dense rows of c floats).  spnet_dense_consumer_fin:
+ * dbeta = sum g, dgamma = sum g*x^ over P such rows, u += gamma*dbeta, v += gamma*dgamma. */
 int spnet_dense_consumer_bwd(const float* dz, long ldz, const float* x, long ldx, long M, int c, const float* coef, int cld,
                              const float* mean, const float* invstd, const float* gamma, int relu, float* G, long ldg,
                              float* partial, void* stream);

@@ -17,6 +17,10 @@ static inline int spnet_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
     return (int)e__;                            \
   } while (0)
 
+// Output extent of a VALID window of k taps at stride s over `in` elements: floor((in - k) / s) + 1, 0 when the window
+// is longer than the input.  (C++ division truncates toward zero: in = k - 1 at stride 2 would give (-1)/2 + 1 = 1.)
+static inline int spnet_valid_out(int in, int k, int s) { return in < k ? 0 : (in - k) / s + 1; }
+
 // Memory-bound elementwise kernels: cap the grid and grid-stride the rest (256 CUs x 8 blocks).
 static inline int spnet_ew_grid(long n_items, int block) {
   long g = (n_items + block - 1) / block;

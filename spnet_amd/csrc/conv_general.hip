@@ -190,7 +190,7 @@ static void conv_geom(int in, int k, int s, int same, int* out, int* before) {
     if (total < 0) total = 0;
     *before = total / 2;
   } else {
-    *out = (in - k) / s + 1;
+    *out = spnet_valid_out(in, k, s);
     *before = 0;
   }
 }
@@ -198,7 +198,8 @@ static void conv_geom(int in, int k, int s, int same, int* out, int* before) {
 // backward == 0: col [B*OH*OW][KH*KW*C] from x;  backward == 1: dx [B][H][W][C] from dcol (x = dcol, out = dx).
 extern "C" int spnet_patches(const float* in, float* out, int B, int H, int W, int C, int KH, int KW, int stride, int same,
                              int backward, void* stream) {
-  if ((C & 3) || KH < 1 || KW < 1 || (stride != 1 && stride != 2)) return (int)hipErrorInvalidValue;
+  if (!in || !out || B < 1 || H < 1 || W < 1 || (C & 3) || KH < 1 || KW < 1 || (stride != 1 && stride != 2))
+    return (int)hipErrorInvalidValue;
   int OH, OW, pt, pl;
   conv_geom(H, KH, stride, same, &OH, &pt);
   conv_geom(W, KW, stride, same, &OW, &pl);
@@ -224,7 +225,8 @@ extern "C" int spnet_patches_bwd_bnsums_ld(const float* dcol, float* dx, long ld
                                            int stride, int same, const float* y, long ldy, const float* yp, long ldyp,
                                            const float* mean, const float* invstd, int relu, float* partial, long ldp,
                                            int rows, void* stream) {
-  if ((C & 3) || KH < 1 || KW < 1 || (stride != 1 && stride != 2) || !yp || !mean || !invstd || !partial || (relu && !y))
+  if (!dcol || !dx || B < 1 || H < 1 || W < 1 || (C & 3) || KH < 1 || KW < 1 || (stride != 1 && stride != 2) || !yp ||
+      !mean || !invstd || !partial || (relu && !y))
     return (int)hipErrorInvalidValue;
   if (lddx < C || ldy < C || ldyp < C || ldp < C || ((lddx | ldy | ldyp | ldp) & 3)) return (int)hipErrorInvalidValue;
   int OH, OW, pt, pl;
@@ -256,7 +258,10 @@ extern "C" int spnet_patches_bwd_bnsums(const float* dcol, float* dx, int B, int
 extern "C" int spnet_copy_cols_bnsums_ld(const float* src, int lds, float* dst, long ldd, long M, int C, const float* y,
                                          long ldy, const float* yp, long ldyp, const float* mean, const float* invstd,
                                          int relu, float* partial, long ldp, int rows, void* stream) {
-  if ((C & 3) || (lds & 3) || M < 1 || !yp || !mean || !invstd || !partial || (relu && !y)) return (int)hipErrorInvalidValue;
+  // (the kernel runs this as a 1 x 1 x M image: M is an int there)
+  if (!src || !dst || (C & 3) || (lds & 3) || lds < C || M < 1 || M >= (1L << 31) || !yp || !mean || !invstd || !partial ||
+      (relu && !y))
+    return (int)hipErrorInvalidValue;
   if (ldd < C || ldy < C || ldyp < C || ldp < C || ((ldd | ldy | ldyp | ldp) & 3)) return (int)hipErrorInvalidValue;
   if (rows < 1 || rows > spnet_grad_bnsums_rows(M, rows)) return (int)hipErrorInvalidValue;
   dim3 grid((C / 4 + GS_CL - 1) / GS_CL, (unsigned)rows), block(GS_CL, 32);
@@ -302,7 +307,9 @@ extern "C" int spnet_copy_cols_batched(const void* jobs, int njobs, long max_ele
 // output of one member of a sibling group, _IRGroup).
 extern "C" int spnet_patches_ld(const float* in, long ldx, float* out, int B, int H, int W, int C, int KH, int KW, int stride,
                                 int same, void* stream) {
-  if ((C & 3) || (ldx & 3) || ldx < C || KH < 1 || KW < 1 || (stride != 1 && stride != 2)) return (int)hipErrorInvalidValue;
+  if (!in || !out || B < 1 || H < 1 || W < 1 || (C & 3) || (ldx & 3) || ldx < C || KH < 1 || KW < 1 ||
+      (stride != 1 && stride != 2))
+    return (int)hipErrorInvalidValue;
   int OH, OW, pt, pl;
   conv_geom(H, KH, stride, same, &OH, &pt);
   conv_geom(W, KW, stride, same, &OW, &pl);
@@ -314,8 +321,8 @@ extern "C" int spnet_patches_ld(const float* in, long ldx, float* out, int B, in
 }
 
 // inception_resnet_block's Lambda + Activation: y = x + scale*up, ReLU if relu.
-// backward (y = the forward OUTPUT, g = dL/dy): gm = g * (y > 0 if relu); dup = scale * gm; dx = gm (written only when
-// dx != g: with dx == g and no ReLU the incoming buffer already is the x-branch gradient).
+// backward (y = the forward OUTPUT, g = dL/dy): gm = g * (y > 0 if relu); dup = scale * gm; dx = gm, always written (dx may
+// be g itself: every element is read before it is stored, by the same thread).
 __global__ __launch_bounds__(256) void resadd_kernel(const float* __restrict__ x, const float* __restrict__ up,
                                                      float* __restrict__ y, long n4, float scale, int relu) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -354,7 +361,8 @@ extern "C" int spnet_resadd_bwd(const float* y, const float* g, float* dx, float
 }
 
 // Gradient accumulation where a tensor feeds several branches, and channel-block copies for Concatenate:
-// dst[r*ldd + c] (+)= src[r*lds + c], c < cols (cols, ldd, lds multiples of 4).
+// dst[r*ldd + c] (+)= src[r*lds + c], c < cols (cols, ldd, lds multiples of 4; lds, ldd >= cols: rows that overlap would
+// make an accumulation depend on the order of the threads, and are refused as the GEMM family refuses them).
 __global__ __launch_bounds__(256) void copy_cols_kernel(const float* __restrict__ src, int lds, float* __restrict__ dst,
                                                         int ldd, long rows, int cols, int accumulate) {
   const int c4n = cols >> 2;
@@ -374,7 +382,7 @@ __global__ __launch_bounds__(256) void copy_cols_kernel(const float* __restrict_
 
 extern "C" int spnet_copy_cols(const float* src, int lds, float* dst, int ldd, long rows, int cols, int accumulate,
                                void* stream) {
-  if ((cols & 3) || (lds & 3) || (ldd & 3) || rows < 1) return (int)hipErrorInvalidValue;
+  if ((cols & 3) || (lds & 3) || (ldd & 3) || lds < cols || ldd < cols || rows < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(copy_cols_kernel, dim3(spnet_ew_grid(rows * (cols / 4), 256)), dim3(256), 0, (hipStream_t)stream, src,
                      lds, dst, ldd, rows, cols, accumulate ? 1 : 0);
   SPNET_RETURN_LAUNCH_STATUS();

@@ -642,7 +642,7 @@ extern "C" int spnet_conv_gemm_f32(const float* x, long ldx, const float* Wk, fl
     int th = (cg.OH - 1) * stride + KH - H, tw = (cg.OW - 1) * stride + KW - W;
     cg.pt = (th < 0 ? 0 : th) / 2; cg.pl = (tw < 0 ? 0 : tw) / 2;
   } else {
-    cg.OH = (H - KH) / stride + 1; cg.OW = (W - KW) / stride + 1;
+    cg.OH = spnet_valid_out(H, KH, stride); cg.OW = spnet_valid_out(W, KW, stride);
     cg.pt = cg.pl = 0;
   }
   if (cg.OH < 1 || cg.OW < 1) return (int)hipErrorInvalidValue;

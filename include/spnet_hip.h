@@ -61,7 +61,7 @@ int spnet_gemm_plan(int a_major, int b_major, int M, int N, int K, int split_k, 
  *                                K = cin, N = cout, sn 1, sk cout; data gradient dX = dY W^T: K = cout, N = cin, sn cout,
  *                                sk 1); max_elems = the largest plane_elems(N, K) of the batch
  *   spnet_gemm_bf16x3_fwd        C[M][N] = A B^T, A [M][K] fp32 split inside the kernel (lda % 4 == 0, K % 4 == 0, 16-byte
- *                                aligned), B = planes of [N][K]
+ *                                aligned, lda >= K, ldc >= N), B = planes of [N][K]
  *   spnet_gemm_bf16x3_pp         the same with A given as planes of [M][K] (written by the producing kernel:
  *                                spnet_dwconv3x3_*_x3, spnet_bn_bwd_*_x3): no split, no stage registers, LDS-DMA only
  *   _colstats / colstats != NULL BatchNorm column sums of C as [*stat_rows][2][N] partial rows, *stat_rows = ceil(M/96)

@@ -828,7 +828,7 @@ static bool x3_planes_ok(const void* p, long R, int K) {
 // C[M][N] = A[M][K] * B, A fp32 (lda % 4 == 0, K % 4 == 0, 16-byte aligned), B given as the planes of [N][K].
 static int x3_launch(const float* A, int lda, const void* planes, float* C, int ldc, int M, int N, int K, float* colstats,
                      int* stat_rows, void* stream) {
-  if (!A || !C || M < 1 || N < 1 || K < 4 || (lda & 3) || (K & 3)) return (int)hipErrorInvalidValue;
+  if (!A || !C || M < 1 || N < 1 || K < 4 || (lda & 3) || (K & 3) || lda < K || ldc < N) return (int)hipErrorInvalidValue;
   if ((((uintptr_t)A) & 15) || !x3_planes_ok(planes, N, K)) return (int)hipErrorInvalidValue;
   const int tm = spnet_cdiv(M, X3_BM), tn = spnet_cdiv(N, X3_BN);
   if (stat_rows) *stat_rows = tm;

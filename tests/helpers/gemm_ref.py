@@ -3,7 +3,8 @@
 numpy only, nothing of the code under test.  The idea: with small integer operands whose absolute product
 (|A| @ |B|).max() stays below 2^24, every partial sum of every summation order is an integer that fp32 holds exactly, so
 every tile, operand form, main loop, K split and fused epilogue must return the int64 product bit for bit -- no tolerance.
-The same holds for the bf16x3 kernels while |a|, |b| <= 256 (such integers are their own high bf16 piece).
+The same holds for the bf16x3 kernels while |a|, |b| <= 256 (such integers are their own high bf16 piece), and, for all
+six of their piece products, with the multi-piece integers of x3_operands() at the end of this file.
 
 embed() places a matrix as a column block of a wider, guarded buffer; check_output() compares the block with the int64
 result and demands that nothing outside the block was written.  Inputs are poisoned with NaN outside their block: a kernel
@@ -190,3 +191,109 @@ def patch_matrix(x, KH, KW, stride, same):
                     if 0 <= ih < H and 0 <= iw < W:
                         col[:, oh, ow, kh, kw, :] = x[:, ih, iw, :]
     return col.reshape(B * OH * OW, KH * KW * C)
+
+
+# ---- bf16x3: exact operands with non-zero middle and low pieces (csrc/gemm_bf16x3.hip, x3t.h) ----------------------------
+# A bf16x3 kernel forms ah*bh + (ah*bm + am*bh) + (ah*bl + am*bm + al*bh) from the pieces h = bf16(x), m = bf16(x - h),
+# l = bf16(x - h - m) and drops am*bl, al*bm, al*bl.  x3_operands() draws integer operands in which the dropped terms are
+# identically zero while all six kept ones occur, so that the int64 product is what such a kernel must return bit for bit.
+X3_TERMS = ((0, 0), (0, 1), (1, 0), (0, 2), (1, 1), (2, 0))       # (piece of A, piece of B) of the six kept products
+X3_DROPPED = ((1, 2), (2, 1), (2, 2))
+X3_TERM_NAMES = {(0, 0): "ah*bh", (0, 1): "ah*bm", (1, 0): "am*bh", (0, 2): "ah*bl", (1, 1): "am*bm", (2, 0): "al*bh"}
+
+
+def bf16_rne(x):
+    """float32 -> the nearest bf16 (ties to even) as float32, by integer arithmetic on the bit pattern; finite input only"""
+    x = np.ascontiguousarray(x, np.float32)
+    if not np.isfinite(x).all():
+        raise ValueError("bf16_rne: non-finite input")
+    u = x.view(np.uint32).astype(np.uint64)
+    r = (u + np.uint64(0x7FFF) + ((u >> np.uint64(16)) & np.uint64(1))) & np.uint64(0xFFFF0000)
+    return r.astype(np.uint32).view(np.float32).reshape(x.shape)
+
+
+def bf16x3_pieces(x):
+    """[3] + x.shape float64: h = bf16(x), m = bf16(x - h), l = bf16(x - h - m) of a float32 array (both differences are
+    exact in fp32); asserts h + m + l == x"""
+    x = np.asarray(x)
+    x32 = x.astype(np.float32)
+    if not np.array_equal(x32.astype(np.float64), x.astype(np.float64)):
+        raise ValueError("bf16x3_pieces: the values are not float32")
+    h = bf16_rne(x32)
+    r = x32 - h
+    m = bf16_rne(r)
+    l = bf16_rne(r - m)
+    p = np.stack([h, m, l]).astype(np.float64)
+    assert np.array_equal(p.sum(0), x32.astype(np.float64)), "the three pieces do not sum to x"
+    return p
+
+
+def _hot(ks, count):
+    """`count` of the indices ks, evenly spread, the first and the last among them"""
+    ks = np.asarray(ks)
+    if count <= 0 or ks.size == 0:
+        return ks[:0]
+    return ks[np.unique(np.rint(np.linspace(0, ks.size - 1, min(count, ks.size))).astype(int))]
+
+
+def _multi(rs, shape, pieces):
+    """integers with exactly `pieces` non-zero bf16 pieces: 3: +-((128 + j) * 2^11 +- (128 + i) * 4 +- 1), about 2^18 (the
+    smallest magnitude at which an INTEGER has a low piece that no rounding tie decides); 2: +-((128 + j) * 4 +- 1), about 2^9"""
+    sgn = lambda: rs.choice([-1, 1], size=shape)
+    if pieces == 3:
+        v = sgn() * ((128 + rs.randint(1, 17, size=shape)) * 2048 + sgn() * (128 + rs.randint(0, 128, size=shape)) * 4 + sgn())
+    else:
+        v = sgn() * ((128 + rs.randint(1, 17, size=shape)) * 4 + sgn())
+    return v.astype(np.int64)
+
+
+def x3_operands(M, N, K, seed, density=0.7, hot=3, pieces=3, pair=True, swap=False, small=2, facing=1.0, a_every=0):
+    """(A [M][K], B [K][N]) integer-valued float32.  The contraction index k falls into three classes by k % 3:
+         0: A is a `pieces`-piece integer in some places, B a small one      -> ah*bh, am*bh, al*bh
+         1: the mirror image                                                 -> ah*bh, ah*bm, ah*bl
+         2: A and B are both two-piece integers in some places (pair)        -> ah*bh, ah*bm, am*bh, am*bm
+    and everything else is a small integer |v| <= small (its own high piece).  No k pairs (m, l), (l, m) or (l, l): the
+    three products a bf16x3 kernel drops are identically zero.  The multi-piece entries sit at `hot` values of k per class
+    only -- evenly spread over the class, its first and its last k among them, so that the first and the last K step, and
+    every slice of a K split, hold some -- and there in a share `density` of the rows of A / columns of B: a fixed small
+    count per row and per column, whatever K, which is what keeps (|A| @ |B|).max() below 2^24 at a long K.
+    swap: classes 0 and 1 change roles (B multi-piece where A was).  pieces=2, pair=False: two-piece values times small
+    ones only, small enough for exact column statistics.  density and facing may be pairs (for A, for B); facing < 1
+    zeroes that share of the SMALL entries that face the other operand's multi-piece ones (a row of B at a hot k of A and
+    the reverse): sums over many rows of the product -- column statistics, the sums behind a fused epilogue -- then stay
+    below 2^24 as well.  a_every = P > 0 replaces the random choice of A's rows by a regular one, for the operands of a
+    kernel that sums over row tiles: rows P apart (another offset for every hot k), so that every tile of P or more rows,
+    a ragged last one included, holds its share; B is drawn as before."""
+    pair_of = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    (da, db), (fa, fb) = pair_of(density), pair_of(facing)
+    rs = np.random.RandomState(seed)
+    A = rs.randint(-small, small + 1, size=(M, K)).astype(np.int64)
+    B = rs.randint(-small, small + 1, size=(K, N)).astype(np.int64)
+    k = np.arange(K)
+    ca, cb = (1, 0) if swap else (0, 1)
+    rows_a = lambda share, off: (np.arange(M) - off) % a_every == 0 if a_every > 0 else rs.random_sample(M) < share
+    for j, kk in enumerate(_hot(k[k % 3 == ca], hot)):
+        A[:, kk] = np.where(rows_a(da, 16 * j), _multi(rs, M, pieces), A[:, kk])
+        B[kk, :] *= rs.random_sample(N) < fb
+    for j, kk in enumerate(_hot(k[k % 3 == cb], hot)):
+        B[kk, :] = np.where(rs.random_sample(N) < db, _multi(rs, N, pieces), B[kk, :])
+        A[:, kk] *= rows_a(fa, 16 * j + 5)
+    if pair:
+        for j, kk in enumerate(_hot(k[k % 3 == 2], hot)):
+            A[:, kk] = np.where(rows_a(da, 16 * j + 10), _multi(rs, M, 2), A[:, kk])
+            B[kk, :] = np.where(rs.random_sample(N) < db, _multi(rs, N, 2), B[kk, :])
+    return A.astype(np.float32), B.astype(np.float32)
+
+
+def x3_term(pa, pb, i, j):
+    """the contribution of the product (piece i of A) x (piece j of B), int64 [M][N]"""
+    return as_int(pa[i]) @ as_int(pb[j])
+
+
+def x3_model(pa, pb, scale=None):
+    """what a six-term kernel returns from the pieces pa [3][M][K], pb [3][K][N]; scale: {(i, j): factor} (0 knocks a term
+    out, 2 doubles it)"""
+    out = 0
+    for t in X3_TERMS:
+        out = out + x3_term(pa, pb, *t) * (1 if scale is None else scale.get(t, 1))
+    return out

@@ -1,7 +1,9 @@
 """tests/helpers/gemm_ref.py and the tables of tests/test_gemm_gpu.py, without a GPU: the checker finds what a subtly wrong
 strided GEMM does (numpy models of a correct kernel and of eight broken ones), assert_exact rejects operands that are not
 exact, the patch-matrix restatement agrees with the oracle's convolution, and spnet_gemm_plan (host only) confirms that
-every row of the GPU tables takes the path it is there for."""
+every row of the GPU tables takes the path it is there for.  At the end: the multi-piece operands of
+tests/test_gemm_x3_gpu.py -- the six-term model of a bf16x3 kernel equals the int64 product on every one of them, and a
+dropped or doubled term, or swapped middle and low planes, does not."""
 import ctypes
 
 import numpy as np
@@ -216,3 +218,133 @@ def test_gpu_table_operands_are_exact():
     for base, table in ((500, G.BATCHED), (600, G.BATCHED_SPLIT)):
         for i, row in enumerate(table):
             G.batch_operands(*row[-3:], base + i)
+
+
+# ---- the bf16x3 operands of tests/test_gemm_x3_gpu.py: what a subtly wrong six-term kernel would do to them ------------------
+from tests import test_gemm_x3_gpu as X
+
+
+def x3_sets():
+    """(name, A [M][K], B [K][N], row group) of every plain GEMM operand set the GPU file launches"""
+    for i, (s, swap) in enumerate(X.GEMM):
+        yield ("gemm %dx%dx%d swap %d" % (X.X3_SHAPES[s] + (swap,)),) + X.gemm_case(i) + (96,)
+    for i, (M, c, nb) in enumerate(X.WGRAD):
+        for b in range(nb):
+            z, dy = X.wgrad_case(i, b)
+            yield ("wgrad M %d %dx%d problem %d of %d" % ((M,) + X.WGRAD_CH[c] + (b, nb)), z.T, dy, 96)
+
+
+def knock_outs(A, B, finish=None):
+    """{term: (share of outputs the model without it gets wrong, share with the term doubled)}; finish: the epilogue
+    between the GEMM and the compared output"""
+    pa, pb = R.bf16x3_pieces(A), R.bf16x3_pieces(B)
+    finish = finish or (lambda y: y)
+    want = finish(R.as_int(A) @ R.as_int(B))
+    return {t: tuple(float((finish(R.x3_model(pa, pb, {t: f})) != want).mean()) for f in (0, 2)) for t in R.X3_TERMS}
+
+
+def test_bf16_rounding_and_pieces():
+    x = np.array([1.0, 257.0, 259.0, 261.0, -257.0, 262657.0, 3.1415927, 1e-3, -7.25e5, 0.0], np.float32)
+    # 257 = 0x101 lies halfway between 256 and 258 (8 significand bits): ties go to the even one, 259 to 260
+    assert R.bf16_rne(x)[:5].tolist() == [1.0, 256.0, 260.0, 260.0, -256.0]
+    p = R.bf16x3_pieces(x)
+    assert p[:, 5].tolist() == [262144.0, 512.0, 1.0] and np.array_equal(p.sum(0), x.astype(np.float64))
+    assert np.array_equal(R.bf16_rne(p.astype(np.float32)), p.astype(np.float32))          # every piece is a bf16
+    f = X.full_mantissa((64, 64), 1)
+    q = R.bf16x3_pieces(f)
+    assert (q[2] != 0).mean() > 0.9 and (f < 0).any() and (f > 0).any() and np.abs(f).max() / np.abs(f).min() > 2.0 ** 30
+    assert (np.abs(q[1]) <= np.abs(q[0]) * 2.0 ** -8).all() and (np.abs(q[2]) <= np.abs(q[0]) * 2.0 ** -16).all()
+    with pytest.raises(ValueError):
+        R.bf16x3_pieces(np.array([0.1]))                       # not a float32
+    with pytest.raises(ValueError):
+        R.bf16_rne(np.array([np.inf], np.float32))
+
+
+def test_x3_operands_make_the_six_term_model_exact():
+    """every operand set of the GPU file: exact in fp32, the six-term model is the int64 product, the three dropped terms
+    are identically zero, and the operands do hold three-piece and two-piece values"""
+    sets = [(n, A, B) for n, A, B, _ in x3_sets()] + [("stats %d" % s,) + X.stats_case(s) for s in range(len(X.X3_SHAPES))]
+    sets += [("dwfwd %d" % i,) + X.DwFwd(i).operands() for i in range(len(X.DWFWD))]
+    sets += [("dwbwd %d" % i,) + X.DwBwd(i).operands() for i in range(len(X.DWBWD))]
+    for name, A, B in sets:
+        assert np.abs(A).max() < 2 ** 19 and np.abs(B).max() < 2 ** 19, name
+        R.assert_exact(R.as_int(A), R.as_int(B))
+        pa, pb = R.bf16x3_pieces(A), R.bf16x3_pieces(B)
+        assert np.array_equal(R.x3_model(pa, pb), R.as_int(A) @ R.as_int(B)), name
+        for t in R.X3_DROPPED:
+            assert not R.x3_term(pa, pb, *t).any(), (name, t)
+        if not name.startswith("stats"):
+            assert (pa[2] != 0).any() and (pb[2] != 0).any() and ((pa[1] != 0) & (pa[2] == 0)).any(), name
+    for s in range(len(X.X3_SHAPES)):
+        A, B = X.stats_case(s)
+        R.assert_exact_stats(R.as_int(A) @ R.as_int(B), X.X3_BM)
+    for i in range(len(X.DWFWD)):
+        X.DwFwd(i).assert_exact()
+    for i in range(len(X.DWBWD)):
+        X.DwBwd(i).assert_exact()
+
+
+def test_x3_every_knock_out_shows_in_half_of_the_outputs():
+    """a kernel that drops or doubles one of its six products gets at least half of the outputs of every plain GEMM case
+    wrong -- a property of the operands, which is what makes the GPU comparison a test of all six"""
+    for name, A, B, _ in x3_sets():
+        for t, (gone, twice) in knock_outs(A, B).items():
+            assert gone >= 0.5 and twice >= 0.5, (name, R.X3_TERM_NAMES[t], gone, twice)
+
+
+def test_x3_knock_outs_show_in_the_last_row_group_and_the_last_k_step():
+    """... in the rows past the last multiple of 96 and of 16 alone, and with nothing but the last K step of 32 (the ragged
+    one, where there is one) contributing"""
+    for name, A, B, bm in x3_sets():
+        M, K = A.shape
+        for g in (bm, 16):
+            r0 = (M - 1) // g * g
+            for t, (gone, twice) in knock_outs(A[r0:], B).items():
+                assert gone > 0 and twice > 0, (name, "rows from %d" % r0, R.X3_TERM_NAMES[t])
+        k0 = (K - 1) // 32 * 32
+        for t, (gone, twice) in knock_outs(A[:, k0:], B[k0:]).items():
+            assert gone > 0 and twice > 0, (name, "k from %d" % k0, R.X3_TERM_NAMES[t])
+
+
+def test_x3_swapped_planes_show():
+    """reading the low plane for the middle one (and the reverse), of either operand, changes the result"""
+    for name, A, B, _ in x3_sets():
+        pa, pb = R.bf16x3_pieces(A), R.bf16x3_pieces(B)
+        want = R.as_int(A) @ R.as_int(B)
+        assert float((R.x3_model(pa[[0, 2, 1]], pb) != want).mean()) >= 0.5, name
+        assert float((R.x3_model(pa, pb[[0, 2, 1]]) != want).mean()) >= 0.5, name
+
+
+def test_x3_statistics_sets_hold_the_two_piece_terms():
+    for s in range(len(X.X3_SHAPES)):
+        A, B = X.stats_case(s)
+        ko = knock_outs(A, B)
+        for t in ((0, 0), (0, 1), (1, 0)):
+            assert ko[t][0] > 0 and ko[t][1] > 0, (s, R.X3_TERM_NAMES[t])
+        stat = lambda y: R.col_stats(y, X.X3_BM)
+        for t in ((0, 1), (1, 0)):
+            assert knock_outs(A, B, stat)[t][0] > 0, (s, R.X3_TERM_NAMES[t])
+
+
+def test_x3_knock_outs_reach_every_tile_of_the_fused_kernels():
+    """the fused cases are sparse in multi-piece values (sums over a tile's 192 pixels have to stay exact), so a knock-out
+    changes fewer outputs there; but each of the six changes the compared output in every 192-row tile and every block of
+    96 output channels, the ragged last ones included"""
+    cases = [("dwfwd %d" % i, X.DwFwd(i), lambda c, y: c.finish(y)) for i in range(len(X.DWFWD))]
+    cases += [("dwbwd %d" % i, X.DwBwd(i), lambda c, y: c.finish(y)[0]) for i in range(len(X.DWBWD))]
+    for name, c, fin in cases:
+        A, B = c.operands()
+        pa, pb = R.bf16x3_pieces(A), R.bf16x3_pieces(B)
+        want = fin(c, R.as_int(A) @ R.as_int(B))
+        for t in R.X3_TERMS:
+            diff = fin(c, R.x3_model(pa, pb, {t: 0})) != want
+            for r0 in range(0, diff.shape[0], X.FB_BM):
+                for c0 in range(0, diff.shape[1], 96):
+                    assert diff[r0:r0 + X.FB_BM, c0:c0 + 96].any(), (name, R.X3_TERM_NAMES[t], r0, c0)
+    c = X.DwBwd(1)
+    A, B = c.operands()
+    pa, pb = R.bf16x3_pieces(A), R.bf16x3_pieces(B)
+    _, dw, bn = c.finish(R.as_int(A) @ R.as_int(B))
+    for t in R.X3_TERMS:                                       # the summed partial rows notice as well
+        _, dw1, bn1 = c.finish(R.x3_model(pa, pb, {t: 0}))
+        assert (dw1 != dw).any() and (bn1 != bn).any(), R.X3_TERM_NAMES[t]

@@ -2,7 +2,8 @@
 seeded inputs.  fp32 tolerances are written next to each check (the kernels and the oracle sum in
 different orders, so agreement is to rounding, not bitwise, except where noted).
 The stem head, loss / head and augmentation kernels are pinned one by one in tests/test_small_kernels_gpu.py.
-The GEMM family on strided operands, against exact integer products: tests/test_gemm_gpu.py."""
+The GEMM family on strided operands, against exact integer products: tests/test_gemm_gpu.py; all six piece products
+of the bf16x3 kernels, and their planes piece by piece: tests/test_gemm_x3_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -11,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import numpy_ref as R
 from oracle import torch_ref as T
+from tests.helpers.x3_layout import x3_untile
 
 
 @pytest.fixture(scope="module")
@@ -152,17 +154,6 @@ def x3_planes(L, R, K, fill=0):
     """a zeroed (or poisoned) plane set for an [R][K] matrix"""
     n = 3 * int(L.spnet_bf16x3_plane_elems(R, K))
     return torch.full((n,), fill, dtype=torch.int16, device="cuda")
-
-
-def x3_untile(planes, R, K):
-    """planes in the pieces layout of csrc/x3t.h -> float64 [3][R16][Kp] (R16, Kp: R, K rounded up to 16 / 32): element
-    (r, k) of a plane sits at ((r/16)*nk + k/32)*512 + (r%16)*32 + (((k%32)/8 ^ -((r%16)/4)) & 3)*8 + k%8."""
-    nk, rg = (K + 31) // 32, (R + 15) // 16
-    p = planes.view(torch.bfloat16).reshape(3, rg, nk, 16, 4, 8).float().cpu().double()
-    r16 = torch.arange(16)
-    cpos = torch.arange(4)[None, :] ^ ((-(r16 // 4)) & 3)[:, None]            # [r16][chunk] -> stored position
-    q = p[:, :, :, r16[:, None], cpos, :]                                     # [3][rg][nk][16][chunk][8]
-    return q.permute(0, 1, 3, 2, 4, 5).reshape(3, rg * 16, nk * 32)
 
 
 @pytest.mark.parametrize("M,N,K", [(6144, 728, 728), (200, 96, 32), (97, 100, 260), (1536, 1024, 1536), (5000, 800, 100),

@@ -869,6 +869,40 @@ int spnet_jpeg_pixels(const int16_t* coef, long total_blocks, const int* files, 
                       int n_quant, int H, int W, int channels, unsigned char* first, unsigned char* all, int* status,
                       void* stream);
 
+/* spnet_jpeg_entropy_sync (csrc/jpeg_decode_sync.hip, csrc/jpeg_sync_core.h): spnet_jpeg_entropy's decoding of the same
+ * tables into the same workspace, for intervals that are too long for one lane (a file without restart markers is ONE
+ * interval): ONE WORKGROUP PER INTERVAL, a lane per segment of seg_bytes bytes (a multiple of 4 in 4 .. 4096; else
+ * hipErrorInvalidValue, as for the argument errors of spnet_jpeg_entropy).  The intervals need no grouping by table set
+ * and no padding; an interval with MCUs 0 is skipped.  The result is spnet_jpeg_entropy's, coefficient for coefficient and
+ * status for status, whatever seg_bytes is.  Recipe:
+ *   segment      bytes [first + i seg_bytes, first + (i + 1) seg_bytes) of the interval; it OWNS every symbol (code and
+ *                magnitude bits) whose first bit lies in it, the last segment also what starts at the interval's end
+ *   state        between two symbols: position of the next bit (byte, bit; at a byte boundary the next DATA byte, never a
+ *                stuffed 00), the block's index in the MCU, the zigzag position k (0: a DC symbol is next)
+ *   first pass   segment 0 from the true state (bit 0, block 0, k 0), every other from a guess: its first bit -- one byte
+ *                later where its first byte is the 00 stuffed behind the previous segment's FF --, block 0, k 0.  A lane
+ *                decodes the symbols it owns (the reader is bounded by the interval's end, not the segment's) and notes its
+ *                exit state, the blocks that FINISHED, per component the sum of the DC differences (modulo 2^32) and
+ *                whether it met one of the errors 1 .. 4; an error ends the lane's decode, and its exit is then the next
+ *                segment's guess (the chain is cut there, the lanes behind keep what they found)
+ *   rounds       a lane takes its predecessor's latest exit as its entry and decodes again only if that differs (as a
+ *                whole) from the entry it last used; until no lane decoded again.  After round r segments 0 .. r are true,
+ *                so the fixed point is the serial decode; at most as many rounds as segments
+ *   batches      min(256, 32,768 / seg_bytes) segments at a time; lane 0 of a batch enters in the final exit of the batch
+ *                before
+ *   write        an exclusive prefix sum over the lanes gives each the ordinal of its block in progress, its three DC
+ *                predictors and whether the true decode failed before it (then it does nothing).  Each lane decodes its
+ *                symbols once more and stores them where spnet_jpeg_entropy does; a block that straddles segments is
+ *                written by several lanes at disjoint k.  No block at or beyond MCUs x blocks per MCU is decoded or
+ *                written: the lane that finishes the last block applies the trailing-bytes rule (status 5) and the lanes
+ *                behind it do nothing.  Data that ends early is status 4.
+ * status is NOT cleared: codes are merged with atomicMax, so the call follows spnet_jpeg_entropy (which clears status even
+ * with n_intervals 0) on the same status array; spnet_jpeg_pixels follows both.  Reads and writes are bounded as for
+ * spnet_jpeg_entropy; every loop is bounded by a count of segments or of the interval's bits. */
+int spnet_jpeg_entropy_sync(const unsigned char* blob, long blob_bytes, const int* intervals, int n_intervals,
+                            const int* files, int n_files, const uint32_t* tables, int n_sets, int seg_bytes, int16_t* coef,
+                            long total_blocks, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

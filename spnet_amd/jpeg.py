@@ -24,7 +24,9 @@ the markers and finds the restart intervals, plan_decode builds what the kernels
 read_jpeg_device have the contract of their PNG namesakes (one size per call, host fallback through png._host_frame, one
 pinned upload, one status download), read_frames_device routes a list of PNG and JPEG files by signature, MjpegReader
 walks a RIFF AVI.  Baseline JPEG, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0; the pixels are Pillow's, sample for sample (DESIGN.md
-section 5f).
+section 5f).  Two entropy kernels share one workspace: a lane per restart interval (spnet_jpeg_entropy) and, for the long
+intervals of files without restart markers, a workgroup per interval that decodes segments speculatively and chains them
+until the result is the serial one (spnet_jpeg_entropy_sync, csrc/jpeg_sync_core.h); entropy= picks, see ENTROPY_MODES.
 """
 import struct
 from concurrent.futures import ThreadPoolExecutor
@@ -387,6 +389,13 @@ STATUS_NAMES = ("ok", "bit pattern that is no code", "coefficient index past 63"
 TABLE_WORDS = 4 * 226           # one Huffman table set in device form: DC 0, AC 0, DC 1, AC 1 (jpeg_decode_core.h)
 MAX_BLOB = (1 << 31) - 1024     # spnet_jpeg_entropy: 32-bit byte positions
 MAX_PIXELS = 1 << 28            # H * W of one frame
+# entropy=: "interval": every restart interval is one lane of spnet_jpeg_entropy; "sync": every interval is a workgroup of
+# spnet_jpeg_entropy_sync; "auto": intervals of at least SYNC_MIN_BYTES bytes go to the sync kernel, the rest to the lane
+# kernel, in one call on one workspace.  The coefficients are the same whichever kernel wrote them.
+ENTROPY_MODES = ("auto", "interval", "sync")
+DEFAULT_ENTROPY = "auto"
+SYNC_MIN_BYTES = 8192           # the measured crossover (tools/jpeg_decode_time.py)
+SYNC_SEG_BYTES = 128            # bytes of a lane's segment: a multiple of 4 in 4 .. 4096 (measured, as above)
 _SOF_OTHER = frozenset(range(0xC1, 0xD0)) - {0xC4, 0xC8, 0xCC}
 _EMPTY_TABLE = ((0,) * 16, ())
 
@@ -628,7 +637,7 @@ def device_table(table):
     return np.concatenate([look.view(np.uint32), maxcode.view(np.uint32), valoff.view(np.uint32), symbols.view(np.uint32)])
 
 
-def plan_decode(infos):
+def plan_decode(infos, sync_min_bytes=None):
     """The arrays one launch pair reads, for files that are all info.device (host numpy arrays):
       blob       uint8: the files' entropy-coded bytes, interval after interval (markers left out)
       intervals  int32 [n][8]: first byte, end byte (positions in blob), file, first MCU, MCUs, 0, 0, 0 -- grouped by table
@@ -637,10 +646,15 @@ def plan_decode(infos):
                  (DC table | AC table << 4) x 3, quantisation table x 3, 0, 0
       tables     uint32 [sets][TABLE_WORDS], deduplicated
       quant      uint16 [q][64], natural order, deduplicated
-      blocks     8 x 8 blocks of the workspace"""
+      blocks     8 x 8 blocks of the workspace
+    sync_min_bytes (None: as above, nothing else): the intervals are split -- one of at least that many bytes goes to
+      sync_intervals  int32 [m][8], the same record, in file order, neither grouped nor padded (spnet_jpeg_entropy_sync
+                 loads the table set per interval)
+    and only the others stay in `intervals`; every interval is in exactly one of the two."""
     sets, quants = {}, {}
     files = np.zeros((len(infos), 16), np.int32)
     per_set = {}
+    sync_rows = []
     pieces = []
     at = 0
     block = 0
@@ -660,11 +674,14 @@ def plan_decode(infos):
         for i, (lo, hi) in enumerate(info.bounds):
             lo, hi = int(lo), int(hi)
             pieces.append(raw[lo:hi])
-            rows.append((at, at + hi - lo, f, i * ri, min(ri, mw * mh - i * ri), 0, 0, 0))
+            long = sync_min_bytes is not None and hi - lo >= sync_min_bytes
+            (sync_rows if long else rows).append((at, at + hi - lo, f, i * ri, min(ri, mw * mh - i * ri), 0, 0, 0))
             at += hi - lo
     intervals = []
     for s in sorted(per_set):
         rows = per_set[s]
+        if not rows:
+            continue
         f0 = rows[0][2]
         rows += [(0, 0, f0, 0, 0, 0, 0, 0)] * (-len(rows) % 64)
         intervals += rows
@@ -672,18 +689,43 @@ def plan_decode(infos):
         np.zeros((0, TABLE_WORDS), np.uint32)
     quant = np.stack([np.frombuffer(q, np.uint16) for q in quants]) if quants else np.zeros((0, 64), np.uint16)
     blob = np.concatenate(pieces) if pieces else np.zeros(0, np.uint8)
-    return dict(blob=blob, intervals=np.array(intervals, np.int32).reshape(-1, 8), files=files, tables=tables,
+    plan = dict(blob=blob, intervals=np.array(intervals, np.int32).reshape(-1, 8), files=files, tables=tables,
                 quant=quant, blocks=block)
+    if sync_min_bytes is not None:
+        plan["sync_intervals"] = np.array(sync_rows, np.int32).reshape(-1, 8)
+    return plan
+
+
+class DecodeInfo(list):
+    """The third value of return_info: the sorted indices of the files the host decoded (a list, as it always was), and as
+    attributes how many restart intervals each entropy kernel decoded in the call."""
+
+    def __init__(self, fallback=(), lane_intervals=0, sync_intervals=0):
+        super().__init__(fallback)
+        self.lane_intervals, self.sync_intervals = int(lane_intervals), int(sync_intervals)
+
+
+def _entropy_split(entropy, seg_bytes):
+    """(sync_min_bytes for plan_decode, seg_bytes) of an entropy= / seg_bytes= pair; ValueError before anything else."""
+    if entropy is None:
+        entropy = DEFAULT_ENTROPY
+    if entropy not in ENTROPY_MODES:
+        raise ValueError('jpeg: entropy is "auto", "interval" or "sync", got %r' % (entropy,))
+    seg = SYNC_SEG_BYTES if seg_bytes is None else seg_bytes
+    if not isinstance(seg, (int, np.integer)) or isinstance(seg, bool) or seg < 4 or seg > 4096 or seg % 4:
+        raise ValueError("jpeg: seg_bytes is a multiple of 4 in 4 .. 4096, got %r" % (seg_bytes,))
+    return {"interval": None, "sync": 0, "auto": SYNC_MIN_BYTES}[entropy], int(seg)
 
 
 # ----------------------------------------------------------------------------- reading: device
-def _decode_parsed(infos, sources, device, channels, return_info):
+def _decode_parsed(infos, sources, device, channels, return_info, entropy=None, seg_bytes=None):
     import os
+    if channels not in ("first", "all"):
+        raise ValueError('jpeg: channels is "first" or "all", got %r' % (channels,))
+    sync_min, seg_bytes = _entropy_split(entropy, seg_bytes)
     import torch
     from . import _lib as L
     from .png import _host_frame
-    if channels not in ("first", "all"):
-        raise ValueError('jpeg: channels is "first" or "all", got %r' % (channels,))
     if not torch.cuda.is_available():
         raise RuntimeError("jpeg: decode_jpeg_device decodes on the GPU (there is no CPU decoder here)")
     device = torch.device("cuda" if device is None else device)
@@ -699,7 +741,7 @@ def _decode_parsed(infos, sources, device, channels, return_info):
 
     if N == 0:
         out = torch.empty((0, 0, 0) if channels == "first" else (0, 0, 0, 0), dtype=torch.uint8, device=device)
-        return (out, status, []) if return_info else out
+        return (out, status, DecodeInfo()) if return_info else out
     shape = shape_of(0)
     for k in range(1, N):
         if shape_of(k) != shape:
@@ -709,15 +751,19 @@ def _decode_parsed(infos, sources, device, channels, return_info):
     out = torch.empty((N,) + tuple(shape), dtype=torch.uint8, device=device)
     H, W = int(shape[0]), int(shape[1])
     idx = [k for k in range(N) if infos[k].device]
-    plan = plan_decode([infos[k] for k in idx]) if idx else None
+    plan = plan_decode([infos[k] for k in idx], sync_min) if idx else None
+    counts = [0, 0]
     if plan is not None and (plan["blob"].size > MAX_BLOB or plan["blocks"] * 64 > (1 << 31) - 1):
         raise ValueError("jpeg: %d files of %d x %d are more than one call decodes; pass fewer" % (len(idx), W, H))
     if plan is not None:
         n = len(idx)
         C = int(shape[2]) if channels == "all" else 1
         # one pinned upload: the tables first (every piece padded to 16 bytes), the bytes last
+        sync_iv = plan.get("sync_intervals", np.zeros((0, 8), np.int32))
+        counts = [int((plan["intervals"][:, 4] > 0).sum()), int(sync_iv.shape[0])]
         parts = [plan["intervals"].view(np.uint8).ravel(), plan["files"].view(np.uint8).ravel(),
-                 plan["tables"].view(np.uint8).ravel(), plan["quant"].view(np.uint8).ravel(), plan["blob"]]
+                 plan["tables"].view(np.uint8).ravel(), plan["quant"].view(np.uint8).ravel(), plan["blob"],
+                 sync_iv.view(np.uint8).ravel()]
         starts, total = [], 0
         for p in parts:
             starts.append(total)
@@ -736,6 +782,10 @@ def _decode_parsed(infos, sources, device, channels, return_info):
             L.spnet_jpeg_entropy(base + starts[4], int(plan["blob"].size), base + starts[0], int(plan["intervals"].shape[0]),
                                  base + starts[1], n, base + starts[2], int(plan["tables"].shape[0]), coef.data_ptr(),
                                  int(plan["blocks"]), st.data_ptr(), L.current_stream())
+            if sync_iv.shape[0]:                 # behind the lane kernel, which has cleared the status
+                L.spnet_jpeg_entropy_sync(base + starts[4], int(plan["blob"].size), base + starts[5], int(sync_iv.shape[0]),
+                                          base + starts[1], n, base + starts[2], int(plan["tables"].shape[0]), seg_bytes,
+                                          coef.data_ptr(), int(plan["blocks"]), st.data_ptr(), L.current_stream())
             L.spnet_jpeg_pixels(coef.data_ptr(), int(plan["blocks"]), base + starts[1], n, base + starts[3],
                                 int(plan["quant"].shape[0]), H, W, C, got.data_ptr() if channels == "first" else 0,
                                 got.data_ptr() if channels == "all" else 0, st.data_ptr(), L.current_stream())
@@ -752,23 +802,28 @@ def _decode_parsed(infos, sources, device, channels, return_info):
     if fallback:
         up = torch.from_numpy(np.stack([host_frames[k] for k in fallback])).to(device)
         out[torch.as_tensor(fallback, device=device)] = up
-    return (out, status, fallback) if return_info else out
+    return (out, status, DecodeInfo(fallback, *counts)) if return_info else out
 
 
-def decode_jpeg_device(datas, device=None, channels="first", return_info=False, threads=MAX_THREADS):
+def decode_jpeg_device(datas, device=None, channels="first", return_info=False, threads=MAX_THREADS, entropy=None,
+                       seg_bytes=None):
     """JPEG files (a list of bytes) -> a uint8 DEVICE tensor [N,H,W] holding channel 0 of every pixel (what
     utils._load_one(..., as_uint8=True) keeps: the grey level, or R), or [N,H,W,C] with channels="all".  The entropy-coded
     bytes are uploaded as they are and decoded on the GPU (Huffman, dequantisation, IDCT, upsampling, colour).  Files the
     device does not take (see parse_jpeg) and files it rejects (status != 0) are decoded by the default path's Pillow call
     and uploaded into their place, so the pixels are the default path's in every case and a corrupt file raises what it
     raises there.  All files of a call have one size (ValueError otherwise).  return_info: also the status array
-    (jpeg_decode_core.h's codes, STATUS_NAMES) and the sorted indices of the files the host decoded."""
+    (jpeg_decode_core.h's codes, STATUS_NAMES) and the sorted indices of the files the host decoded, as a DecodeInfo,
+    whose lane_intervals / sync_intervals say how many restart intervals each entropy kernel decoded.  entropy: one of
+    ENTROPY_MODES (None: DEFAULT_ENTROPY); seg_bytes: the sync kernel's segment (None: SYNC_SEG_BYTES).  Neither changes
+    a pixel."""
     datas = list(datas)
+    _entropy_split(entropy, seg_bytes)
     if not datas:
-        return _decode_parsed([], [], device, channels, return_info)
+        return _decode_parsed([], [], device, channels, return_info, entropy, seg_bytes)
     with ThreadPoolExecutor(max_workers=_pool_size(threads, len(datas))) as pool:
         infos = list(pool.map(parse_jpeg, datas))
-    return _decode_parsed(infos, datas, device, channels, return_info)
+    return _decode_parsed(infos, datas, device, channels, return_info, entropy, seg_bytes)
 
 
 def _read_file(path):
@@ -776,15 +831,17 @@ def _read_file(path):
         return f.read()
 
 
-def read_jpeg_device(paths, threads=MAX_THREADS, device=None, channels="first", return_info=False):
+def read_jpeg_device(paths, threads=MAX_THREADS, device=None, channels="first", return_info=False, entropy=None,
+                     seg_bytes=None):
     """decode_jpeg_device of files on disk, read and parsed by a thread pool of this process (at most 16 threads; nothing
     is forked)."""
     paths = list(paths)
+    _entropy_split(entropy, seg_bytes)
     if not paths:
-        return _decode_parsed([], [], device, channels, return_info)
+        return _decode_parsed([], [], device, channels, return_info, entropy, seg_bytes)
     with ThreadPoolExecutor(max_workers=_pool_size(threads, len(paths))) as pool:
         infos = list(pool.map(lambda p: parse_jpeg(_read_file(p)), paths))
-    return _decode_parsed(infos, paths, device, channels, return_info)
+    return _decode_parsed(infos, paths, device, channels, return_info, entropy, seg_bytes)
 
 
 def _is_jpeg(path):
@@ -792,25 +849,28 @@ def _is_jpeg(path):
         return f.read(2) == b"\xff\xd8"
 
 
-def read_frames_device(paths, threads=MAX_THREADS, device=None, channels="first", return_info=False):
+def read_frames_device(paths, threads=MAX_THREADS, device=None, channels="first", return_info=False, entropy=None,
+                       seg_bytes=None):
     """Frames of PNG and JPEG files, routed by signature: files that begin FF D8 go to read_jpeg_device, every other file
     to png.read_png_device, unchanged; the results land in one tensor in input order.  A list without JPEG files is ONE
     call of read_png_device with the same arguments.  With return_info the status of a JPEG file is offset by 100 (PNG and
-    JPEG codes share one array)."""
+    JPEG codes share one array).  entropy / seg_bytes: read_jpeg_device's, handed on only where given."""
     from . import png
     paths = list(paths)
+    _entropy_split(entropy, seg_bytes)
+    how = {k: v for k, v in (("entropy", entropy), ("seg_bytes", seg_bytes)) if v is not None}
     jpg = [k for k, p in enumerate(paths) if _is_jpeg(p)]
     if not jpg:
         return png.read_png_device(paths, threads=threads, device=device, channels=channels, return_info=return_info)
     if len(jpg) == len(paths):
-        got = read_jpeg_device(paths, threads=threads, device=device, channels=channels, return_info=return_info)
+        got = read_jpeg_device(paths, threads=threads, device=device, channels=channels, return_info=return_info, **how)
         if return_info:
             return got[0], np.where(got[1] != 0, got[1] + 100, 0).astype(np.int32), got[2]
         return got
     import torch
     other = [k for k in range(len(paths)) if k not in set(jpg)]
     a, sa, fa = read_jpeg_device([paths[k] for k in jpg], threads=threads, device=device, channels=channels,
-                                 return_info=True)
+                                 return_info=True, **how)
     b, sb, fb = png.read_png_device([paths[k] for k in other], threads=threads, device=device, channels=channels,
                                     return_info=True)
     if a.shape[1:] != b.shape[1:]:
@@ -824,7 +884,8 @@ def read_frames_device(paths, threads=MAX_THREADS, device=None, channels="first"
     status = np.zeros(len(paths), np.int32)
     status[jpg] = np.where(sa != 0, sa + 100, 0)
     status[other] = sb
-    return out, status, sorted([jpg[k] for k in fa] + [other[k] for k in fb])
+    return out, status, DecodeInfo(sorted([jpg[k] for k in fa] + [other[k] for k in fb]),
+                                   getattr(fa, "lane_intervals", 0), getattr(fa, "sync_intervals", 0))
 
 
 # ----------------------------------------------------------------------------- Motion-JPEG in a RIFF AVI: reading
@@ -904,10 +965,10 @@ class MjpegReader:
         at, length = self._chunks[range(len(self._chunks))[i]]
         return self._data[at:at + length]
 
-    def read_device(self, indices=None, channels="first", device=None, return_info=False):
+    def read_device(self, indices=None, channels="first", device=None, return_info=False, entropy=None, seg_bytes=None):
         """decode_jpeg_device of the frames `indices` (a slice, an iterable of indices, None: all), in that order."""
         if indices is None:
             indices = slice(None)
         picks = range(len(self))[indices] if isinstance(indices, slice) else [range(len(self))[int(i)] for i in indices]
         return decode_jpeg_device([self.frame_bytes(i) for i in picks], device=device, channels=channels,
-                                  return_info=return_info)
+                                  return_info=return_info, entropy=entropy, seg_bytes=seg_bytes)

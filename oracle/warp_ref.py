@@ -48,18 +48,7 @@ def warp_affine_cv2(img, M):
       + 16; X = (X0 + adelta) >> 5 (1/32 px); weights (32-fy)(32-fx)*32 of 2^15 (int16 table: 32768 saturates to
       32767, harmless for 8-bit pixels); result = (sum w p + 2^14) >> 15."""
     H, W = img.shape[:2]
-    m = np.asarray(M, np.float64).reshape(2, 3).copy()
-    D = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
-    D = 1.0 / D if D != 0 else 0.0
-    A11, A22 = m[1, 1] * D, m[0, 0] * D
-    m[0, 0], m[0, 1], m[1, 0], m[1, 1] = A11, m[0, 1] * -D, m[1, 0] * -D, A22
-    b1 = -m[0, 0] * m[0, 2] - m[0, 1] * m[1, 2]
-    b2 = -m[1, 0] * m[0, 2] - m[1, 1] * m[1, 2]
-    m[0, 2], m[1, 2] = b1, b2
-    xs, ys = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
-    adelta, bdelta = np.rint(m[0, 0] * xs * 1024).astype(np.int64), np.rint(m[1, 0] * xs * 1024).astype(np.int64)
-    X0 = np.rint((m[0, 1] * ys + m[0, 2]) * 1024).astype(np.int64) + 16
-    Y0 = np.rint((m[1, 1] * ys + m[1, 2]) * 1024).astype(np.int64) + 16
+    X0, Y0, adelta, bdelta = cv2_fixed_point_terms(M, H, W)
     X = (X0[:, None] + adelta[None, :]) >> 5
     Y = (Y0[:, None] + bdelta[None, :]) >> 5
     sx, sy, fx, fy = X >> 5, Y >> 5, X & 31, Y & 31
@@ -74,6 +63,24 @@ def warp_affine_cv2(img, M):
     w01, w10, w11 = ((32 - fy) * fx * 32)[..., None], (fy * (32 - fx) * 32)[..., None], (fy * fx * 32)[..., None]
     v = (at(sy, sx) * w00 + at(sy, sx + 1) * w01 + at(sy + 1, sx) * w10 + at(sy + 1, sx + 1) * w11 + (1 << 14)) >> 15
     return np.clip(v, 0, 255).astype(np.uint8)
+
+
+def cv2_fixed_point_terms(M, H, W):
+    """the host-rounded row and column terms of warp_affine_cv2 for a forward 2x3 matrix: (X0 [H], Y0 [H], adelta [W],
+    bdelta [W]) in int64"""
+    m = np.asarray(M, np.float64).reshape(2, 3).copy()
+    D = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = m[1, 1] * D, m[0, 0] * D
+    m[0, 0], m[0, 1], m[1, 0], m[1, 1] = A11, m[0, 1] * -D, m[1, 0] * -D, A22
+    b1 = -m[0, 0] * m[0, 2] - m[0, 1] * m[1, 2]
+    b2 = -m[1, 0] * m[0, 2] - m[1, 1] * m[1, 2]
+    m[0, 2], m[1, 2] = b1, b2
+    xs, ys = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
+    adelta, bdelta = np.rint(m[0, 0] * xs * 1024).astype(np.int64), np.rint(m[1, 0] * xs * 1024).astype(np.int64)
+    X0 = np.rint((m[0, 1] * ys + m[0, 2]) * 1024).astype(np.int64) + 16
+    Y0 = np.rint((m[1, 1] * ys + m[1, 2]) * 1024).astype(np.int64) + 16
+    return X0, Y0, adelta, bdelta
 
 
 def flip(img, code):

@@ -351,7 +351,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_kernel(const float* __re
                                                 (long)9 * CIN * COUT, nullptr, nullptr, tid, lane, wm, wn);
 }
 
+// 32-bit element offsets.  The gathers of all three kernels hold their operand offsets in `int` (TileStage::load_gather);
+// every store goes through gemm_epilogue, whose rows are `int` and whose element offsets are `long`.  Each entry point
+// therefore rejects every geometry in which an operand offset it computes -- used or masked -- could pass 2^31 - 1; the
+// rule is stated above each of them.  An output may be larger than that (forward: y has up to twice the elements of x).
+
 // dy [B][H-2][W-2][cout], w HWIO [3][3][cin][cout], dx [B][H][W][cin].  Supported: (cin, cout) = (32, 64).
+// Offsets: the gather reads dy at ((b*OH + ih)*OW + iw)*64 for every INPUT pixel (b, ih, iw), in the image or masked; the
+// largest is below B*H*W*64.  Rejected unless B*H*W*64 < 2^31 (which also keeps the row count M = B*H*W an int).
 extern "C" int spnet_conv3x3_dgrad(const float* dy, const float* w, float* dx, int B, int H, int W, int cin,
                                    int cout, void* stream) {
   if (cin != 32 || cout != 64 || H < 3 || W < 3 || B < 1) return (int)hipErrorInvalidValue;
@@ -364,6 +371,9 @@ extern "C" int spnet_conv3x3_dgrad(const float* dy, const float* w, float* dx, i
 }
 
 // x [B][H][W][cin], w HWIO -> y [B][H-2][W-2][cout].  Supported: (cin, cout) = (32, 64).
+// Offsets: the gather reads x at ((b*H + oh)*W + ow)*32 plus a tap shift of at most (2*W + 2)*32, all inside x: below
+// B*H*W*32.  Rejected unless B*H*W*32 < 2^31.  y needs no rule of its own: M = B*OH*OW < 2^26 rows are an int and the
+// epilogue forms row*64 in 64 bits (M*64 may pass 2^31).
 extern "C" int spnet_conv3x3_fwd(const float* x, const float* w, float* y, int B, int H, int W, int cin,
                                  int cout, void* stream) {
   if (cin != 32 || cout != 64 || H < 3 || W < 3 || B < 1) return (int)hipErrorInvalidValue;
@@ -387,12 +397,19 @@ extern "C" long spnet_conv3x3_wgrad_ws(int B, int H, int W, int cin, int cout) {
 }
 
 // x [B][H][W][cin], dy [B][H-2][W-2][cout] -> dw HWIO [3][3][cin][cout].  Supported: (cin, cout) = (32, 64).
+// Offsets: both walkers step 32 pixels per tile and form their offsets for the two tiles prefetched behind a slice as
+// well, masked or not, so they reach up to 127 pixels past the last of the P = B*OH*OW output pixels.
+//   dy: pixel p is read at p*64.  Rejected unless (P + 128)*64 <= 2^31.
+//   x:  pixel p lies in image p / (OH*OW), whose offsets (window and tap included) are below (p / (OH*OW) + 1)*H*W*32;
+//       the walker reaches image B + 127 / (OH*OW) at most.  Rejected unless (B + 1 + 127 / (OH*OW))*H*W*32 <= 2^31.
 extern "C" int spnet_conv3x3_wgrad(const float* x, const float* dy, float* dw, int B, int H, int W, int cin,
                                    int cout, float* workspace, long ws_floats, void* stream) {
   if (cin != 32 || cout != 64 || H < 3 || W < 3 || B < 1) return (int)hipErrorInvalidValue;
   if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)workspace) & 15) return (int)hipErrorInvalidValue;
-  if ((long)B * H * W * 32 >= (1L << 31)) return (int)hipErrorInvalidValue;
   const long P = (long)B * (H - 2) * (W - 2);
+  const long past = 127 / ((long)(H - 2) * (W - 2));          // whole images the x walker can run past the last one
+  if (((long)B + 1 + past) * H * W * 32 > (1L << 31)) return (int)hipErrorInvalidValue;
+  if ((P + 128) * 64 > (1L << 31)) return (int)hipErrorInvalidValue;
   const long need = spnet_conv3x3_wgrad_ws(B, H, W, cin, cout);
   if (!workspace || ws_floats < need) return (int)hipErrorInvalidValue;
   int ns = (int)(need / (9 * cin * cout));

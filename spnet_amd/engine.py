@@ -858,7 +858,9 @@ class Engine:
             self.y_true = self.new(B, self.n_out)
             self.dout = self.new(B, self.n_out)
             self.loss_parts = self.new(B, 5)
-            self.loss_out = self.new(8)            # center,size,angle,noobj,class,total, l2, total+l2
+            # center,size,angle,noobj,class,total, l2, and one float no kernel writes: zeroed, so that the tensor train_step
+            # returns never carries whatever the allocation held before (a NaN there made two equal runs compare unequal)
+            self.loss_out = torch.zeros(8, device=self.dev, dtype=torch.float32)
             self.sq_scratch = self.new(2 * 2048)        # sum-of-squares partials of the optimizer's two ranges
             off, n, _ = self.p_off["FinalOutput/kernel"]
             self._head_hi = n if (off == 0 and n % 4 == 0) else 0

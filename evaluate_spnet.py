@@ -11,10 +11,35 @@ from spnet.utils import build_dataset, denorm_Y, make_sure_path_exists, show_pre
 import spnet.config as cf
 
 
+MASK_METRIC_LOG = "mask_metric.txt"
+
+
+def mask_metric_report(Yp, Yt, log_dir, chunk=256, tol=5):
+    """(additive, --mask_metric) The detector scored in pixels that carry a ring count: predicted and true grids are painted
+    as ring-count masks on the device (spnet_amd.masks, one row per predictor, at the frames' own size), chunk by chunk, and
+    compared pixel by pixel.  Prints the three ratios and the five counts and appends them to log_dir/mask_metric.txt."""
+    from spnet.utils import orig_img_dims
+    from spnet_amd import masks as MK
+    W, H = int(orig_img_dims[0]), int(orig_img_dims[1])
+    counts = np.zeros(5, np.int64)
+    for lo in range(0, Yp.shape[0], chunk):
+        pred = MK.masks_from_predictions(Yp[lo:lo + chunk], H, W)
+        true = MK.masks_from_predictions(Yt[lo:lo + chunk], H, W)
+        counts += MK.mask_counts_device(pred, true, tol).sum(0).cpu().numpy()
+    res = MK.metrics_from_counts(*counts.tolist())
+    lines = ["Mask metric (%d frames of %d x %d, ring tolerance %d/10):" % (Yp.shape[0], H, W, tol),
+             "    pixel_acc = %s   object_iou = %s   ring_acc = %s" % (res["pixel_acc"], res["object_iou"], res["ring_acc"]),
+             "    " + "   ".join("%s = %d" % (k, res[k]) for k in MK.COUNT_NAMES)]
+    print("\n".join(lines))
+    with open(log_dir + MASK_METRIC_LOG, "a") as f:
+        f.write("\n".join(lines) + "\n")
+    return res
+
+
 def evaluate_network(model=None, weights_file="", datapath="Test/", fraction=1.0, log_dir="", batch_size=32,
                      pred_grid=[6, 6, 2], set_means_ranges=True, device_png=False, device_decode=False,
                      device_overlay=False, device_png_lz=False, device_jpeg=False, jpeg_quality=90, movie=None,
-                     movie_fps=5.0):
+                     movie_fps=5.0, mask_metric=False):
     np.random.seed(1)
     print("Getting data..., fraction = ", fraction)
     X_test, Y_test, test_file_list, pred_shape = build_dataset(
@@ -55,6 +80,8 @@ def evaluate_network(model=None, weights_file="", datapath="Test/", fraction=1.0
           ' % class. accuracy rate (lack of mistakes)', sep="")
 
     make_sure_path_exists(log_dir)
+    if mask_metric:
+        mask_metric_report(Yp, Yt, log_dir)
     print("    Drawing sample ellipse images...")
     show_pred_ellipses(Yt, Yp, test_file_list, num_draw=m, log_dir=log_dir, out_csv=log_dir + 'hawley_spnet.csv',
                        png="device-jpeg" if device_jpeg else "device-lz" if device_png_lz else "device" if device_png
@@ -94,6 +121,10 @@ if __name__ == '__main__':
     p.add_argument('--movie', default=None, metavar='PATH',
                    help="(additive) also append every overlay, in order, to a Motion-JPEG AVI at PATH (encoded on the GPU)")
     p.add_argument('--movie_fps', type=float, default=5.0, help="frames per second of --movie")
+    p.add_argument('--mask_metric', action='store_true',
+                   help="(additive) also score the predictions as ring-count segmentation masks, pixel by pixel on the GPU: "
+                        "pixel_acc, object_iou, ring_acc and the five pixel counts, printed and appended to "
+                        "<logdir>/" + MASK_METRIC_LOG)
     args = p.parse_args()
     if args.device_jpeg and (args.device_png or args.device_png_lz):
         p.error("--device_jpeg writes .jpg files: not with --device_png / --device_png_lz")
@@ -106,7 +137,7 @@ if __name__ == '__main__':
                              log_dir=args.logdir, batch_size=args.batch_size, device_png=args.device_png,
                              device_decode=args.device_decode, device_overlay=args.device_overlay,
                              device_png_lz=args.device_png_lz, device_jpeg=args.device_jpeg, jpeg_quality=args.jpeg_quality,
-                             movie=args.movie, movie_fps=args.movie_fps)
+                             movie=args.movie, movie_fps=args.movie_fps, mask_metric=args.mask_metric)
     weights2name = "eval_end_weights.hdf5"
     print("Saving model to", weights2name)
     model.save_weights(weights2name)

@@ -12,7 +12,12 @@ Additive flags: --seed; --count_range LO HI (antinodes per frame; 0 6 is the pub
 --bp_real DIR --bp_path DIR (also the band-pass mixed copies, steelpan_NNNNNNN_bp.png + .csv, as a data set of their own
 under bp_path, as fake_espi.write_dataset writes them); --host_params (the parameters of the reference-ordered host stream,
 fake_espi.draw_params, instead of the device sampler's own stream: the same distributions, other frames); --device_png (the
-PNGs are encoded from HBM by spnet_amd.png instead of copied out for Pillow: the same pixels, other file bytes).
+PNGs are encoded from HBM by spnet_amd.png instead of copied out for Pillow: the same pixels, other file bytes); --masks
+(beside every X/steelpan_NNNNNNN.png a ring-count segmentation mask X/masks/steelpan_NNNNNNN.png, spnet_amd.masks: painted on
+the device from the parameter arrays the frames were rasterised from, or from the label rows with --host_params; the
+loaders glob X/*.png only and do not see the sub-directory).  Without a GPU the script stops, as before; only --masks
+then still runs, on the host generator's frames (fake_espi.generate, the reference-ordered stream) and the host mask rule,
+and says so.
 
 The PNGs are encoded (by default) and written by at most 16 threads of this process; nothing is forked once the GPU is
 initialised."""
@@ -44,22 +49,28 @@ def split_dirs(n, everything):
 
 
 def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_range=(1, 7), bp_real=None, bp_path=None,
-                host_params=False, chunk=256, device="cuda:0", threads=None, device_png=False, device_png_lz=False):
+                host_params=False, chunk=256, device="cuda:0", threads=None, device_png=False, device_png_lz=False,
+                masks=False):
     """Writes the data set; returns the label rows of every frame, in frame order.  device_png: the frames are encoded where
     they are (spnet_amd.png.write_png_device) and only the compressed bytes cross to the host.  device_png_lz: the same (it
-    implies device_png), with the encoder's LZ77 stage on."""
+    implies device_png), with the encoder's LZ77 stage on.  masks: also X/masks/steelpan_NNNNNNN.png, the frame's ring-count
+    mask (spnet_amd.masks), written by the same writer as the frames."""
     import torch
     from spnet_amd import fake_espi as F
     if (bp_real is None) != (bp_path is None):
         raise ValueError("gen_fake_espi: --bp_real and --bp_path go together")
-    if not torch.cuda.is_available():
-        raise RuntimeError("gen_fake_espi: the frames are generated on the GPU (no CPU fallback)")
     device_png = device_png or device_png_lz
     n = int(numframes)
     sub = split_dirs(n, everything)
+    if not torch.cuda.is_available():
+        if not masks:
+            raise RuntimeError("gen_fake_espi: the frames are generated on the GPU (no CPU fallback)")
+        return _gen_dataset_host(datapath, n, sub, seed, tuple(count_range), bp_real, device_png)
     for root in (datapath,) + ((bp_path,) if bp_path else ()):
         for d in sorted(set(sub)):
             os.makedirs(os.path.join(root, d), exist_ok=True)
+            if masks and root == datapath:
+                os.makedirs(os.path.join(root, d, "masks"), exist_ok=True)
     threads = threads or min(16, os.cpu_count() or 1)
     mixer = None
     if bp_real is not None:
@@ -79,15 +90,39 @@ def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_ran
         frames = frames_dev.cpu().numpy()
         return [pool.submit(_write_pair, st, frames[k], rows[k]) for k, st in enumerate(stems)]
 
+    def submit_masks(pool, mask_dev, lo, hi):
+        from spnet_amd.masks import write_masks
+        paths = [os.path.join(datapath, sub[i], "masks", "steelpan_" + str(i).zfill(7) + ".png") for i in range(lo, hi)]
+        if device_png:
+            write_masks(mask_dev, paths, png="device-lz" if device_png_lz else "device", pool=pool)
+            return []
+        host = mask_dev.cpu().numpy()
+        return [pool.submit(write_masks, host[k:k + 1], [p]) for k, p in enumerate(paths)]
+
     with ThreadPoolExecutor(max_workers=threads) as pool:
         for lo in range(0, n, chunk):
             hi = min(n, lo + chunk)
+            mask_dev = None
             if host_params:
                 U, rows = U_host[lo:hi], labels_host[lo:hi]
+                if masks:
+                    from spnet_amd.masks import ring_masks_device
+                    mask_dev = ring_masks_device(rows, H=F.IM_H, W=F.IM_W, device=device)
+            elif masks:     # the label rows stay in HBM for the rasteriser; the CSV rows are read back from them
+                from spnet_amd.masks import ring_masks_device
+                _, (rows_d, count_d), U = F.generate_device(hi - lo, seed, device, want_u8=True, chunk=chunk,
+                                                            count_range=count_range, params="device", first_frame=lo,
+                                                            labels="device")
+                mask_dev = ring_masks_device(rows_d, count_d, H=F.IM_H, W=F.IM_W)
+                packed = torch.cat([rows_d.reshape(hi - lo, -1), count_d.double()[:, None]], 1).cpu().numpy()
+                rows = [[tuple(r) for r in fr.reshape(-1, 6)[:int(k)].astype(np.int64).tolist()]
+                        for fr, k in zip(packed[:, :-1], packed[:, -1])]
             else:
                 _, rows, U = F.generate_device(hi - lo, seed, device, want_u8=True, chunk=chunk, count_range=count_range,
                                                params="device", first_frame=lo)
             jobs = submit(pool, datapath, "", U, rows, lo, hi)
+            if mask_dev is not None:
+                jobs += submit_masks(pool, mask_dev, lo, hi)
             if mixer is not None:
                 bp = mixer.draw(hi - lo, seeds=F.bandpass_seeds(hi - lo, seed, lo))
                 mixed = U.clone()
@@ -100,7 +135,25 @@ def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_ran
     return labels
 
 
-if __name__ == "__main__":
+def _gen_dataset_host(datapath, n, sub, seed, count_range, bp_real, device_png):
+    """gen_dataset(masks=True) on a machine without a GPU: the host generator's frames (fake_espi.generate: the
+    reference-ordered parameter stream, Pillow's rasteriser -- other pixels than the device's) and the host mask rule."""
+    from spnet_amd import fake_espi as F
+    from spnet_amd.masks import ring_masks_host, write_masks
+    if bp_real is not None or device_png or count_range != (1, 7):
+        raise RuntimeError("gen_fake_espi: no GPU -- the band-pass copies, the device PNG encoder and --count_range need one")
+    print("gen_fake_espi: no GPU -- frames from the host generator (fake_espi.generate), masks by the host rule", flush=True)
+    X, labels = F.generate(n, seed)
+    for i in range(n):
+        d = os.path.join(datapath, sub[i])
+        os.makedirs(os.path.join(d, "masks"), exist_ok=True)
+        name = "steelpan_" + str(i).zfill(7)
+        _write_pair(os.path.join(d, name), X[i], labels[i])
+        write_masks(ring_masks_host([labels[i]], H=F.IM_H, W=F.IM_W), [os.path.join(d, "masks", name + ".png")])
+    return labels
+
+
+def main(argv=None):
     p = argparse.ArgumentParser(description="generates fake-ESPI frames and their annotations",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('-d', '--datapath', default=".", help='Directory to write images to (in Train/ and maybe Val/ subdirs)')
@@ -117,7 +170,14 @@ if __name__ == "__main__":
                    help="(additive) encode the PNG files on the GPU (Huffman-only deflate): the same pixels, other file bytes")
     p.add_argument('--device_png_lz', action='store_true',
                    help="(additive) --device_png with the encoder's LZ77 stage: smaller files where pixels repeat")
-    args = p.parse_args()
+    p.add_argument('--masks', action='store_true',
+                   help="(additive) also write X/masks/steelpan_NNNNNNN.png, the frame's ring-count segmentation mask: "
+                        "trunc(10 * rings) inside every ellipse, 0 outside")
+    args = p.parse_args(argv)
     gen_dataset(datapath=args.datapath, numframes=args.numframes, everything=args.all, seed=args.seed,
                 count_range=tuple(args.count_range), bp_real=args.bp_real, bp_path=args.bp_path, host_params=args.host_params,
-                device_png=args.device_png, device_png_lz=args.device_png_lz)
+                device_png=args.device_png, device_png_lz=args.device_png_lz, masks=args.masks)
+
+
+if __name__ == "__main__":
+    main()

@@ -903,6 +903,38 @@ int spnet_jpeg_entropy_sync(const unsigned char* blob, long blob_bytes, const in
                             const int* files, int n_files, const uint32_t* tables, int n_sets, int seg_bytes, int16_t* coef,
                             long total_blocks, int* status, void* stream);
 
+/* ---- Ring-count masks (csrc/masks.hip): segmentation masks painted from label rows, and their pixel-level comparison.
+ *      spnet_amd/masks.py is the host side and holds the same rule in numpy; DESIGN.md 5g ------------------------------- */
+/* THE RULE.  A frame's mask is uint8 [H][W], background 0, painted from its first count[b] rows (count clamped to 0 .. K)
+ * of rows double [B][K][6] = (cx, cy, a, b, angle_deg, rings): augmentation.pad_metadata's layout, the one
+ * spnet_encode_targets reads.  Rows are painted in order and a later row overwrites an earlier one: the LAST row that
+ * contains a pixel gives its value.  Per row, whole numbers:
+ *   cxq, cyq, aq, bq = rint(16 v)                          (1/16 pixel, ties to even)
+ *   c = rint(2^14 cos(t)), s = rint(2^14 sin(t))           t = (-angle_deg) * (pi / 180) as ONE fp64 product with the
+ *                                                          fp64 constant pi / 180; cos / sin in fp64.  The minus sign is
+ *                                                          the image-y-down convention of metrics.hip / espi.hip
+ *   value = min(255, max(0, trunc(10 * rings)))            the product in fp64
+ * Pixel (x, y) has its centre at (16 x + 8, 16 y + 8), the overlay kernel's convention.  With dx = 16 x + 8 - cxq,
+ * dy = 16 y + 8 - cyq, u = dx c + dy s, v = -dx s + dy c, the pixel is inside iff
+ *   (u bq)^2 + (v aq)^2 <= (aq bq 2^14)^2
+ * evaluated exactly (the products fit 64 bits, the squares and their sum 128): no floating point takes part after the
+ * quantisation.  A row paints NOTHING if any of its six values is not finite, if aq <= 0 or bq <= 0, or if |cx|, |cy|, a
+ * or b is 32,768 or more.  A row whose value is 0 paints zeros: over an earlier row it erases, and alone it cannot be told
+ * from background.
+ * spnet_ring_masks  H, W 1 .. 16,384, K 1 .. 128; B == 0: nothing to do, success.  Writes every byte of out uint8
+ *                   [B][H][W] (16 bytes a store where W % 16 == 0 and out is 16-byte aligned; no alignment is required).
+ *                   No value in rows or count causes an access outside the three arrays.
+ * spnet_mask_compare  pred, truth uint8 [N][n_pixels] (n_pixels 1 .. 2^31 - 1; 16-byte loads for a frame whose two
+ *                   addresses are 16-byte aligned, none required), tol 0 .. 255.  counts int32 [N][5] is WRITTEN, not
+ *                   accumulated into: bg_bg (both 0), hit (both above 0 and |p - t| <= tol), miss (both above 0 and
+ *                   further apart), pred_only (only pred above 0), true_only.  Integer sums: the result does not depend on
+ *                   the grid.  N == 0: success.
+ * Both return hipErrorInvalidValue and launch nothing for a NULL pointer, a size or tol outside these limits, rows not
+ * 8-byte aligned, count / counts not 4-byte aligned. */
+int spnet_ring_masks(const double* rows, const int* count, int B, int K, int H, int W, unsigned char* out, void* stream);
+int spnet_mask_compare(const unsigned char* pred, const unsigned char* truth, int N, long n_pixels, int tol, int* counts,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,7 @@ class _DevicePlanes:
 def _planes_or_promise(filename):
     """_read_planes, or for a file the device decodes to the same planes (8 bits, L / RGB / RGBA) a _DevicePlanes."""
     from spnet_amd import png as P
-    info = P._read_and_parse(filename)
+    info = P.parse_png_file(filename)
     if info.device and info.channels in (1, 3, 4):
         return _DevicePlanes(filename, info)
     return _read_planes(filename)

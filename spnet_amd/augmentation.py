@@ -1070,13 +1070,12 @@ def read_real_frames(path, H, W, device_decode=False, device=None, return_info=F
     if not files:
         raise FileNotFoundError("bandpass_mixup: no real *.png images in %r" % path)
     if device_decode:
-        from concurrent.futures import ThreadPoolExecutor
         from . import png as P
+        from .codec_host import map_pool
         if not torch.cuda.is_available():
             raise RuntimeError("bandpass_mixup: device_decode decodes on the GPU (there is no CPU decoder here)")
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        with ThreadPoolExecutor(max_workers=P._pool_size(P.MAX_THREADS, len(files))) as tp:
-            infos = list(tp.map(P._read_and_parse, files))
+        infos = map_pool(P.parse_png_file, files)
         out = torch.empty((len(files), H, W), dtype=torch.uint8, device=device)
         grey = [k for k, i in enumerate(infos) if i.device and i.colour_type == 0]
         host = [k for k in range(len(files)) if k not in set(grey)]
@@ -1085,7 +1084,7 @@ def read_real_frames(path, H, W, device_decode=False, device=None, return_info=F
                 raise ValueError("bandpass_mixup: real image %s is %dx%d, the frames are %dx%d"
                                  % (files[k], infos[k].height, infos[k].width, H, W))
         if grey:
-            got, _, fell = P._decode_parsed([infos[k] for k in grey], [files[k] for k in grey], device, "first", True)
+            got, _, fell = P.decode_parsed_png([infos[k] for k in grey], [files[k] for k in grey], device, "first", True)
             out[torch.as_tensor(grey, device=device)] = got
             host = sorted(host + [grey[j] for j in fell])
         for k in (k for k in host if k not in grey):

@@ -21,20 +21,20 @@ MjpegWriter streams such files into a plain RIFF AVI (hdrl / movi of 00dc chunks
 
 Reading (csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h; additive and opt-in: --device_decode, --movie_in): parse_jpeg walks
 the markers and finds the restart intervals, plan_decode builds what the kernels read, decode_jpeg_device /
-read_jpeg_device have the contract of their PNG namesakes (one size per call, host fallback through png._host_frame, one
-pinned upload, one status download), read_frames_device routes a list of PNG and JPEG files by signature, MjpegReader
-walks a RIFF AVI.  Baseline JPEG, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0; the pixels are Pillow's, sample for sample (DESIGN.md
+read_jpeg_device have the contract of their PNG namesakes (codec_host.decode_batch: one size per call, host fallback through
+codec_host.host_frame, one pinned upload, one status download), read_frames_device routes a list of PNG and JPEG files by
+signature, MjpegReader walks a RIFF AVI.  Baseline JPEG, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0; the pixels are Pillow's, sample for sample (DESIGN.md
 section 5f).  Two entropy kernels share one workspace: a lane per restart interval (spnet_jpeg_entropy) and, for the long
 intervals of files without restart markers, a workgroup per interval that decodes segments speculatively and chains them
 until the result is the serial one (spnet_jpeg_entropy_sync, csrc/jpeg_sync_core.h); entropy= picks, see ENTROPY_MODES.
 """
 import struct
-from concurrent.futures import ThreadPoolExecutor
 from fractions import Fraction
 
 import numpy as np
 
-MAX_THREADS = 16
+from .codec_host import MAX_THREADS, decode_batch, map_pool, read_file, stage, write_files
+
 MAX_DIM = 65535                 # SOF0 holds 16-bit sizes
 MAX_INTERVAL = 64               # MCUs of a restart interval: one lane of a wave each
 
@@ -223,10 +223,6 @@ def scans_device(frames, quality=90):
     return [out[int(off[n]):int(off[n + 1])] for n in range(N)]
 
 
-def _pool_size(threads, jobs):
-    return max(1, min(MAX_THREADS, int(threads), jobs))
-
-
 def encode_jpeg_device(frames, quality=90):
     """JPEG files of uint8 device frames [N,H,W] (grey) or [N,H,W,C] (C = 3: RGB), as a list of bytes."""
     _need_gpu("encode_jpeg_device")
@@ -243,25 +239,13 @@ def write_jpeg_device(frames, paths, quality=90, threads=MAX_THREADS, pool=None)
     pool: a caller's ThreadPoolExecutor to use instead.  Returns the size of every file."""
     _need_gpu("write_jpeg_device")
     N, H, W, channels = _frames_shape(frames)
-    paths = list(paths)
-    if len(paths) != N:
-        raise ValueError("jpeg: %d frames, %d paths" % (N, len(paths)))
-    scans = scans_device(frames, quality)
-    if not scans:
-        return []
-    header = jpeg_header(W, H, channels, quality)
 
-    def job(k):
-        with open(paths[k], "wb") as f:
-            f.write(header)
-            f.write(scans[k])
-            f.write(JPEG_TRAILER)
-        return len(header) + len(scans[k]) + len(JPEG_TRAILER)
+    def encode():
+        scans = scans_device(frames, quality)
+        header = jpeg_header(W, H, channels, quality)
+        return lambda k: (header, scans[k], JPEG_TRAILER)
 
-    if pool is not None:
-        return list(pool.map(job, range(N)))
-    with ThreadPoolExecutor(max_workers=_pool_size(threads, N)) as own:
-        return list(own.map(job, range(N)))
+    return write_files(paths, N, encode, threads, pool, "jpeg")
 
 
 # ----------------------------------------------------------------------------- Motion-JPEG in a RIFF AVI
@@ -718,91 +702,44 @@ def _entropy_split(entropy, seg_bytes):
 
 
 # ----------------------------------------------------------------------------- reading: device
-def _decode_parsed(infos, sources, device, channels, return_info, entropy=None, seg_bytes=None):
-    import os
-    if channels not in ("first", "all"):
-        raise ValueError('jpeg: channels is "first" or "all", got %r' % (channels,))
-    sync_min, seg_bytes = _entropy_split(entropy, seg_bytes)
-    import torch
-    from . import _lib as L
-    from .png import _host_frame
-    if not torch.cuda.is_available():
-        raise RuntimeError("jpeg: decode_jpeg_device decodes on the GPU (there is no CPU decoder here)")
-    device = torch.device("cuda" if device is None else device)
-    N = len(infos)
-    status = np.zeros(N, np.int32)
-    host = [k for k in range(N) if not infos[k].device]
-    host_frames = {k: _host_frame(sources[k], channels) for k in host}          # raises what the default path raises
+def _decode_parsed(infos, sources, device, channels, return_info, split):
+    """split: _entropy_split's pair, which the entry points work out before they read a file."""
+    sync_min, seg_bytes = split
 
-    def shape_of(k):
-        if k in host_frames:
-            return host_frames[k].shape
-        return (infos[k].height, infos[k].width) + ((infos[k].components,) if channels == "all" else ())
-
-    if N == 0:
-        out = torch.empty((0, 0, 0) if channels == "first" else (0, 0, 0, 0), dtype=torch.uint8, device=device)
-        return (out, status, DecodeInfo()) if return_info else out
-    shape = shape_of(0)
-    for k in range(1, N):
-        if shape_of(k) != shape:
-            name = sources[k] if isinstance(sources[k], (str, os.PathLike)) else "file %d" % k
-            raise ValueError("jpeg: %s is %s, the files before it are %s (one call decodes files of one size)"
-                             % (name, "x".join(str(v) for v in shape_of(k)), "x".join(str(v) for v in shape)))
-    out = torch.empty((N,) + tuple(shape), dtype=torch.uint8, device=device)
-    H, W = int(shape[0]), int(shape[1])
-    idx = [k for k in range(N) if infos[k].device]
-    plan = plan_decode([infos[k] for k in idx], sync_min) if idx else None
-    counts = [0, 0]
-    if plan is not None and (plan["blob"].size > MAX_BLOB or plan["blocks"] * 64 > (1 << 31) - 1):
-        raise ValueError("jpeg: %d files of %d x %d are more than one call decodes; pass fewer" % (len(idx), W, H))
-    if plan is not None:
+    def launch(idx, shape, out, device):
+        import torch
+        from . import _lib as L
+        if not idx:
+            return [], (0, 0)
+        H, W = shape[:2]
+        plan = plan_decode([infos[k] for k in idx], sync_min)
+        if plan["blob"].size > MAX_BLOB or plan["blocks"] * 64 > (1 << 31) - 1:
+            raise ValueError("jpeg: %d files of %d x %d are more than one call decodes; pass fewer" % (len(idx), W, H))
         n = len(idx)
-        C = int(shape[2]) if channels == "all" else 1
-        # one pinned upload: the tables first (every piece padded to 16 bytes), the bytes last
+        C = shape[2] if channels == "all" else 1
         sync_iv = plan.get("sync_intervals", np.zeros((0, 8), np.int32))
-        counts = [int((plan["intervals"][:, 4] > 0).sum()), int(sync_iv.shape[0])]
-        parts = [plan["intervals"].view(np.uint8).ravel(), plan["files"].view(np.uint8).ravel(),
-                 plan["tables"].view(np.uint8).ravel(), plan["quant"].view(np.uint8).ravel(), plan["blob"],
-                 sync_iv.view(np.uint8).ravel()]
-        starts, total = [], 0
-        for p in parts:
-            starts.append(total)
-            total += (p.size + 15) // 16 * 16
-        staging = torch.empty((max(total, 16),), dtype=torch.uint8).pin_memory()
-        buf = staging.numpy()
-        for s, p in zip(starts, parts):
-            buf[s:s + p.size] = p
-        dev = staging.to(device, non_blocking=True)
-        base = dev.data_ptr()
-        whole = n == N
-        got = out if whole else torch.empty((n,) + tuple(shape), dtype=torch.uint8, device=device)
+        # one pinned upload, every piece padded to 16 bytes
+        dev, starts, staging = stage([plan["intervals"], plan["files"], plan["tables"], plan["quant"], plan["blob"], sync_iv],
+                                     device, pinned=True, align=16)
+        p_iv, p_files, p_tables, p_quant, p_blob, p_sync = (dev.data_ptr() + s for s in starts)
+        got = out if n == len(out) else torch.empty((n,) + shape, dtype=torch.uint8, device=device)
         coef = torch.zeros((max(plan["blocks"], 1), 64), dtype=torch.int16, device=device)
         st = torch.empty((n,), dtype=torch.int32, device=device)
         with torch.cuda.device(device):
-            L.spnet_jpeg_entropy(base + starts[4], int(plan["blob"].size), base + starts[0], int(plan["intervals"].shape[0]),
-                                 base + starts[1], n, base + starts[2], int(plan["tables"].shape[0]), coef.data_ptr(),
-                                 int(plan["blocks"]), st.data_ptr(), L.current_stream())
+            L.spnet_jpeg_entropy(p_blob, int(plan["blob"].size), p_iv, int(plan["intervals"].shape[0]), p_files, n, p_tables,
+                                 int(plan["tables"].shape[0]), coef.data_ptr(), int(plan["blocks"]), st.data_ptr(),
+                                 L.current_stream())
             if sync_iv.shape[0]:                 # behind the lane kernel, which has cleared the status
-                L.spnet_jpeg_entropy_sync(base + starts[4], int(plan["blob"].size), base + starts[5], int(sync_iv.shape[0]),
-                                          base + starts[1], n, base + starts[2], int(plan["tables"].shape[0]), seg_bytes,
-                                          coef.data_ptr(), int(plan["blocks"]), st.data_ptr(), L.current_stream())
-            L.spnet_jpeg_pixels(coef.data_ptr(), int(plan["blocks"]), base + starts[1], n, base + starts[3],
-                                int(plan["quant"].shape[0]), H, W, C, got.data_ptr() if channels == "first" else 0,
-                                got.data_ptr() if channels == "all" else 0, st.data_ptr(), L.current_stream())
-        status[idx] = st.cpu().numpy()           # the D2H copy of the status: the only synchronisation
-        del staging
-        if not whole:
-            out[torch.as_tensor(idx, device=device)] = got
-    failed = [k for k in range(N) if status[k] != 0]
-    for k in failed:
-        host_frames[k] = _host_frame(sources[k], channels)      # a corrupt file raises here what it raises today
-        if host_frames[k].shape != tuple(shape):
-            raise ValueError("jpeg: file %d decodes to %s on the host, %s was expected" % (k, host_frames[k].shape, shape))
-    fallback = sorted(host_frames)
-    if fallback:
-        up = torch.from_numpy(np.stack([host_frames[k] for k in fallback])).to(device)
-        out[torch.as_tensor(fallback, device=device)] = up
-    return (out, status, DecodeInfo(fallback, *counts)) if return_info else out
+                L.spnet_jpeg_entropy_sync(p_blob, int(plan["blob"].size), p_sync, int(sync_iv.shape[0]), p_files, n, p_tables,
+                                          int(plan["tables"].shape[0]), seg_bytes, coef.data_ptr(), int(plan["blocks"]),
+                                          st.data_ptr(), L.current_stream())
+            L.spnet_jpeg_pixels(coef.data_ptr(), int(plan["blocks"]), p_files, n, p_quant, int(plan["quant"].shape[0]), H, W,
+                                C, got.data_ptr() if channels == "first" else 0, got.data_ptr() if channels == "all" else 0,
+                                st.data_ptr(), L.current_stream())
+        return [(idx, st, got, (staging, coef))], (int((plan["intervals"][:, 4] > 0).sum()), int(sync_iv.shape[0]))
+
+    return decode_batch(infos, sources, device, channels, return_info, "jpeg", lambda info: info.components, launch,
+                        DecodeInfo)
 
 
 def decode_jpeg_device(datas, device=None, channels="first", return_info=False, threads=MAX_THREADS, entropy=None,
@@ -818,17 +755,8 @@ def decode_jpeg_device(datas, device=None, channels="first", return_info=False, 
     ENTROPY_MODES (None: DEFAULT_ENTROPY); seg_bytes: the sync kernel's segment (None: SYNC_SEG_BYTES).  Neither changes
     a pixel."""
     datas = list(datas)
-    _entropy_split(entropy, seg_bytes)
-    if not datas:
-        return _decode_parsed([], [], device, channels, return_info, entropy, seg_bytes)
-    with ThreadPoolExecutor(max_workers=_pool_size(threads, len(datas))) as pool:
-        infos = list(pool.map(parse_jpeg, datas))
-    return _decode_parsed(infos, datas, device, channels, return_info, entropy, seg_bytes)
-
-
-def _read_file(path):
-    with open(path, "rb") as f:
-        return f.read()
+    split = _entropy_split(entropy, seg_bytes)
+    return _decode_parsed(map_pool(parse_jpeg, datas, threads), datas, device, channels, return_info, split)
 
 
 def read_jpeg_device(paths, threads=MAX_THREADS, device=None, channels="first", return_info=False, entropy=None,
@@ -836,12 +764,9 @@ def read_jpeg_device(paths, threads=MAX_THREADS, device=None, channels="first", 
     """decode_jpeg_device of files on disk, read and parsed by a thread pool of this process (at most 16 threads; nothing
     is forked)."""
     paths = list(paths)
-    _entropy_split(entropy, seg_bytes)
-    if not paths:
-        return _decode_parsed([], [], device, channels, return_info, entropy, seg_bytes)
-    with ThreadPoolExecutor(max_workers=_pool_size(threads, len(paths))) as pool:
-        infos = list(pool.map(lambda p: parse_jpeg(_read_file(p)), paths))
-    return _decode_parsed(infos, paths, device, channels, return_info, entropy, seg_bytes)
+    split = _entropy_split(entropy, seg_bytes)
+    infos = map_pool(lambda p: parse_jpeg(read_file(p)), paths, threads)
+    return _decode_parsed(infos, paths, device, channels, return_info, split)
 
 
 def _is_jpeg(path):

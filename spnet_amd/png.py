@@ -32,12 +32,12 @@ stream; 8-bit non-interlaced colour types 0 / 2 / 4 / 6) and leave every other f
 the default path's Pillow call.
 """
 import heapq
-import os
 import struct
 import zlib
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
+
+from .codec_host import MAX_THREADS, decode_batch, map_pool, read_file, stage, write_files
 
 NSYM = 257                      # 256 literals + end of block
 EOB = 256
@@ -47,7 +47,6 @@ NDIST = 30                      # distance alphabet
 LZ_HEADER_WORDS = 72            # spnet_png_lz_pack's header stride: 2304 bits >= 3 + 14 + 19 * 3 + 316 * 7
 LENGTH_EXTRA = (0,) * 8 + (1,) * 4 + (2,) * 4 + (3,) * 4 + (4,) * 4 + (5,) * 4 + (0,)        # symbols 257 .. 285
 DIST_EXTRA = tuple(max(0, k // 2 - 1) for k in range(NDIST))
-MAX_THREADS = 16
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 COLOUR_TYPE = {1: 0, 2: 4, 3: 2, 4: 6}       # channels -> PNG colour type, 8 bits per sample
 _CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
@@ -359,13 +358,10 @@ def frame_statistics(frames):
 
 
 def _upload(arrays, device):
-    """The arrays as ONE host-to-device copy, in their order (64-bit arrays first keep every one aligned): (the device
-    tensor that owns the bytes, the device pointer of every array)."""
-    import torch
-    parts = [np.ascontiguousarray(v).reshape(-1).view(np.uint8) for v in arrays]
-    dev = torch.from_numpy(np.concatenate(parts)).to(device)
-    at = np.cumsum([0] + [v.nbytes for v in parts[:-1]]) + dev.data_ptr()
-    return dev, [int(v) for v in at]
+    """The arrays as ONE host-to-device copy (pageable, blocking), every one 16-byte aligned: (the device tensor that owns
+    the bytes, the device pointer of every array)."""
+    dev, starts, _ = stage(arrays, device, pinned=False, align=16)
+    return dev, [dev.data_ptr() + s for s in starts]
 
 
 def pack_frames(frames, plan, adler, out=None, base=0):
@@ -454,46 +450,24 @@ def zlib_streams_device(frames, lz77=False):
     return [out[int(off[n]):int(off[n + 1])] for n in range(N)]
 
 
-def _pool_size(threads, jobs):
-    return max(1, min(MAX_THREADS, int(threads), jobs))
-
-
 def encode_png_device(frames, threads=MAX_THREADS, lz77=False):
     """PNG files of uint8 device frames [N,H,W] (grey) or [N,H,W,C] (C = 3: RGB), as a list of bytes.  lz77: see
     zlib_streams_device."""
     N, H, W, channels = _frames_shape(frames)
     streams = zlib_streams_device(frames, lz77=lz77)
-    if not streams:
-        return []
-    with ThreadPoolExecutor(max_workers=_pool_size(threads, N)) as pool:       # zlib.crc32 runs without the interpreter lock
-        return list(pool.map(lambda z: png_container(z, W, H, channels), streams))
-
-
-def _write_pieces(path, pieces):
-    with open(path, "wb") as f:
-        for piece in pieces:
-            f.write(piece)
-    return sum(len(piece) for piece in pieces)
+    return map_pool(lambda z: png_container(z, W, H, channels), streams, threads)      # zlib.crc32 runs without the lock
 
 
 def write_png_device(frames, paths, threads=MAX_THREADS, pool=None, lz77=False):
     """encode_png_device, written to `paths` by a thread pool of this process (at most 16 threads; nothing is forked).  pool:
     a caller's ThreadPoolExecutor to use instead.  Returns the size of every file."""
     N, H, W, channels = _frames_shape(frames)
-    paths = list(paths)
-    if len(paths) != N:
-        raise ValueError("png: %d frames, %d paths" % (N, len(paths)))
-    streams = zlib_streams_device(frames, lz77=lz77)
-    if not streams:
-        return []
 
-    def job(k):
-        return _write_pieces(paths[k], png_pieces(streams[k], W, H, channels))
+    def encode():
+        streams = zlib_streams_device(frames, lz77=lz77)
+        return lambda k: png_pieces(streams[k], W, H, channels)
 
-    if pool is not None:
-        return list(pool.map(job, range(N)))
-    with ThreadPoolExecutor(max_workers=_pool_size(threads, N)) as own:
-        return list(own.map(job, range(N)))
+    return write_files(paths, N, encode, threads, pool, "png")
 
 
 # ----------------------------------------------------------------------------- reading: container
@@ -597,20 +571,6 @@ def parse_png(data):
 
 
 # ----------------------------------------------------------------------------- reading: device
-def _host_frame(source, channels):
-    """The default path's decode of one file (spnet_amd.utils._load_one's Pillow call decides what a damaged file is):
-    channel 0 of convert("RGB") as [H,W], or every channel as the file holds them, [H,W,C]."""
-    import io
-    from PIL import Image
-    f = source if isinstance(source, (str, os.PathLike)) else io.BytesIO(source)
-    if channels == "first":
-        return np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8)[:, :, 0]
-    arr = np.asarray(Image.open(f))
-    if arr.dtype != np.uint8:
-        raise ValueError('png: channels="all" holds 8-bit samples, this file decodes to %s' % arr.dtype)
-    return arr.reshape(arr.shape[0], arr.shape[1], -1)
-
-
 def inflate_unfilter_device(blob, offsets, N, H, W, channels, first=None, full=None):
     """The two launches on uploaded streams: blob (uint8 device tensor), offsets (int64 device tensor [N + 1], positions in
     blob).  first [N,H,W] / full [N,H,W,channels]: uint8 device tensors to fill (either may be None).  Returns status, an
@@ -628,76 +588,32 @@ def inflate_unfilter_device(blob, offsets, N, H, W, channels, first=None, full=N
     return status
 
 
-def _decode_parsed(infos, sources, device, channels, return_info):
+def decode_parsed_png(infos, sources, device=None, channels="first", return_info=False):
+    """decode_png_device of files that are already parsed: infos[k] = parse_png of the file sources[k] (bytes, or a path
+    for the host decoder to open)."""
     import torch
-    if channels not in ("first", "all"):
-        raise ValueError('png: channels is "first" or "all", got %r' % (channels,))
-    if not torch.cuda.is_available():
-        raise RuntimeError("png: decode_png_device decodes on the GPU (there is no CPU decoder here)")
-    device = torch.device("cuda" if device is None else device)
-    N = len(infos)
-    status = np.zeros(N, np.int32)
-    host = [k for k in range(N) if not infos[k].device]
-    host_frames = {k: _host_frame(sources[k], channels) for k in host}          # raises what the default path raises
 
-    def shape_of(k):
-        if k in host_frames:
-            return host_frames[k].shape
-        return (infos[k].height, infos[k].width) + ((infos[k].channels,) if channels == "all" else ())
-
-    if N == 0:
-        out = torch.empty((0, 0, 0) if channels == "first" else (0, 0, 0, 0), dtype=torch.uint8, device=device)
-        return (out, status, []) if return_info else out
-    shape = shape_of(0)
-    for k in range(1, N):
-        if shape_of(k) != shape:
-            name = sources[k] if isinstance(sources[k], (str, os.PathLike)) else "file %d" % k
-            raise ValueError("png: %s is %s, the files before it are %s (one call decodes files of one size)"
-                             % (name, "x".join(str(v) for v in shape_of(k)), "x".join(str(v) for v in shape)))
-    out = torch.empty((N,) + tuple(shape), dtype=torch.uint8, device=device)
-    H, W = int(shape[0]), int(shape[1])
-    groups = {}                                  # bytes per pixel -> files: one pair of launches each
-    for k in range(N):
-        if infos[k].device:
+    def launch(idx, shape, out, device):
+        H, W = shape[:2]
+        groups = {}                                  # bytes per pixel -> files: one pair of launches each
+        for k in idx:
             groups.setdefault(infos[k].channels, []).append(k)
-    pending = []
-    for bpp, idx in groups.items():
-        n = len(idx)
-        sizes = np.array([len(infos[k].zstream) for k in idx], np.int64)
-        # one pinned upload: the offsets (64-bit, relative to the start of the streams) first, then the streams
-        head = 8 * (n + 1)
-        staging = torch.empty((head + int(sizes.sum()),), dtype=torch.uint8).pin_memory()
-        buf = staging.numpy()
-        offsets = np.zeros(n + 1, np.int64)
-        np.cumsum(sizes, out=offsets[1:])
-        buf[:head] = offsets.view(np.uint8)
-        for j, k in enumerate(idx):
-            buf[head + int(offsets[j]):head + int(offsets[j + 1])] = np.frombuffer(infos[k].zstream, np.uint8)
-        dev = staging.to(device, non_blocking=True)
-        whole = n == N
-        if channels == "first":
-            first = out if whole else torch.empty((n, H, W), dtype=torch.uint8, device=device)
-            st = inflate_unfilter_device(dev[head:], dev[:head].view(torch.int64), n, H, W, bpp, first=first)
-            got = first
-        else:
-            full = out if whole else torch.empty((n, H, W, bpp), dtype=torch.uint8, device=device)
-            st = inflate_unfilter_device(dev[head:], dev[:head].view(torch.int64), n, H, W, bpp, full=full)
-            got = full
-        pending.append((idx, st, got, whole, staging))
-    for idx, st, got, whole, _ in pending:
-        status[idx] = st.cpu().numpy()           # the D2H copy of the status: the only synchronisation
-        if not whole:
-            out[torch.as_tensor(idx, device=device)] = got
-    failed = [k for k in range(N) if status[k] != 0]
-    for k in failed:
-        host_frames[k] = _host_frame(sources[k], channels)      # a corrupt file raises here what it raises today
-        if host_frames[k].shape != tuple(shape):
-            raise ValueError("png: file %d decodes to %s on the host, %s was expected" % (k, host_frames[k].shape, shape))
-    fallback = sorted(host_frames)
-    if fallback:
-        up = torch.from_numpy(np.stack([host_frames[k] for k in fallback])).to(device)
-        out[torch.as_tensor(fallback, device=device)] = up
-    return (out, status, fallback) if return_info else out
+        pending = []
+        for bpp, ks in groups.items():
+            n = len(ks)
+            streams = [np.frombuffer(infos[k].zstream, np.uint8) for k in ks]
+            offsets = np.zeros(n + 1, np.int64)      # relative to the start of the streams
+            np.cumsum([v.size for v in streams], out=offsets[1:])
+            # one pinned upload: the offsets (64-bit) first, then the streams back to back
+            dev, _, staging = stage([offsets] + streams, device, pinned=True, align=1)
+            head = 8 * (n + 1)
+            got = out if n == len(out) else torch.empty((n,) + shape, dtype=torch.uint8, device=device)
+            st = inflate_unfilter_device(dev[head:], dev[:head].view(torch.int64), n, H, W, bpp,
+                                         **{"first" if channels == "first" else "full": got})
+            pending.append((ks, st, got, staging))
+        return pending, ()
+
+    return decode_batch(infos, sources, device, channels, return_info, "png", lambda info: info.channels, launch)
 
 
 def decode_png_device(datas, device=None, channels="first", return_info=False, threads=MAX_THREADS):
@@ -709,24 +625,15 @@ def decode_png_device(datas, device=None, channels="first", return_info=False, t
     have one size (ValueError otherwise).  return_info: also the status array (inflate_core.h's codes, STATUS_NAMES) and
     the sorted indices of the files the host decoded."""
     datas = list(datas)
-    if not datas:
-        return _decode_parsed([], [], device, channels, return_info)
-    with ThreadPoolExecutor(max_workers=_pool_size(threads, len(datas))) as pool:      # zlib.crc32 releases the lock
-        infos = list(pool.map(parse_png, datas))
-    return _decode_parsed(infos, datas, device, channels, return_info)
+    return decode_parsed_png(map_pool(parse_png, datas, threads), datas, device, channels, return_info)  # crc32: no lock
 
 
-def _read_and_parse(path):
-    with open(path, "rb") as f:
-        return parse_png(f.read())
+def parse_png_file(path):
+    return parse_png(read_file(path))
 
 
 def read_png_device(paths, threads=MAX_THREADS, device=None, channels="first", return_info=False):
     """decode_png_device of files on disk, read and parsed by a thread pool of this process (at most 16 threads; nothing
     is forked)."""
     paths = list(paths)
-    if not paths:
-        return _decode_parsed([], [], device, channels, return_info)
-    with ThreadPoolExecutor(max_workers=_pool_size(threads, len(paths))) as pool:
-        infos = list(pool.map(_read_and_parse, paths))
-    return _decode_parsed(infos, paths, device, channels, return_info)
+    return decode_parsed_png(map_pool(parse_png_file, paths, threads), paths, device, channels, return_info)

@@ -155,6 +155,35 @@ def test_damaged_file_between_sound_ones(kind):
     assert np.array_equal(got[0], want) and np.array_equal(got[2], want) and np.array_equal(got[1], pil)
 
 
+def test_no_files():
+    _need_gpu()
+    from spnet_amd import jpeg as J
+    assert tuple(J.decode_jpeg_device([]).shape) == (0, 0, 0)
+    assert tuple(J.decode_jpeg_device([], channels="all").shape) == (0, 0, 0, 0)
+    for channels, shape in (("first", (0, 0, 0)), ("all", (0, 0, 0, 0))):
+        out, status, info = J.decode_jpeg_device([], channels=channels, return_info=True)
+        assert tuple(out.shape) == shape and out.dtype == torch.uint8 and out.is_cuda
+        assert status.shape == (0,) and status.dtype == np.int32
+        assert isinstance(info, J.DecodeInfo) and info == [] and (info.lane_intervals, info.sync_intervals) == (0, 0)
+
+
+@pytest.mark.parametrize("at", [0, 1, 2])
+def test_host_only_file_among_device_files(at):
+    """Two files the device decodes and a progressive one the host has to, first, in the middle and last: the device's
+    frames are scattered into their places, the host's uploaded into its own; Pillow's pixels in input order."""
+    _need_gpu()
+    from spnet_amd import jpeg as J
+    frames = [C.content("noise", (16, 16), s) for s in range(3)]
+    datas = [jpeg_ref.encode_jpeg(frames[0], 90), C.pillow_jpeg(frames[1], quality=60)]
+    datas.insert(at, C.progressive(frames[2]))
+    assert [J.parse_jpeg(d).device for d in datas] == [k != at for k in range(3)]
+    want = np.stack([C.pillow_pixels(d) for d in datas])
+    for channels, pixels in (("first", want[:, :, :, 0]), ("all", want)):
+        out, status, info = J.decode_jpeg_device(datas, channels=channels, return_info=True)
+        assert info == [at] and not status.any() and info.lane_intervals + info.sync_intervals == 3
+        assert np.array_equal(out.cpu().numpy(), pixels)
+
+
 def test_round_trips_through_the_device_encoder_and_a_movie(tmp_path):
     _need_gpu()
     from spnet_amd import jpeg as J

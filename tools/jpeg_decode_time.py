@@ -141,11 +141,11 @@ def main():
     def default_path(paths):
         def one(p):
             return np.asarray(Image.open(p).convert("RGB"), dtype=np.uint8)[:, :, 0]
-        with ThreadPoolExecutor(max_workers=16) as pool:
+        with ThreadPoolExecutor(max_workers=J.MAX_THREADS) as pool:
             host = np.stack(list(pool.map(one, paths)))
         return torch.from_numpy(host).cuda()
 
-    result = dict(frames=N, size=[384, 512], quality=args.quality, rounds=args.rounds, host_workers=16,
+    result = dict(frames=N, size=[384, 512], quality=args.quality, rounds=args.rounds, host_workers=J.MAX_THREADS,
                   device=torch.cuda.get_device_name(0), default_entropy=J.DEFAULT_ENTROPY, sync_min_bytes=J.SYNC_MIN_BYTES,
                   sync_seg_bytes=J.SYNC_SEG_BYTES, sync_workgroup_lanes=256, sources={})
     with tempfile.TemporaryDirectory() as tmp:

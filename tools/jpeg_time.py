@@ -30,7 +30,7 @@ from tools.png_time import draw_overlays
 from tools.resize_time import gpu_time
 
 CHUNK = 256
-THREADS = 16
+from spnet_amd.codec_host import MAX_THREADS as THREADS
 
 
 def four_ways(dev, tmp, repeats, quality):

@@ -37,7 +37,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 from PIL import Image
 
-THREADS = 16
+from spnet_amd.codec_host import MAX_THREADS as THREADS
 FORMS = ("pillow", "device", "level1")
 
 

@@ -33,7 +33,7 @@ from PIL import Image
 from tools.resize_time import gpu_time
 
 CHUNK = 256
-THREADS = 16
+from spnet_amd.codec_host import MAX_THREADS as THREADS
 
 
 def draw_overlays(frames, labels):

@@ -935,6 +935,37 @@ int spnet_ring_masks(const double* rows, const int* count, int B, int K, int H, 
 int spnet_mask_compare(const unsigned char* pred, const unsigned char* truth, int N, long n_pixels, int tol, int* counts,
                        void* stream);
 
+/* ---- Mask fitting (csrc/mask_fit.hip, csrc/mask_fit_core.h): the inverse of spnet_ring_masks as far as it has one --
+ *      connected components of a ring-count mask and eight integer sums per component, from which the host forms ellipse
+ *      rows (spnet_amd/masks.py rows_from_sums, float64).  masks.py holds the same rule in numpy; DESIGN.md 5h ----------- */
+/* THE RULE.  A mask is uint8 [H][W], background 0.
+ *   Adjacency   two pixels are adjacent iff they are 8-neighbours, both are nonzero, and their values differ by at most
+ *               join_tol (0 .. 255).  join_tol 0 joins equal values only (what spnet_ring_masks paints: one value per
+ *               row); 255 joins anything nonzero.
+ *   Component   a connected component of that graph (well defined although the predicate is not transitive: 10, 14, 18
+ *               in a chain are one component at join_tol 4).
+ *   Label       1 + (y * W + x) of the component's FIRST pixel in raster order, for every pixel of the component;
+ *               background 0.  int32: H * W <= 2^31 - 2, which H, W <= 16,384 guarantees.
+ *   Order       the components of a frame in ascending label.
+ *   Sums        eight int64 per component: n, sum x, sum y, sum x^2, sum y^2, sum x y, sum v, first -- first = label - 1,
+ *               v the pixel's value, x and y its whole-number coordinates.  All fit 64 bits at 16,384 x 16,384.
+ * spnet_mask_label    masks uint8 [B][H][W], H, W 1 .. 16,384, join_tol 0 .. 255.  Writes EVERY element of labels int32
+ *                     [B][H][W] (which is also the working store: its contents before the call do not matter).  Three
+ *                     launches for any mask: no readback, no iteration count that depends on the mask.
+ * spnet_mask_moments  labels as spnet_mask_label wrote them for masks (the label form above is what it relies on: a
+ *                     component's first pixel, and only that pixel, holds its own index + 1).  C 1 .. 128.  Writes
+ *                     n_components int32 [B], the TRUE number of components of each frame, which may exceed C, and sums
+ *                     int64 [B][C][8]: the first min(n, C) components of the frame in label order, the remaining slots
+ *                     zeroed.  Both are written, not accumulated into.  The sums are integer additions: they do not
+ *                     depend on the grid or on the order of arrival.
+ * Both: B == 0 succeeds and launches nothing.  hipErrorInvalidValue, and nothing launched, for a NULL pointer, a size,
+ * join_tol or C outside these limits, labels / n_components not 4-byte aligned, sums not 8-byte aligned.  No value in
+ * masks or labels causes an access outside the arrays (labels are only ever compared, never used as an address, by
+ * spnet_mask_moments). */
+int spnet_mask_label(const unsigned char* masks, int B, int H, int W, int join_tol, int* labels, void* stream);
+int spnet_mask_moments(const unsigned char* masks, const int* labels, int B, int H, int W, int C, int* n_components,
+                       long long* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

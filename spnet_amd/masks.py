@@ -21,6 +21,19 @@ finite, if aq <= 0 or bq <= 0, or if |cx|, |cy|, a or b is 32,768 or more.  A ro
   write_masks             PNG files, by Pillow or by the device encoder (png.write_png_device)
   ring_masks_host         the rule in numpy (exact; slow): what the product uses where there is no GPU
 
+THE WAY BACK (csrc/mask_fit.hip; include/spnet_hip.h "Mask fitting"): ellipse rows from a mask.  Two pixels are
+adjacent iff they are 8-neighbours, both nonzero, and their values differ by at most join_tol (0 .. 255; 0 joins equal values
+only, 255 anything nonzero).  A component is a connected component of that graph; its label, for every one of its pixels, is
+1 + (y W + x) of its FIRST pixel in raster order, background 0; components are ordered by label; each has eight int64 sums
+(n, sum x, sum y, sum x^2, sum y^2, sum xy, sum v, first = label - 1).  rows_from_sums turns the sums into rows in float64, on
+the host, for the device path and the host path alike -- so the two agree bit for bit.
+
+  label_components_device / _host     uint8 [B,H,W] -> int32 labels [B,H,W]
+  component_sums_device / _host       -> (n_components int32 [B] -- the TRUE count --, sums int64 [B,C,8])
+  rows_from_sums                      sums -> (rows float64 [B,C,6], count int32 [B]): pad_metadata's layout
+  ellipses_from_masks_device / _host  masks -> (rows, count)
+  read_masks                          PNG files -> uint8 [N,H,W], by Pillow or by png.read_png_device
+
 Nothing here imports torch or the HIP library until a device function is called.
 """
 import math
@@ -276,3 +289,262 @@ def write_masks(masks, paths, png="pillow", pool=None):
     if not masks.is_cuda:
         masks = masks.to(_default_device(None))
     write_png_device(masks, paths, pool=pool, lz77=(png == "device-lz"))
+
+
+# ----------------------------------------------------------------------------- the way back: components, sums, rows
+N_SUMS = 8
+SUM_NAMES = ("n", "sx", "sy", "sxx", "syy", "sxy", "sv", "first")
+
+
+def _check_fit(join_tol, max_components=1, min_pixels=1):
+    if not (isinstance(join_tol, (int, np.integer)) and 0 <= join_tol <= 255):
+        raise ValueError("masks: join_tol is an integer 0 .. 255, got %r" % (join_tol,))
+    if not (isinstance(max_components, (int, np.integer)) and 1 <= max_components <= MAX_K):
+        raise ValueError("masks: max_components is an integer 1 .. %d, got %r" % (MAX_K, max_components))
+    if not (isinstance(min_pixels, (int, np.integer)) and min_pixels >= 1):
+        raise ValueError("masks: min_pixels is an integer >= 1, got %r" % (min_pixels,))
+
+
+def _host_masks(masks):
+    m = np.asarray(masks)
+    if m.dtype != np.uint8 or m.ndim != 3:
+        raise TypeError("masks: expected uint8 [B,H,W], got %s %s" % (m.dtype, m.shape))
+    if m.shape[0]:
+        _check_size(m.shape[1], m.shape[2])
+    return m
+
+
+def _label_frame_host(mask, join_tol):
+    """One frame.  A union-find over RUNS: a run is a maximal stretch of a row whose consecutive pixels are adjacent; runs
+    are numbered in raster order of their first pixel, two runs of neighbouring rows are linked where a pixel of one is
+    adjacent (by the rule: value test included) to a pixel of the other, and every root is its tree's smallest run -- whose
+    first pixel is the component's first pixel."""
+    H, W = mask.shape
+    v = mask.astype(np.int16)
+    nz = v != 0
+    if not nz.any():
+        return np.zeros((H, W), np.int32)
+    link_w = np.zeros((H, W), bool)
+    link_w[:, 1:] = nz[:, 1:] & nz[:, :-1] & (np.abs(v[:, 1:] - v[:, :-1]) <= join_tol)
+    start = (nz & ~link_w).ravel()
+    first_pixel = np.flatnonzero(start)                          # of every run, ascending
+    run_of = (np.cumsum(start) - 1).reshape(H, W)                # of every nonzero pixel (meaningless on background)
+    ea, eb = [], []
+    for cur, up in (((slice(1, None), slice(1, None)), (slice(None, -1), slice(None, -1))),       # NW
+                    ((slice(1, None), slice(None)), (slice(None, -1), slice(None))),              # N
+                    ((slice(1, None), slice(None, -1)), (slice(None, -1), slice(1, None)))):      # NE
+        ok = nz[cur] & nz[up] & (np.abs(v[cur] - v[up]) <= join_tol)
+        ea.append(run_of[cur][ok])
+        eb.append(run_of[up][ok])
+    n_runs = first_pixel.size
+    pairs = np.unique(np.concatenate(ea).astype(np.int64) * n_runs + np.concatenate(eb))
+    ea, eb = pairs // n_runs, pairs % n_runs
+    parent = np.arange(n_runs, dtype=np.int64)
+    while ea.size:                                               # every round merges at least one pair of trees
+        ra, rb = parent[ea], parent[eb]                          # roots: the forest is flat at the top of a round
+        differ = ra != rb
+        if not differ.any():
+            break
+        np.minimum.at(parent, np.maximum(ra, rb)[differ], np.minimum(ra, rb)[differ])     # the larger root under a smaller
+        while True:                                              # flatten: depths halve
+            pp = parent[parent]
+            if np.array_equal(pp, parent):
+                break
+            parent = pp
+    return np.where(nz, first_pixel[parent[run_of]] + 1, 0).astype(np.int32)
+
+
+def label_components_host(masks, join_tol=0):
+    """The labelling rule in numpy: uint8 [B,H,W] -> int32 [B,H,W].  What the product uses where there is no GPU."""
+    masks = _host_masks(masks)
+    _check_fit(join_tol)
+    out = np.zeros(masks.shape, np.int32)
+    for b in range(masks.shape[0]):
+        out[b] = _label_frame_host(masks[b], int(join_tol))
+    return out
+
+
+def _sums_frame_host(mask, labels):
+    """int64 [n,8] of one frame's components in label order (all of them)."""
+    W = mask.shape[1]
+    idx = np.flatnonzero(labels.ravel() > 0)
+    if not idx.size:
+        return np.zeros((0, N_SUMS), np.int64)
+    lab = labels.ravel()[idx].astype(np.int64)
+    order = np.argsort(lab, kind="stable")
+    lab, idx = lab[order], idx[order]
+    starts = np.flatnonzero(np.concatenate([[True], lab[1:] != lab[:-1]]))
+    y, x = np.divmod(idx.astype(np.int64), W)
+    v = mask.ravel()[idx].astype(np.int64)
+    cols = [np.ones_like(x), x, y, x * x, y * y, x * y, v]
+    return np.stack([np.add.reduceat(c, starts) for c in cols] + [lab[starts] - 1], 1)
+
+
+def component_sums_host(masks, join_tol=0, max_components=MAX_K, labels=None):
+    """(n_components int32 [B] -- the true count, which may exceed max_components --, sums int64 [B,C,8]: the first
+    min(n, C) components of every frame in label order, the other slots zero).  labels: label_components_host's, if the
+    caller has them."""
+    masks = _host_masks(masks)
+    _check_fit(join_tol, max_components)
+    if labels is None:
+        labels = label_components_host(masks, join_tol)
+    labels = np.asarray(labels)
+    if labels.shape != masks.shape:
+        raise ValueError("component_sums: labels %s for masks %s" % (labels.shape, masks.shape))
+    B, C = masks.shape[0], int(max_components)
+    n, sums = np.zeros(B, np.int32), np.zeros((B, C, N_SUMS), np.int64)
+    for b in range(B):
+        s = _sums_frame_host(masks[b], labels[b])
+        n[b] = s.shape[0]
+        sums[b, :min(s.shape[0], C)] = s[:C]
+    return n, sums
+
+
+def rows_from_sums(sums, n_components, min_pixels=1):
+    """Ellipse rows of components: (rows float64 [B,C,6] = (cx, cy, a, b, angle_deg, rings), count int32 [B]), in
+    pad_metadata's layout.  The ONE float64 function of the fit, shared by the device path and the host path (numpy on the
+    host; torch tensors are brought to the host and the result goes back to their device), so both give the same bits.
+    With N = n, mx = sx / N, my = sy / N: mu20 = sxx / N - mx^2 + 1/12 (1/12: a pixel is a unit square), mu02 likewise,
+    mu11 = sxy / N - mx my; l1 >= l2 the eigenvalues of [[mu20, mu11], [mu11, mu02]]; cx = mx + 0.5, cy = my + 0.5 (the
+    painter puts pixel centres at x + 0.5); a = 2 sqrt(l1), b = 2 sqrt(max(l2, 0)) (a filled ellipse of semi-axis a has
+    variance a^2 / 4); angle_deg = -deg(atan2(2 mu11, mu20 - mu02) / 2) (image y points down: the painter's convention);
+    rings = sv / (10 N).  Only the first min(n_components, C) slots of a frame count; of those, components with fewer than
+    min_pixels pixels are dropped, the rest are packed to the front in order, the rows behind them are zero."""
+    as_torch = hasattr(sums, "is_cuda")
+    if as_torch:
+        import torch
+        device = sums.device
+        sums, n_components = sums.cpu().numpy(), n_components.cpu().numpy()
+    s, n = np.asarray(sums), np.asarray(n_components)
+    if s.dtype != np.int64 or s.ndim != 3 or s.shape[2] != N_SUMS or n.shape != (s.shape[0],):
+        raise ValueError("rows_from_sums: sums are int64 [B,C,8] with n_components [B], got %s %s and %s"
+                         % (s.dtype, s.shape, n.shape))
+    _check_fit(0, min_pixels=min_pixels)
+    B, C = s.shape[:2]
+    slot = np.arange(C)[None, :]
+    valid = (slot < np.minimum(n.astype(np.int64), C)[:, None]) & (s[..., 0] >= int(min_pixels))
+    f = s.astype(np.float64)
+    N = np.where(valid, f[..., 0], 1.0)
+    mx, my = f[..., 1] / N, f[..., 2] / N
+    mu20 = f[..., 3] / N - mx * mx + 1.0 / 12.0
+    mu02 = f[..., 4] / N - my * my + 1.0 / 12.0
+    mu11 = f[..., 5] / N - mx * my
+    mean, half = 0.5 * (mu20 + mu02), 0.5 * (mu20 - mu02)
+    r = np.sqrt(half * half + mu11 * mu11)
+    a = 2.0 * np.sqrt(np.maximum(mean + r, 0.0))
+    b = 2.0 * np.sqrt(np.maximum(mean - r, 0.0))
+    angle = -np.degrees(0.5 * np.arctan2(2.0 * mu11, mu20 - mu02)) + 0.0          # + 0.0: no negative zero
+    rings = f[..., 6] / (10.0 * N)
+    rows = np.stack([mx + 0.5, my + 0.5, a, b, angle, rings], -1)
+    order = np.argsort(~valid, axis=1, kind="stable")                             # kept components first, in order
+    rows = np.take_along_axis(rows, order[..., None], 1)
+    count = valid.sum(1).astype(np.int32)
+    rows[slot >= count[:, None]] = 0.0
+    if as_torch:
+        return torch.from_numpy(rows).to(device), torch.from_numpy(count).to(device)
+    return rows, count
+
+
+def _overflow_check(n, C, overflow):
+    if overflow not in ("raise", "truncate"):
+        raise ValueError("masks: overflow is 'raise' or 'truncate', got %r" % (overflow,))
+    over = np.flatnonzero(np.asarray(n) > C)
+    if overflow == "raise" and over.size:
+        raise ValueError("masks: frame %d holds %d components, more than max_components = %d (overflow='truncate' keeps "
+                         "the first %d in raster order)" % (over[0], n[over[0]], C, C))
+
+
+def ellipses_from_masks_host(masks, join_tol=0, min_pixels=1, max_components=MAX_K, overflow="raise"):
+    """(rows float64 [B,C,6], count int32 [B]) of masks uint8 [B,H,W], in numpy.  ValueError naming the frame that holds
+    more than max_components components, unless overflow="truncate"."""
+    _check_fit(join_tol, max_components, min_pixels)
+    n, sums = component_sums_host(masks, join_tol, max_components)
+    _overflow_check(n, int(max_components), overflow)
+    return rows_from_sums(sums, n, min_pixels)
+
+
+def _device_masks(masks):
+    import torch
+    if not isinstance(masks, torch.Tensor):
+        masks = torch.from_numpy(np.ascontiguousarray(_host_masks(masks)))
+    if not masks.is_cuda:
+        masks = masks.to(_default_device(None))
+    if masks.dtype != torch.uint8 or masks.dim() != 3:
+        raise TypeError("masks: expected a uint8 tensor [B,H,W], got %s %s" % (masks.dtype, tuple(masks.shape)))
+    if masks.shape[0]:
+        _check_size(int(masks.shape[1]), int(masks.shape[2]))
+    return masks.contiguous()
+
+
+def label_components_device(masks, join_tol=0):
+    """int32 [B,H,W] device tensor of labels (spnet_mask_label: three launches on the current stream, for any mask).
+    masks: a uint8 device tensor [B,H,W], or a host array, which is uploaded."""
+    import torch
+    from . import _lib as L
+    _check_fit(join_tol)
+    masks = _device_masks(masks)
+    B, H, W = (int(v) for v in masks.shape)
+    labels = torch.empty((B, H, W), dtype=torch.int32, device=masks.device)
+    if B and H and W:
+        with torch.cuda.device(masks.device):
+            L.spnet_mask_label(masks.data_ptr(), B, H, W, int(join_tol), labels.data_ptr(), L.current_stream())
+    return labels
+
+
+def component_sums_device(masks, join_tol=0, max_components=MAX_K, labels=None):
+    """(n_components int32 [B], sums int64 [B,C,8]) device tensors, see component_sums_host (spnet_mask_moments: two
+    launches behind label_components_device's three).  labels: label_components_device's, if the caller has them."""
+    import torch
+    from . import _lib as L
+    _check_fit(join_tol, max_components)
+    masks = _device_masks(masks)
+    if labels is None:
+        labels = label_components_device(masks, join_tol)
+    if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int32 and labels.device == masks.device and
+            labels.shape == masks.shape and labels.is_contiguous()):
+        raise ValueError("component_sums_device: labels are a contiguous int32 tensor %s on %s"
+                         % (tuple(masks.shape), masks.device))
+    B, H, W = (int(v) for v in masks.shape)
+    C = int(max_components)
+    n = torch.empty((B,), dtype=torch.int32, device=masks.device)
+    sums = torch.empty((B, C, N_SUMS), dtype=torch.int64, device=masks.device)
+    if B and H and W:
+        with torch.cuda.device(masks.device):
+            L.spnet_mask_moments(masks.data_ptr(), labels.data_ptr(), B, H, W, C, n.data_ptr(), sums.data_ptr(),
+                                 L.current_stream())
+    return n, sums
+
+
+def ellipses_from_masks_device(masks, join_tol=0, min_pixels=1, max_components=MAX_K, overflow="raise"):
+    """ellipses_from_masks_host with the labelling and the sums on the GPU: (rows float64 [B,C,6], count int32 [B]) device
+    tensors, ready for ring_masks_device, augmentation.encode_targets_device (K <= 16 there) and the overlay planner.  The
+    B x C x 8 sums come to the host for rows_from_sums (a few KB; the component counts have to come anyway, for the
+    ValueError that names a frame with more than max_components components -- overflow="truncate" keeps the first
+    max_components in raster order instead) and the rows go back: the same bits as the host path."""
+    _check_fit(join_tol, max_components, min_pixels)
+    n, sums = component_sums_device(masks, join_tol, max_components)
+    _overflow_check(n.cpu().numpy(), int(max_components), overflow)
+    return rows_from_sums(sums, n, min_pixels)
+
+
+def read_masks(paths, device_decode=False):
+    """uint8 [N,H,W] of 8-bit grey PNG mask files: a host array by Pillow, or with device_decode a device tensor by
+    png.read_png_device.  A missing file is a FileNotFoundError that names it; all files have one size."""
+    import os
+    paths = list(paths)
+    for p in paths:
+        if not os.path.isfile(p):
+            raise FileNotFoundError("read_masks: no mask file %s" % p)
+    if device_decode:
+        from .png import read_png_device
+        return read_png_device(paths)
+    from PIL import Image
+    out = []
+    for p in paths:
+        with Image.open(p) as img:
+            if img.mode not in ("L", "P", "1"):
+                raise ValueError("read_masks: %s is not an 8-bit grey image (mode %s)" % (p, img.mode))
+            out.append(np.asarray(img.convert("L") if img.mode == "1" else img, np.uint8))
+        if out[-1].shape != out[0].shape:
+            raise ValueError("read_masks: %s is %s, the first file %s" % (p, out[-1].shape, out[0].shape))
+    return np.stack(out) if out else np.zeros((0, 1, 1), np.uint8)

@@ -592,9 +592,9 @@ int spnet_fake_espi_params(long first_frame, int N, int H, int W, unsigned seed,
 
 /* ---- band-pass mix-up (spnet/augmentation.py:10-62; csrc/bandpass.hip) ------------------------------------------- */
 /* Frames x [*][H][W], one channel, 16 <= H, W <= 2048; x_kind 0 = uint8, 1 = fp32 pixel units (0..255), 2 = fp32 network
- * units ([-1,1], pixel = (x/2 + 1/2) * 255).  A window is the 16 x 16 block of the centred spectrum, frequencies k, l in
- * [-8, 8), as [16][16] complex (re, im) fp32, row k + 8, column l + 8.  ws: spnet_bandpass_ws(N, H, W) floats (-1 = the
- * dimensions are not supported).
+ * units ([-1,1], pixel = (x/2 + 1/2) * 255, each operation rounded on its own: the bits of x_kind 1 on those pixels).
+ * A window is the 16 x 16 block of the centred spectrum, frequencies k, l in [-8, 8), as [16][16] complex (re, im) fp32,
+ * row k + 8, column l + 8.  ws: spnet_bandpass_ws(N, H, W) floats (-1 = the dimensions are not supported).
  *   spnet_bandpass_project  win[n] = window of x[n] after cv2.flip(x[n], flip[n]) (flip NULL or a code outside
  *                           {-1, 0, 1}: not flipped) -- the real-image table of the mix-up.
  *   spnet_bandpass_apply    frame m = x[sel[m]] (sel NULL: x[m]; sel clamped to [0, n_src)), mixed with window

@@ -41,10 +41,14 @@ __device__ __forceinline__ int bp_mod(long a, int n) {
 
 template <int KIND>
 __device__ __forceinline__ float bp_pixel(const void* __restrict__ x, long i) {
+  // Products written here, under contract(off): __fmul_rn is a plain product in a header, which the caller's
+  // `pixel - p0` fuses with into one FMA -- the centred value is then not that of the rounded pixel, and x_kind 2 differs
+  // from x_kind 1 on the same pixels.
+#pragma clang fp contract(off)
   if (KIND == 0) return (float)static_cast<const unsigned char*>(x)[i];
   const float v = static_cast<const float*>(x)[i];
   if (KIND == 1) return v;
-  return __fmul_rn(__fadd_rn(__fmul_rn(v, 0.5f), 0.5f), 255.f);
+  return (v * 0.5f + 0.5f) * 255.f;
 }
 
 __device__ __forceinline__ int bp_clamp(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }

@@ -141,3 +141,103 @@ def test_frames_smaller_than_the_window_raise(tmp_path, H, W):
         A.BandpassPool(str(tmp_path), H, W)
     with pytest.raises(ValueError, match="16 x 16"):
         A.bandpass_mixup(np.zeros((H, W), np.uint8), str(tmp_path))
+
+
+# ---- the kernel-level helpers of bandpass_ref: the emulation of csrc/bandpass.hip sits within the derived bounds ----------
+def _complex(F):
+    return np.stack([F.real, F.imag], -1)
+
+
+def _project_ratio(d, flip, mutant=None):
+    """largest |emulate_project - window()| / project_bound over the frames of d [N,H,W] (float32 pixel values)"""
+    got = R.emulate_project(d, flip=flip, mutant=mutant).astype(np.float64)
+    worst = 0.0
+    for n in range(len(d)):
+        t = R.cv2_flip(d[n].astype(np.float64), 2 if flip is None else int(flip[n]))
+        worst = max(worst, R.ratio(np.abs(got[n] - _complex(R.window(t))), R.project_bound(t)))
+    return worst
+
+
+def _apply_ratio(x, table, row, s, mutant=None, need_finite=True):
+    got = R.emulate_apply(x, table, row, s, mutant=mutant).astype(np.float64)
+    worst = 0.0
+    for n in range(len(x)):
+        b = R.apply_bound(x[n], table[row[n]], s[n])
+        if need_finite:
+            assert np.isfinite(b["bound"]).all()
+        if np.isfinite(b["bound"]).all():                         # the bound's reference is mixed()
+            assert np.abs(b["ref"] - R.mixed(x[n], table[row[n]], s[n])).max() <= 1e-6
+        worst = max(worst, R.ratio(np.abs(got[n] - b["ref"]), b["bound"]))
+    return worst
+
+
+def _impulses(H, W):
+    pos = R.edge_positions(H, W)
+    return pos, np.stack([R.impulse_frame(H, W, r, c) for r, c in pos])
+
+
+@pytest.mark.parametrize("H,W", R.SHAPES)
+def test_emulated_projection_is_within_project_bound(H, W):
+    pos, x = _impulses(H, W)
+    for shift, codes in enumerate(([-1, 0, 1, 2, 7], [0, 1, 2, 7, -1], [1, 2, 7, -1, 0])):
+        flip = [codes[i % 5] for i in range(len(pos))]
+        assert _project_ratio(x, flip) <= 1.0
+    for r, c in pos:                                              # one term: a few ulp of A (ulp(200) = 2^-16)
+        assert R.project_bound(R.impulse_frame(H, W, r, c)).max() <= 5 * 2.0 ** -16
+    assert _project_ratio(R.dense_frames(3, H, W, H + W), [1, -1, 0]) <= 1.0
+    assert _project_ratio(R.dense_frames(3, H, W, H + W + 1), None) <= 1.0
+    assert np.array_equal(R.emulate_project(np.zeros((1, H, W), np.float32)), np.zeros((1, 16, 16, 2), np.float32))
+
+
+@pytest.mark.parametrize("H,W", R.SHAPES)
+def test_reconstruction_cases_are_well_conditioned_and_emulation_within_recon_bound(H, W):
+    table = R.recon_table(H, W)
+    x = np.full((3, H, W), 77.0, np.float32)                      # constant: d = 0 and F = 0 exactly
+    s = np.ones(3, np.float32)
+    G = R.mix_g32(table, s, np.zeros_like(table), H, W)
+    got = R.emulate_apply(x, table, np.arange(3), s).astype(np.float64)
+    for n in range(3):
+        b = R.recon_bound(G[n], np.zeros((H, W)), centred=False)
+        assert b["range"] >= 0.25 * b["ymax"], (n, b["range"], b["ymax"])
+        assert np.isfinite(b["bound"]).all() and b["bound"].max() < 1e-2
+        assert R.ratio(np.abs(got[n] - b["ref"]), b["bound"]) <= 1.0
+
+
+@pytest.mark.parametrize("H,W", R.SHAPES)
+def test_emulated_apply_is_within_the_propagated_bound(H, W):
+    pos, x = _impulses(H, W)
+    zero = np.zeros((1, 16, 16, 2), np.float32)
+    n = len(pos)
+    # at 16 x 16 the window is the whole spectrum: y = 0 in exact arithmetic and the bound is infinite (says nothing)
+    assert _apply_ratio(x, zero, np.zeros(n, int), np.ones(n, np.float32), need_finite=(H, W) != (16, 16)) <= 1.0
+    table = R.dense_table(4, H, W, 5)
+    for s in R.S_VALUES:
+        assert _apply_ratio(R.dense_frames(3, H, W, 9), table, np.array([3, 0, 2]), np.full(3, s, np.float32),
+                            need_finite=(H, W) != (16, 16) or s > 0) <= 1.0
+
+
+@pytest.mark.parametrize("H,W", R.SHAPES)
+def test_wrong_emulations_break_the_bounds_on_the_impulse_cases(H, W):
+    """the evidence that the bounds can fail: three one-line bugs, each far outside them wherever its branch is reached"""
+    pos, x = _impulses(H, W)
+    if W > R.BP_TPB:                                              # a second column tile exists
+        assert _project_ratio(x, None, mutant="phase") > 100.0
+    else:
+        assert _project_ratio(x, None, mutant="phase") <= 1.0
+    if H % R.BP_RB:                                               # the last row block is ragged: it reads the next frame's rows
+        assert _project_ratio(x, None, mutant="nr") > 100.0
+    else:
+        assert _project_ratio(x, None, mutant="nr") <= 1.0
+    if (H, W) != (16, 16):
+        n = len(pos)
+        zero = np.zeros((1, 16, 16, 2), np.float32)
+        assert _apply_ratio(x, zero, np.zeros(n, int), np.ones(n, np.float32), mutant="sign") > 100.0
+
+
+def test_pixel_conversion_and_twiddles_of_the_emulation():
+    v = R.network_value_of(R.IMPULSE)
+    assert v is None or float(R.to_pixel32(v)) == R.IMPULSE
+    assert float(R.to_pixel32(np.float32(1.0))) == 255.0 and float(R.to_pixel32(np.float32(-1.0))) == 0.0
+    c, s = R.twiddle32(np.arange(8), 8)
+    assert c[2] == 0 and c[6] == 0 and s[0] == 0 and s[4] == 0 and c[4] == -1 and s[6] == -1
+    assert abs(float(c[1]) - np.sqrt(0.5)) <= 2.0 ** -25

@@ -966,6 +966,53 @@ int spnet_mask_label(const unsigned char* masks, int B, int H, int W, int join_t
 int spnet_mask_moments(const unsigned char* masks, const int* labels, int B, int H, int W, int C, int* n_components,
                        long long* sums, void* stream);
 
+/* ---- Antinode tracks (csrc/tracks.hip, csrc/tracks_core.h, csrc/mask_rule.h): which ellipse of a later frame is the same
+ *      antinode as one of an earlier frame.  spnet_amd/tracks.py is the host side and holds the same rule in numpy;
+ *      DESIGN.md 5i ----------------------------------------------------------------------------------------------------- */
+/* THE RULE.  Input is rows double [N][K][6] = (cx, cy, a, b, angle_deg, rings) and count int32 [N], clamped to 0 .. K:
+ * the layout spnet_ring_masks reads, frames in time order.
+ *   Live      detection (t, k) is live iff k < count[t] and the mask rule's quantisation accepts the row: six finite
+ *             values, |cx|, |cy|, a, b below 32,768, aq > 0 and bq > 0.  rings takes no part.
+ *   Pixel set S(t, k): the pixels 0 <= x < W, 0 <= y < H that the mask rule calls inside row (t, k) -- the same integers
+ *             and the same 128-bit comparison as spnet_ring_masks, every row taken ALONE ("last row wins" plays no part).
+ *             area[t][k] = |S(t, k)|, 0 for a dead row.
+ *   Overlap   for a gap d in 1 .. G and t + d < N: inter_d[t][i][j] = |S(t, i) ^ S(t + d, j)| (intersection),
+ *             union = area_i + area_j - inter.
+ *   Eligible  a pair is eligible iff inter > 0 and 1024 * inter >= iou_q * union; iou_q 1 .. 1024 is the IoU threshold in
+ *             1/1024.
+ *   Better    candidate p beats q iff inter_p * union_q > inter_q * union_p; on equality the LOWER INDEX wins.  No floating
+ *             point takes part after the quantisation; every product fits 64 bits.
+ *   Linking   passes d = 1, 2, .., G in this order.  In pass d, for every frame pair (t, t + d): F = the live detections of
+ *             frame t with no successor yet, P = the live detections of frame t + d with no predecessor yet; i -> j is
+ *             linked iff j is the best eligible member of P for i AND i is the best eligible member of F for j.
+ *             next[t][i] = (t + d) * K + j, prev[t + d][j] = t * K + i, -1 where there is no link.  Within one pass the
+ *             pairs are independent: pair (t, t + d) alone writes next[t] and prev[t + d] and reads only what earlier
+ *             passes wrote.  A detection has at most one successor and one predecessor: the links form chains.
+ *   Tracks    track[t][k] = 1 + the flat index of its chain's head (the member with prev == -1), age[t][k] = the number
+ *             of members before it in the chain; both 0 for a dead row.
+ * Limits: H, W 1 .. 16,384; K 1 .. 128; d 1 .. 8; N * K <= 2^31 - 2; N == 0 and N == 1 succeed.
+ * spnet_track_area     writes (not accumulates) area int32 [N][K].
+ * spnet_track_overlap  the pairs (t, t + d) for t = t0 .. t0 + n_pairs - 1, which must all lie in 0 .. N-1; writes (not
+ *                      accumulates) inter int32 [n_pairs][K][K].  Integer sums: the result does not depend on the grid.
+ * spnet_track_link     one pass over that range with inter and area as the two calls above wrote them: next and prev int32
+ *                      [N][K] (the caller fills them with -1 before the first pass) are read and updated.  A count is used
+ *                      only where 0 < inter <= min(area_i, area_j), which every true count satisfies.
+ * spnet_track_rank     track and age int32 [N][K] from prev by pointer jumping between two halves of ws
+ *                      (spnet_track_rank_ws(N, K) bytes, 4-byte aligned; -1 for sizes outside the limits): 2 +
+ *                      ceil(log2(max(N, 2))) launches, a function of N alone; no readback, no workgroup waits for another.
+ *                      A prev entry is followed only where it points into an earlier frame; any other value is a head.
+ * All write every element of their outputs.  hipErrorInvalidValue, and nothing launched or written, for a NULL pointer, a
+ * size, d, iou_q or range outside these limits, rows not 8-byte aligned, any int32 array not 4-byte aligned.  No value in
+ * rows, count, inter, area, next or prev causes an access outside the arrays. */
+int spnet_track_area(const double* rows, const int* count, int N, int K, int H, int W, int* area, void* stream);
+int spnet_track_overlap(const double* rows, const int* count, int N, int K, int H, int W, int t0, int n_pairs, int d,
+                        int* inter, void* stream);
+int spnet_track_link(const int* inter, const int* area, const double* rows, const int* count, int N, int K, int t0,
+                     int n_pairs, int d, int iou_q, int* next, int* prev, void* stream);
+long spnet_track_rank_ws(int N, int K);
+int spnet_track_rank(const int* prev, const double* rows, const int* count, int N, int K, int* track, int* age, void* ws,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

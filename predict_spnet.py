@@ -18,7 +18,7 @@ default_image_dir = '/home/shawley/datasets/zooniverse_steelpan/'
 def predict_network(weights_file="spnet.model", datapath=default_image_dir, fraction=1.0, log_dir='logs/Predicting/',
                     batch_size=16, model=None, X_pred='', u8_frames=False, device_resize=False, device_png=False,
                     device_decode=False, device_overlay=False, device_png_lz=False, device_jpeg=False, jpeg_quality=90,
-                    movie=None, movie_fps=5.0, movie_in=None):
+                    movie=None, movie_fps=5.0, movie_in=None, tracks=None, track_iou=0.25, track_gap=1, track_min_len=3):
     img_file_list = []
     resize = False
     frames = None
@@ -102,6 +102,18 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
                            "device" if device_png else "host", jpeg_quality=jpeg_quality, movie=movie, movie_fps=movie_fps,
                            draw="device" if device_overlay else "host", device_decode=bool(device_decode and device_overlay),
                            frames=frames)
+    if tracks is not None and img_file_list:
+        # (additive) link the predicted ellipses through time on the GPU: file order (-d, sorted) or frame order (movie_in)
+        # is time order.  The grids go up once; the rows are formed, linked and ranked there (spnet_amd/tracks.py)
+        import os
+        from spnet_amd import tracks as TK
+        from spnet.utils import orig_img_dims
+        names = [os.path.basename(f) for f in img_file_list[:m]]
+        rows, track, age = TK.tracks_from_predictions(Yp[:len(names)], orig_img_dims[1], orig_img_dims[0], iou=track_iou,
+                                                      max_gap=track_gap)[:3]
+        table, summary = TK.write_tracks(tracks, rows, track, age, names, min_len=track_min_len)
+        print(f"    Tracks: {len(summary)} of at least {track_min_len} frames, {len(table)} detections -> {tracks}, "
+              f"{TK.summary_path(tracks)}")
     return model
 
 
@@ -144,11 +156,25 @@ if __name__ == '__main__':
     p.add_argument('--movie', default=None, metavar='PATH',
                    help="(additive) also append every overlay, in order, to a Motion-JPEG AVI at PATH (encoded on the GPU)")
     p.add_argument('--movie_fps', type=float, default=5.0, help="frames per second of --movie")
+    p.add_argument('--tracks', default=None, metavar='PATH.csv',
+                   help="(additive) link the predicted ellipses from frame to frame on the GPU (sorted file order of -d, or "
+                        "the frame order of --movie_in, is time order) and write one row per tracked detection to PATH.csv "
+                        "and one row per track -- frames, length, mean and maximal ring count -- to PATH_summary.csv")
+    p.add_argument('--track_iou', type=float, default=0.25,
+                   help="least intersection over union of two ellipses' pixel sets for a link, applied in 1/1024 (a choice, "
+                        "not a measurement)")
+    p.add_argument('--track_gap', type=int, default=1,
+                   help="link across up to this many frames, 1 .. 8: 2 bridges one missed detection (a choice, not a "
+                        "measurement)")
+    p.add_argument('--track_min_len', type=int, default=3,
+                   help="leave tracks with fewer detections out of the two tables (a choice, not a measurement)")
     args = p.parse_args()
     if args.device_jpeg and (args.device_png or args.device_png_lz):
         p.error("--device_jpeg writes .jpg files: not with --device_png / --device_png_lz")
     if not 1 <= args.jpeg_quality <= 100:
         p.error("--jpeg_quality is 1 .. 100")
+    if not 1 <= args.track_gap <= 8 or args.track_min_len < 1:
+        p.error("--track_gap is 1 .. 8 and --track_min_len at least 1")
     for attr, val in (("model_type", args.model_type), ("loss_type", args.loss_type)):
         if val is not None:
             setattr(cf, attr, val)
@@ -156,4 +182,5 @@ if __name__ == '__main__':
                     batch_size=args.batch_size, u8_frames=args.u8_frames, device_resize=args.device_resize,
                     device_png=args.device_png, device_decode=args.device_decode, device_overlay=args.device_overlay,
                     device_png_lz=args.device_png_lz, device_jpeg=args.device_jpeg, jpeg_quality=args.jpeg_quality,
-                    movie=args.movie, movie_fps=args.movie_fps, movie_in=args.movie_in)
+                    movie=args.movie, movie_fps=args.movie_fps, movie_in=args.movie_in, tracks=args.tracks,
+                    track_iou=args.track_iou, track_gap=args.track_gap, track_min_len=args.track_min_len)

@@ -23,44 +23,9 @@
 // mask_compare_kernel: blocks (chunk, frame); integer counts per lane, wave reduction by shuffles, one LDS reduction per
 // workgroup, five integer atomics per workgroup on the frame's counts (zeroed by a memset node ahead of the launch):
 // integer sums do not depend on their order, so the result does not depend on the grid.
-#include "common.h"
+#include "mask_rule.h"        // MaskRow, quantise_row, the 128-bit inside test and the ordered cull: shared with tracks.hip
 
 namespace {
-
-constexpr int MK_TW = 64, MK_TH = 16, MK_THREADS = 256, MK_MAX_K = 128;
-constexpr int MK_SUB = 16, MK_CENTER = 8, MK_TRIG_BITS = 14;
-constexpr double MK_COORD_LIMIT = 32768.0;
-constexpr int MK_MAX_DIM = 16384;
-
-struct MaskRow {                          // one quantised row; `live` false: it paints nothing
-  int cxq, cyq, aq, bq, c, s, value;
-  int bx0, by0, bx1, by1;                 // pixel box, inclusive
-};
-
-__device__ __forceinline__ bool quantise_row(const double* __restrict__ r, MaskRow& q) {
-  const double cx = r[0], cy = r[1], a = r[2], b = r[3], ang = r[4], rings = r[5];
-  // (x - x == 0) is false for NaN and +-Inf
-  if (!((cx - cx) == 0.0 && (cy - cy) == 0.0 && (a - a) == 0.0 && (b - b) == 0.0 && (ang - ang) == 0.0 &&
-        (rings - rings) == 0.0))
-    return false;
-  if (!(fabs(cx) < MK_COORD_LIMIT && fabs(cy) < MK_COORD_LIMIT && a < MK_COORD_LIMIT && b < MK_COORD_LIMIT)) return false;
-  q.cxq = (int)rint(16.0 * cx);
-  q.cyq = (int)rint(16.0 * cy);
-  const double aqd = rint(16.0 * a), bqd = rint(16.0 * b);
-  if (!(aqd > 0.0 && bqd > 0.0)) return false;
-  q.aq = (int)aqd;
-  q.bq = (int)bqd;
-  const double rad = __dmul_rn(-ang, 3.14159265358979323846 / 180.0);
-  q.c = (int)rint(__dmul_rn(16384.0, cos(rad)));
-  q.s = (int)rint(__dmul_rn(16384.0, sin(rad)));
-  q.value = (int)fmin(fmax(trunc(__dmul_rn(10.0, rings)), 0.0), 255.0);
-  const double A = fmax(a, b);
-  const int R = (int)ceil(A) + 1 + (A > 16384.0 ? 1 : 0);
-  const int fx = (int)floor(cx), fy = (int)floor(cy);
-  q.bx0 = fx - R; q.bx1 = fx + R;
-  q.by0 = fy - R; q.by1 = fy + R;
-  return true;
-}
 
 __global__ __launch_bounds__(MK_THREADS) void ring_masks_kernel(const double* __restrict__ rows, const int* __restrict__ count,
                                                                 int b_base, int K, int H, int W,
@@ -73,52 +38,21 @@ __global__ __launch_bounds__(MK_THREADS) void ring_masks_kernel(const double* __
   const long n = (long)b_base + blockIdx.z;
   const int x0 = blockIdx.x * MK_TW, y0 = blockIdx.y * MK_TH;
   const int x1 = min(x0 + MK_TW, W), y1 = min(y0 + MK_TH, H);
-  const int tid = threadIdx.x, lane = tid & (SPNET_WAVE - 1), wave = tid / SPNET_WAVE;
+  const int tid = threadIdx.x;
   const int px = x0 + (tid & 15) * 4, py = y0 + (tid >> 4);
   const int cnt = min(max(count[n], 0), K);
 
   // ---- quantise and cull, keeping the rows' order
-  bool hit = false;
-  if (tid < cnt) {
-    MaskRow q;
-    if (quantise_row(rows + (n * K + tid) * 6, q)) {
-      hit = q.bx0 < x1 && q.bx1 >= x0 && q.by0 < y1 && q.by1 >= y0;
-      if (hit) s_row[tid] = q;
-    }
-  }
-  const unsigned long long ball = __ballot(hit);
-  if (lane == 0) s_wave[wave] = __popcll(ball);
-  __syncthreads();
-  int before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < MK_THREADS / SPNET_WAVE; ++w) {
-    const int c = s_wave[w];
-    before += (w < wave) ? c : 0;
-    total += c;
-  }
-  if (hit) s_list[before + __popcll(ball & ((1ull << lane) - 1ull))] = tid;
-  __syncthreads();
+  const int total = mask_cull_rows(rows + n * K * 6, cnt, x0, y0, x1, y1, s_row, s_list, s_wave);
 
   // ---- paint: every lane walks the list in order over its 4 pixels
   unsigned pix = 0;                                                     // pixel px + i in byte i
-  const long long cyc = (long long)py * MK_SUB + MK_CENTER, cxc = (long long)px * MK_SUB + MK_CENTER;
   for (int i = 0; i < total; ++i) {
     const MaskRow& q = s_row[s_list[i]];
-    if (py < q.by0 || py > q.by1 || px + 3 < q.bx0 || px > q.bx1) continue;
-    const long long dy = cyc - q.cyq, dx0 = cxc - q.cxq;
-    const long long c = q.c, s = q.s, aq = q.aq, bq = q.bq;
-    const long long rr = (aq * bq) << MK_TRIG_BITS;
-    const unsigned __int128 rhs = (unsigned __int128)(unsigned long long)rr * (unsigned long long)rr;
-    long long u = dx0 * c + dy * s, v = dy * c - dx0 * s;
+    const unsigned in = mask_inside4(q, px, py);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long P = u * bq, Q = v * aq;
-      const unsigned long long Pa = (unsigned long long)(P < 0 ? -P : P), Qa = (unsigned long long)(Q < 0 ? -Q : Q);
-      const unsigned __int128 lhs = (unsigned __int128)Pa * Pa + (unsigned __int128)Qa * Qa;
-      if (lhs <= rhs) pix = (pix & ~(255u << (8 * j))) | (unsigned)q.value << (8 * j);
-      u += MK_SUB * c;
-      v -= MK_SUB * s;
-    }
+    for (int j = 0; j < 4; ++j)
+      if (in >> j & 1u) pix = (pix & ~(255u << (8 * j))) | (unsigned)q.value << (8 * j);
   }
 
   // ---- store
@@ -197,7 +131,6 @@ __global__ __launch_bounds__(MC_THREADS) void mask_compare_kernel(const unsigned
 
 extern "C" int spnet_ring_masks(const double* rows, const int* count, int B, int K, int H, int W, unsigned char* out,
                                 void* stream) {
-  static_assert(sizeof(MaskRow) == 44, "eleven ints a row");
   if (!rows || !count || !out || B < 0 || K < 1 || K > MK_MAX_K || H < 1 || W < 1 || H > MK_MAX_DIM || W > MK_MAX_DIM ||
       ((uintptr_t)rows & 7) || ((uintptr_t)count & 3))
     return (int)hipErrorInvalidValue;

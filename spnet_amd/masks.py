@@ -79,18 +79,20 @@ def row_box(row):
     return fx - R, fy - R, fx + R, fy + R
 
 
-def _paint_row_host(mask, row, use_box=True):
-    q = quantise_row(row)
+def _inside_row_host(row, H, W, use_box=True, q=None):
+    """The pixels of an H x W frame inside one row, as (x0, y0, bool [h, w]): the window's corner and the test on every
+    pixel of the window (the row's box cut to the frame; the whole frame without use_box).  None where the row paints
+    nothing or its window is empty.  q: quantise_row(row), if the caller has it."""
+    q = quantise_row(row) if q is None else q
     if q is None:
-        return
-    cxq, cyq, aq, bq, c, s, value = q
-    H, W = mask.shape
+        return None
+    cxq, cyq, aq, bq, c, s, _ = q
     x0, y0, x1, y1 = 0, 0, W - 1, H - 1
     if use_box:
         bx0, by0, bx1, by1 = row_box(row)
         x0, y0, x1, y1 = max(x0, bx0), max(y0, by0), min(x1, bx1), min(y1, by1)
     if x1 < x0 or y1 < y0:
-        return
+        return None
     dx = (SUBPIXEL * np.arange(x0, x1 + 1, dtype=np.int64) + CENTER - cxq)[None, :]
     dy = (SUBPIXEL * np.arange(y0, y1 + 1, dtype=np.int64) + CENTER - cyq)[:, None]
     P = (dx * c + dy * s) * bq                                # |.| < 2^54: exact in int64
@@ -102,7 +104,16 @@ def _paint_row_host(mask, row, use_box=True):
     RR = R * R
     for j, i in zip(*np.nonzero(np.abs(level - 1.0) <= 1e-9)):
         inside[j, i] = int(P[j, i]) ** 2 + int(Q[j, i]) ** 2 <= RR
-    mask[y0:y1 + 1, x0:x1 + 1][inside] = value
+    return x0, y0, inside
+
+
+def _paint_row_host(mask, row, use_box=True):
+    q = quantise_row(row)
+    win = _inside_row_host(row, mask.shape[0], mask.shape[1], use_box, q)
+    if win is None:
+        return
+    x0, y0, inside = win
+    mask[y0:y0 + inside.shape[0], x0:x0 + inside.shape[1]][inside] = q[6]
 
 
 def _host_rows(rows, count=None):

@@ -17,7 +17,8 @@ PNGs are encoded from HBM by spnet_amd.png instead of copied out for Pillow: the
 the device from the parameter arrays the frames were rasterised from, or from the label rows with --host_params; the
 loaders glob X/*.png only and do not see the sub-directory).  Without a GPU the script stops, as before; only --masks
 then still runs, on the host generator's frames (fake_espi.generate, the reference-ordered stream) and the host mask rule,
-and says so.
+and says so.  --strike S --strike_frames T [--strike_jitter J] [--movie]: instead of a data set, S movies of T frames with
+known tracks (gen_strike below), for predict_spnet.py --tracks --track_truth.
 
 The PNGs are encoded (by default) and written by at most 16 threads of this process; nothing is forked once the GPU is
 initialised."""
@@ -135,6 +136,51 @@ def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_ran
     return labels
 
 
+def gen_strike(datapath=".", sequences=1, frames=64, jitter=0, seed=0, count_range=(1, 7), device="cuda:0", threads=None,
+               device_png=False, device_png_lz=False, movie=False, movie_fps=5.0):
+    """Strike movies with known tracks (spnet_amd.fake_espi.generate_strike_device): for sequence s the directory
+    datapath/strike_NNNN with steelpan_NNNNNNN.png + .csv per frame in time order -- the loaders' own format -- and
+    truth_tracks.csv (spnet_amd.tracks.write_truth_tracks: `track` is the identity, `age` the frames since it first
+    appeared); movie: also datapath/strike_NNNN.avi, the frames as a grey Motion-JPEG movie encoded on the GPU.  Returns per
+    sequence the truth table."""
+    import torch
+    from spnet_amd import fake_espi as F
+    from spnet_amd import tracks as TK
+    if not torch.cuda.is_available():
+        raise RuntimeError("gen_fake_espi: the frames are generated on the GPU (no CPU fallback)")
+    device_png = device_png or device_png_lz
+    S, T = int(sequences), int(frames)
+    threads = threads or min(16, os.cpu_count() or 1)
+    tables = []
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        for s in range(S):
+            root = os.path.join(datapath, "strike_" + str(s).zfill(4))
+            os.makedirs(root, exist_ok=True)
+            _, (rows_d, count_d), ident_d, U = F.generate_strike_device(1, T, seed, jitter, first_sequence=s,
+                                                                        count_range=count_range, device=device, want_u8=True)
+            rows, count, ident = rows_d.cpu().numpy(), count_d.cpu().numpy(), ident_d.cpu().numpy()
+            labels = [[tuple(r) for r in rows[t, :count[t]].astype(np.int64).tolist()] for t in range(T)]
+            stems = [os.path.join(root, "steelpan_" + str(t).zfill(7)) for t in range(T)]
+            if device_png:
+                from spnet_amd.png import write_png_device
+                write_png_device(U, [st + ".png" for st in stems], pool=pool, lz77=device_png_lz)
+                jobs = [pool.submit(_write_csv, st, r) for st, r in zip(stems, labels)]
+            else:
+                host = U.cpu().numpy()
+                jobs = [pool.submit(_write_pair, st, host[t], labels[t]) for t, st in enumerate(stems)]
+            for j in jobs:
+                j.result()
+            tables.append(TK.write_truth_tracks(os.path.join(root, "truth_tracks.csv"), rows, ident,
+                                                [os.path.basename(st) + ".png" for st in stems]))
+            if movie:
+                from spnet_amd.jpeg import MjpegWriter
+                with MjpegWriter(root + ".avi", F.IM_W, F.IM_H, fps=movie_fps, channels=1) as w:
+                    w.add(U)
+            print("   wrote sequence %d of %d: %d frames, %d identities -> %s" % (s, S, T, len({r[2] for r in tables[-1]}), root),
+                  flush=True)
+    return tables
+
+
 def _gen_dataset_host(datapath, n, sub, seed, count_range, bp_real, device_png):
     """gen_dataset(masks=True) on a machine without a GPU: the host generator's frames (fake_espi.generate: the
     reference-ordered parameter stream, Pillow's rasteriser -- other pixels than the device's) and the host mask rule."""
@@ -173,7 +219,24 @@ def main(argv=None):
     p.add_argument('--masks', action='store_true',
                    help="(additive) also write X/masks/steelpan_NNNNNNN.png, the frame's ring-count segmentation mask: "
                         "trunc(10 * rings) inside every ellipse, 0 outside")
+    p.add_argument('--strike', type=int, default=None, metavar='S',
+                   help="(additive, instead of -n / -a) write S strike movies with known tracks: DIR/strike_NNNN/ with the "
+                        "frames in time order and truth_tracks.csv -- the struck note rings at once, the sympathetic notes "
+                        "ramp up after an onset of their own")
+    p.add_argument('--strike_frames', type=int, default=64, metavar='T', help="frames of a strike movie, 1 .. 4096")
+    p.add_argument('--strike_jitter', type=int, default=0, metavar='J',
+                   help="the centres move by up to J whole pixels from frame to frame, 0 .. 8")
+    p.add_argument('--movie', action='store_true', help="(with --strike) also DIR/strike_NNNN.avi, Motion-JPEG encoded on the GPU")
     args = p.parse_args(argv)
+    if args.strike is not None:
+        if args.strike < 0 or not 1 <= args.strike_frames <= 4096 or not 0 <= args.strike_jitter <= 8:
+            p.error("--strike is at least 0, --strike_frames 1 .. 4096 and --strike_jitter 0 .. 8")
+        if args.bp_real or args.bp_path or args.host_params or args.masks or args.all:
+            p.error("--strike combines with --seed, --count_range, --device_png, --device_png_lz and --movie only")
+        return gen_strike(args.datapath, args.strike, args.strike_frames, args.strike_jitter, args.seed, tuple(args.count_range),
+                          device_png=args.device_png, device_png_lz=args.device_png_lz, movie=args.movie)
+    if args.movie:
+        p.error("--movie goes with --strike")
     gen_dataset(datapath=args.datapath, numframes=args.numframes, everything=args.all, seed=args.seed,
                 count_range=tuple(args.count_range), bp_real=args.bp_real, bp_path=args.bp_path, host_params=args.host_params,
                 device_png=args.device_png, device_png_lz=args.device_png_lz, masks=args.masks)

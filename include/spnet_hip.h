@@ -589,6 +589,32 @@ int spnet_fake_espi(const float* waves, const float* nodes, const int* nnode, in
  *   The first passing try is accepted; its ring count is min(rings drawn at t = 0, b_s / 4 of every try s <= t). */
 int spnet_fake_espi_params(long first_frame, int N, int H, int W, unsigned seed, int count_lo, int count_hi,
                            const float* trig2, float* waves, float* nodes, int* nnode, int* tries, void* stream);
+/* Strike sequences (csrc/espi_strike.hip): a movie with KNOWN identities and ring-count curves.  A sequence
+ * is one set of frame-0 parameters -- waves0 [S][5], nodes0 [S][7][8], nnode0 [S] as spnet_fake_espi_params writes them,
+ * row s for the GLOBAL sequence first_sequence + s -- evolved over T frames.  Writes (every element) waves [S*T][5],
+ * nodes [S*T][7][8], nnode [S*T] in the layout spnet_fake_espi reads, and ident int32 [S*T][7]; frame s * T + t is time
+ * step t of sequence s.  Integer and stateless: slot (s, t, j) is a function of (seed, first_sequence + s, t, j) and the
+ * base row alone, one thread per slot; a frame does not depend on S or on how a range of sequences is split into calls.
+ *   mix, u(key, k), randint as for spnet_fake_espi_params above (csrc/counter_rng.h)
+ *   skey(g) = mix(mix(mix(seed ^ 0x51ed270b) + low32(g)) ^ high32(g)), g = first_sequence + s
+ *   key(slot, t) = mix(skey + (slot << 12 | t)): slot 0 with t = j = the envelope draws of antinode j, slot j + 1 = the
+ *     jitter draws of antinode j at time t
+ *   base slot j is VALID iff j < clamp(nnode0[s], 0, 7) and its column 7 is not 0; the first valid slot is the STRUCK
+ *     note: onset 0, rise 0.  Every other valid slot is sympathetic: k 0 onset [0, T/2]; k 1 rise [1, max(T/4, 1)].  All:
+ *     k 2 hold [0, T/4]; k 3 decay [1, T]  (integer divisions)
+ *   envelope e(t) in 0 .. 256, peak = onset + rise, after = peak + hold + 1: 0 for t < onset;
+ *     256 (t - onset + 1) / (rise + 1) for t < peak; 256 for t < after; max(256 - 256 (t - after + 1) / (decay + 1), 0)
+ *     from then on (integer divisions).  It rises, holds and falls: unimodal
+ *   rings(t) = (R e(t) + 128) >> 8 with R = the base row's ring count clamped to 0 .. 255; the antinode is PRESENT at t
+ *     iff rings(t) >= 1 -- one contiguous run of frames
+ *   present: cx = cx0 + randint(u(key(j + 1, t), 0), -J, J), cy = cy0 + randint(u(.., 1), -J, J) (whole numbers added to
+ *     whole numbers: exact floats); axes, angle and start are the base row's; column 5 = rings(t); valid = 1;
+ *     ident = 1 + 7 g + j.  absent: the slot's eight floats are 0 (valid = 0: the rasteriser skips it) and ident = 0
+ *   waves are the base row's; nnode = clamp(nnode0[s], 0, 7) in every frame
+ * S == 0: nothing to do, success.  hipErrorInvalidValue (nothing launched): a NULL pointer, S < 0, first_sequence < 0, T
+ * outside 1 .. 4096, J outside 0 .. 8, S * T > 2^31 - 1, 7 (first_sequence + S) > 2^31 - 2. */
+int spnet_fake_espi_strike(const float* waves0, const float* nodes0, const int* nnode0, long first_sequence, int S, int T,
+                           unsigned seed, int J, float* waves, float* nodes, int* nnode, int* ident, void* stream);
 
 /* ---- band-pass mix-up (spnet/augmentation.py:10-62; csrc/bandpass.hip) ------------------------------------------- */
 /* Frames x [*][H][W], one channel, 16 <= H, W <= 2048; x_kind 0 = uint8, 1 = fp32 pixel units (0..255), 2 = fp32 network
@@ -1012,6 +1038,45 @@ int spnet_track_link(const int* inter, const int* area, const double* rows, cons
 long spnet_track_rank_ws(int N, int K);
 int spnet_track_rank(const int* prev, const double* rows, const int* count, int N, int K, int* track, int* age, void* ws,
                      void* stream);
+
+/* ---- Tracking score (csrc/track_score.hip, csrc/track_score_core.h, csrc/track_tile.h): predicted tracks against
+ *      ground-truth identities.  spnet_amd/tracks.py holds the same rule in numpy; DESIGN.md 5j ------------------------- */
+/* THE RULE, in the vocabulary of "Antinode tracks" above.  Truth: rows_t double [N][Kt][6], count_t int32 [N], ident int32
+ * [N][Kt]; prediction: rows_p [N][Kp][6], count_p [N], track int32 [N][Kp] as spnet_track_rank wrote it; frame n of one
+ * is frame n of the other.
+ *   Live, pixel set, Eligible, Better: the track rule's, word for word.
+ *   Identity  eff(n, i) = ident[n][i] where truth row (n, i) is live, 1 <= ident <= M and no live row i' < i of the frame
+ *             holds the same ident; 0 otherwise.  So an ident of 0, below 0 or above M is no identity, and where an
+ *             identity appears twice in a frame the LOWER INDEX counts and the other row has no identity.
+ *   Open      a truth row is open iff eff > 0; a predicted row is open iff it is live and track > 0.
+ *   Match     inter[i][j] = |S_t(n, i) ^ S_p(n, j)|.  i <-> j are matched iff j is the best eligible open predicted row for
+ *             i AND i is the best eligible open truth row for j (the lower index winning a tie on either side).
+ *             match[n][i] = j, -1 where there is none; frame_counts[n] = (tp, fn, fp) = (matches, open truth rows - tp,
+ *             open predicted rows - tp).
+ *   Identity statistics, for g = 1 .. M over the frames in which some row has eff == g, in time order:
+ *             present = their number; matched = those with match >= 0; switches = the matched frames whose predicted track
+ *             differs from that of g's previous matched frame (the CLEAR-MOT identity switch); fragments = the matched
+ *             frames that follow an unmatched present frame after an earlier matched one; first_matched_frame, -1 for none.
+ *             ident_stats int32 [M + 1][5] in this order, row 0 zeroed.
+ * Limits: those of the track rule for (N, Kt) and (N, Kp), N * Kt * Kp <= 2^31 - 2 for spnet_track_match (the caller takes a
+ * movie a range of frames at a time: frames are independent), M 1 .. 65,536, iou_q 1 .. 1024.
+ * spnet_track_match  ws: spnet_track_match_ws(N, Kt, Kp) bytes, 4-byte aligned (-1 for sizes outside the limits): inter
+ *                    and both areas.  Areas by spnet_track_area, one workgroup per (frame, 64 x 16 tile) for inter, one
+ *                    per frame for the mutual-best step; integer sums, so the result does not depend on the grid.
+ * spnet_track_ident  match as spnet_track_match wrote it (an entry outside 0 .. Kp-1 counts as unmatched).  ws:
+ *                    spnet_track_ident_ws(N, Kt, M) bytes, 4-byte aligned.  One workgroup per frame records eff and the
+ *                    first and last frame of every identity; then one lane per identity walks its own frames.
+ * Both write every element of their outputs, without a readback, and no workgroup waits for another; N == 0 succeeds
+ * (spnet_track_ident then writes the statistics of identities that are never present).  hipErrorInvalidValue, and nothing
+ * launched or written, for a NULL pointer, a size, M or iou_q outside these limits, rows not 8-byte aligned, any int32 array
+ * or ws not 4-byte aligned.  No value in rows, count, ident, track or match causes an access outside the arrays. */
+long spnet_track_match_ws(int N, int Kt, int Kp);
+int spnet_track_match(const double* rows_t, const int* count_t, const int* ident, int Kt, const double* rows_p,
+                      const int* count_p, const int* track, int Kp, int N, int H, int W, int iou_q, int M, void* ws, int* match,
+                      int* frame_counts, void* stream);
+long spnet_track_ident_ws(int N, int Kt, int M);
+int spnet_track_ident(const double* rows_t, const int* count_t, const int* ident, const int* match, const int* track, int N,
+                      int Kt, int Kp, int M, void* ws, int* ident_stats, void* stream);
 
 #ifdef __cplusplus
 }

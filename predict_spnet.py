@@ -18,7 +18,8 @@ default_image_dir = '/home/shawley/datasets/zooniverse_steelpan/'
 def predict_network(weights_file="spnet.model", datapath=default_image_dir, fraction=1.0, log_dir='logs/Predicting/',
                     batch_size=16, model=None, X_pred='', u8_frames=False, device_resize=False, device_png=False,
                     device_decode=False, device_overlay=False, device_png_lz=False, device_jpeg=False, jpeg_quality=90,
-                    movie=None, movie_fps=5.0, movie_in=None, tracks=None, track_iou=0.25, track_gap=1, track_min_len=3):
+                    movie=None, movie_fps=5.0, movie_in=None, tracks=None, track_iou=0.25, track_gap=1, track_min_len=3,
+                    track_truth=None):
     img_file_list = []
     resize = False
     frames = None
@@ -114,6 +115,28 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
         table, summary = TK.write_tracks(tracks, rows, track, age, names, min_len=track_min_len)
         print(f"    Tracks: {len(summary)} of at least {track_min_len} frames, {len(table)} detections -> {tracks}, "
               f"{TK.summary_path(tracks)}")
+        if track_truth is not None:
+            # (additive) score the tracks just linked against ground-truth identities (gen_fake_espi.py --strike writes
+            # them): joined by file name, or by frame index for a movie; matched and counted on the GPU
+            import torch
+            truth = TK.read_truth_tracks(track_truth)
+            if movie_in is not None:
+                kept = [r for r in truth if r[0] < len(names)]
+                rows_t, count_t, ident = TK.truth_arrays(kept, n_frames=len(names))
+            else:       # the loader rounds the frames down to whole batches: truth of frames that were not loaded is left out
+                known = set(names)
+                kept = [r for r in truth if os.path.basename(r[1]) in known]
+                rows_t, count_t, ident = TK.truth_arrays(truth, names=names, skip_unknown=True)
+            if len(kept) < len(truth):
+                print(f"    Track score: {len(truth) - len(kept)} truth rows belong to frames that were not predicted "
+                      f"(the frames are rounded down to whole batches of {batch_size}) and are left out")
+            dev = rows.device
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            got = TK.score_tracks_device(up(rows_t), up(count_t), up(ident), rows, None, track, orig_img_dims[1],
+                                         orig_img_dims[0], iou=track_iou)
+            score = TK.track_score(*got, rows_t, rows, ident=ident, count_t=count_t)
+            TK.write_track_score(TK.score_path(tracks), score, got[2])
+            print(f"    Track score against {track_truth}: {score} -> {TK.score_path(tracks)}")
     return model
 
 
@@ -168,7 +191,13 @@ if __name__ == '__main__':
                         "measurement)")
     p.add_argument('--track_min_len', type=int, default=3,
                    help="leave tracks with fewer detections out of the two tables (a choice, not a measurement)")
+    p.add_argument('--track_truth', default=None, metavar='TRUTH.csv',
+                   help="(additive, with --tracks) score the linked tracks against the ground-truth identities of a "
+                        "truth_tracks.csv (gen_fake_espi.py --strike): frames joined by file name, or by index with "
+                        "--movie_in; prints the score and writes it to PATH_score.csv and PATH_score_idents.csv")
     args = p.parse_args()
+    if args.track_truth is not None and args.tracks is None:
+        p.error("--track_truth scores the tracks of --tracks PATH.csv: give both")
     if args.device_jpeg and (args.device_png or args.device_png_lz):
         p.error("--device_jpeg writes .jpg files: not with --device_png / --device_png_lz")
     if not 1 <= args.jpeg_quality <= 100:
@@ -183,4 +212,5 @@ if __name__ == '__main__':
                     device_png=args.device_png, device_decode=args.device_decode, device_overlay=args.device_overlay,
                     device_png_lz=args.device_png_lz, device_jpeg=args.device_jpeg, jpeg_quality=args.jpeg_quality,
                     movie=args.movie, movie_fps=args.movie_fps, movie_in=args.movie_in, tracks=args.tracks,
-                    track_iou=args.track_iou, track_gap=args.track_gap, track_min_len=args.track_min_len)
+                    track_iou=args.track_iou, track_gap=args.track_gap, track_min_len=args.track_min_len,
+                    track_truth=args.track_truth)

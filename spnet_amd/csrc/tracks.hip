@@ -7,13 +7,11 @@
 // LDS list; a lane counts its 4 pixels inside every listed row into an LDS counter per row, and the nonzero counters are
 // added to area[t][k] with one global atomic each.  area is zeroed by a memset node ahead of the launch.
 //
-// track_overlap_kernel (the hot path): one workgroup per (frame pair, 64 x 16 tile).  BOTH frames' rows are culled into two
-// ordered LDS lists; a tile that either list leaves empty ends there.  A lane first collects, per pixel, a 128-bit set of
-// the positions in list B whose rows contain the pixel, then walks list A: for a pixel inside row A[i] it adds 1 to
-// table[i][j] for every j of the pixel's set.  The table is uint16 [128][128] in LDS (a tile has 1,024 pixels), two
-// counters to a 32-bit word, so an LDS atomicAdd of 1 or 1 << 16 cannot carry from one counter into the next.  The nonzero
-// entries of the first nA x nB corner go to inter[pair][i][j] by global integer atomics.  Integer sums do not depend on
-// their order: the result does not depend on the grid or on the order of arrival.
+// track_overlap_kernel (the hot path): one workgroup per (frame pair, 64 x 16 tile).  The tile body and its LDS pair table
+// are track_tile.h's, which csrc/track_score.hip compiles too: both frames' rows culled into two ordered LDS lists, a
+// 128-bit set of list-B positions per pixel, uint16 LDS counters, and the nonzero counts added to inter[pair][i][j] by
+// global integer atomics.  Integer sums do not depend on their order: the result does not depend on the grid or on the
+// order of arrival.
 //
 // track_link_kernel: one workgroup per frame pair, threads 0 .. K-1 for the detections of frame t, 128 .. 128+K-1 for those
 // of frame t + d (tracks_core.h: every lane chooses its best, a barrier, then the mutual test).  The workgroup of pair
@@ -24,20 +22,12 @@
 //
 // Bounds: count is clamped to 0 .. K; list positions are < K <= 128; pixels beyond W or H are masked out of every count;
 // next and prev are only compared with -1 by the link step; prev is range-checked by rank_init before it is an address.
-#include "mask_rule.h"
+#include "track_tile.h"
 #include "tracks_core.h"
 
 namespace {
 
-constexpr int TR_THREADS = MK_THREADS;
 static_assert(tracks::MAX_K == MK_MAX_K && tracks::MAX_DIM == MK_MAX_DIM, "one set of limits");
-
-// Bits of the lane's 4 pixels that lie inside the frame.
-__device__ __forceinline__ unsigned valid4(int px, int py, int x1, int y1) {
-  if (py >= y1) return 0u;
-  const int n = x1 - px;
-  return n >= 4 ? 15u : n <= 0 ? 0u : (1u << n) - 1u;
-}
 
 __global__ __launch_bounds__(TR_THREADS) void track_area_kernel(const double* __restrict__ rows, const int* __restrict__ count,
                                                                 int n_base, int K, int H, int W, int tiles_x,
@@ -73,73 +63,11 @@ __global__ __launch_bounds__(TR_THREADS) void track_area_kernel(const double* __
 __global__ __launch_bounds__(TR_THREADS) void track_overlap_kernel(const double* __restrict__ rows, const int* __restrict__ count,
                                                                    int K, int H, int W, int tiles_x, long t0, int pair_base,
                                                                    int d, int* __restrict__ inter) {
-  __shared__ MaskRow s_row[2][MK_MAX_K];
-  __shared__ int s_list[2][MK_MAX_K];
-  __shared__ int s_wave[TR_THREADS / SPNET_WAVE];
-  __shared__ unsigned s_table[MK_MAX_K][MK_MAX_K / 2];                  // uint16 counters [i][j], j and j + 1 share a word
-
+  __shared__ TrackTileLds s;
   const long pair = (long)pair_base + blockIdx.y;
   const long ta = t0 + pair, tb = ta + d;
-  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-  const int x0 = tx * MK_TW, y0 = ty * MK_TH;
-  const int x1 = min(x0 + MK_TW, W), y1 = min(y0 + MK_TH, H);
-  const int tid = threadIdx.x;
-  const int px = x0 + (tid & 15) * 4, py = y0 + (tid >> 4);
-
-  const int nA = mask_cull_rows(rows + ta * K * 6, min(max(count[ta], 0), K), x0, y0, x1, y1, s_row[0], s_list[0], s_wave);
-  if (nA == 0) return;                                                  // uniform over the workgroup
-  const int nB = mask_cull_rows(rows + tb * K * 6, min(max(count[tb], 0), K), x0, y0, x1, y1, s_row[1], s_list[1], s_wave);
-  if (nB == 0) return;
-
-  for (int w = tid; w < nA * (MK_MAX_K / 2); w += TR_THREADS) (&s_table[0][0])[w] = 0u;
-  __syncthreads();
-
-  // ---- per pixel: the set of list-B positions whose rows contain it
-  const unsigned ok = valid4(px, py, x1, y1);
-  unsigned long long setB[2][4] = {{0ull, 0ull, 0ull, 0ull}, {0ull, 0ull, 0ull, 0ull}};   // [half][pixel]: registers
-  unsigned any = 0u;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int jn = min(nB - 64 * h, 64);
-    for (int j = 0; j < jn; ++j) {
-      const unsigned in = mask_inside4(s_row[1][s_list[1][64 * h + j]], px, py) & ok;
-      any |= in;
-      const unsigned long long bit = 1ull << j;
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        if (in >> p & 1u) setB[h][p] |= bit;
-    }
-  }
-
-  // ---- list A: count the pairs
-  if (any) {
-    for (int i = 0; i < nA; ++i) {
-      const unsigned in = mask_inside4(s_row[0][s_list[0][i]], px, py) & any;
-      if (!in) continue;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        if (!(in >> p & 1u)) continue;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          unsigned long long m = setB[h][p];
-          while (m) {
-            const int j = 64 * h + __ffsll((long long)m) - 1;
-            m &= m - 1ull;
-            atomicAdd(&s_table[i][j >> 1], 1u << (16 * (j & 1)));
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-
-  // ---- the nonzero counts of the nA x nB corner
-  int* out = inter + pair * K * K;
-  for (int e = tid; e < nA * nB; e += TR_THREADS) {
-    const int i = e / nB, j = e - i * nB;
-    const unsigned c = (s_table[i][j >> 1] >> (16 * (j & 1))) & 0xffffu;
-    if (c) atomicAdd(out + (long)s_list[0][i] * K + s_list[1][j], (int)c);
-  }
+  track_tile_overlap(rows + ta * K * 6, min(max(count[ta], 0), K), rows + tb * K * 6, count + tb, K, H, W, tiles_x, (int)blockIdx.x, s,
+                     inter + pair * K * K, K);
 }
 
 __global__ __launch_bounds__(TR_THREADS) void track_link_kernel(const int* __restrict__ inter, const int* __restrict__ area,

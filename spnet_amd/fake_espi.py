@@ -204,6 +204,141 @@ def rows_from_params(nodes, nnode):
     return nodes[..., :6].trunc().double().contiguous(), nnode.contiguous()
 
 
+# ----------------------------------------------------------------------------- strike sequences (csrc/espi_strike.hip)
+STRIKE_MAX_T, STRIKE_MAX_J, STRIKE_KEY = 4096, 8, 0x51ed270b
+
+
+def _check_strike(S, T, jitter, first_sequence):
+    if not (S >= 0 and 1 <= T <= STRIKE_MAX_T and 0 <= jitter <= STRIKE_MAX_J and first_sequence >= 0
+            and S * T <= 2 ** 31 - 1 and 7 * (first_sequence + S) <= 2 ** 31 - 2):
+        raise ValueError("strike: S >= 0, T 1 .. %d, jitter 0 .. %d, first_sequence >= 0, S * T and the identities within "
+                         "int32; got S %r, T %r, jitter %r, first_sequence %r" % (STRIKE_MAX_T, STRIKE_MAX_J, S, T, jitter,
+                                                                                   first_sequence))
+
+
+def strike_envelope(t, onset, rise, hold, decay):
+    """The envelope 0 .. 256 of the strike rule (include/spnet_hip.h "Strike sequences") on int64 arrays."""
+    peak = onset + rise
+    after = peak + hold + 1
+    e = np.where(t < peak, 256 * (t - onset + 1) // (rise + 1),
+                 np.where(t < after, 256, np.maximum(256 - 256 * (t - after + 1) // (decay + 1), 0)))
+    return np.where(t < onset, 0, e)
+
+
+def strike_params_host(waves0, nodes0, nnode0, T, seed=0, jitter=0, first_sequence=0):
+    """spnet_fake_espi_strike in numpy, bit for bit: base arrays waves0 [S,5], nodes0 [S,7,8], nnode0 [S] (frame-0
+    parameters, row s for the global sequence first_sequence + s) -> (waves float32 [S*T,5], nodes float32 [S*T,7,8], nnode
+    int32 [S*T], ident int32 [S*T,7]); frame s * T + t is time step t of sequence s."""
+    from .augmentation import _keyed_draw, _mix32
+    waves0, nodes0 = np.asarray(waves0, np.float32), np.asarray(nodes0, np.float32)
+    S, T, J = int(nodes0.shape[0]), int(T), int(jitter)
+    _check_strike(S, T, J, int(first_sequence))
+    nn = np.clip(np.asarray(nnode0, np.int64), 0, 7)
+    u64 = np.uint64
+
+    def randint(u, lo, hi):
+        return lo + ((u * u64(max(hi - lo + 1, 1))) >> u64(32)).astype(np.int64)
+
+    g = np.arange(S, dtype=np.int64) + int(first_sequence)
+    skey = _mix32(_mix32(_mix32(u64((int(seed) & 0xFFFFFFFF) ^ STRIKE_KEY)) + (g.astype(u64) & u64(0xFFFFFFFF)))
+                  ^ (g.astype(u64) >> u64(32)))
+    j = np.arange(7, dtype=np.int64)
+    valid = (j[None, :] < nn[:, None]) & (nodes0[:, :, 7] != 0)                       # [S,7]
+    struck = np.where(valid.any(1), valid.argmax(1), 7)
+    ek = _mix32(skey[:, None] + j.astype(u64)[None, :])                               # key(0, j)
+    is_struck = j[None, :] == struck[:, None]
+    onset = np.where(is_struck, 0, randint(_keyed_draw(ek, 0), 0, T // 2))
+    rise = np.where(is_struck, 0, randint(_keyed_draw(ek, 1), 1, max(T // 4, 1)))
+    hold = randint(_keyed_draw(ek, 2), 0, T // 4)
+    decay = randint(_keyed_draw(ek, 3), 1, T)
+    with np.errstate(invalid="ignore"):
+        R = np.where(nodes0[:, :, 5] == nodes0[:, :, 5], np.clip(nodes0[:, :, 5], 0, 255), 0).astype(np.int64)
+    t = np.arange(T, dtype=np.int64)[None, :, None]
+    env = strike_envelope(t, onset[:, None, :], rise[:, None, :], hold[:, None, :], decay[:, None, :])
+    rings = np.where(valid[:, None, :], (R[:, None, :] * env + 128) >> 8, 0)         # [S,T,7]
+    present = rings >= 1
+    jk = _mix32(skey[:, None, None] + (((j + 1) << 12)[None, None, :] | t).astype(u64))
+    nodes = np.zeros((S, T, 7, 8), np.float32)
+    nodes[..., 0] = nodes0[:, None, :, 0] + randint(_keyed_draw(jk, 0), -J, J).astype(np.float32)
+    nodes[..., 1] = nodes0[:, None, :, 1] + randint(_keyed_draw(jk, 1), -J, J).astype(np.float32)
+    nodes[..., 2:5] = nodes0[:, None, :, 2:5]
+    nodes[..., 5] = rings
+    nodes[..., 6] = nodes0[:, None, :, 6]
+    nodes[..., 7] = 1
+    nodes[~present] = 0
+    ident = np.where(present, 1 + 7 * g[:, None, None] + j[None, None, :], 0).astype(np.int32)
+    waves = np.repeat(waves0[:, :5], T, axis=0)
+    return (np.ascontiguousarray(waves), nodes.reshape(S * T, 7, 8), np.repeat(nn.astype(np.int32), T),
+            ident.reshape(S * T, 7))
+
+
+def strike_params_device(S, T, seed=0, jitter=0, first_sequence=0, count_range=(1, 7), device="cuda:0"):
+    """The parameters of S strike sequences of T frames (csrc/espi_strike.hip): the frame-0 parameters of the global frames
+    first_sequence .. first_sequence + S - 1 from draw_params_device, evolved on the device.  -> (waves [S*T,5], nodes
+    [S*T,7,8], nnode [S*T], ident int32 [S*T,7]) device tensors; enqueued on the current stream, nothing crosses to the
+    host.  A sequence depends on (seed, its global index) only."""
+    import torch
+    from . import _lib as L
+    S, T, J = int(S), int(T), int(jitter)
+    _check_strike(S, T, J, int(first_sequence))
+    dev = torch.device(device)
+    waves = torch.empty((S * T, 5), dtype=torch.float32, device=dev)
+    nodes = torch.empty((S * T, 7, 8), dtype=torch.float32, device=dev)
+    nnode = torch.empty((S * T,), dtype=torch.int32, device=dev)
+    ident = torch.empty((S * T, 7), dtype=torch.int32, device=dev)
+    if S == 0:                                              # empty tensors have no address to pass
+        return waves, nodes, nnode, ident
+    w0, n0, c0 = draw_params_device(S, seed, dev, count_range, first_sequence)
+    with torch.cuda.device(dev):
+        L.spnet_fake_espi_strike(w0.data_ptr(), n0.data_ptr(), c0.data_ptr(), int(first_sequence), S, T, int(seed) & 0xFFFFFFFF,
+                                 J, waves.data_ptr(), nodes.data_ptr(), nnode.data_ptr(), ident.data_ptr(),
+                                 torch.cuda.current_stream(dev).cuda_stream)
+    return waves, nodes, nnode, ident
+
+
+def strike_rows(nodes, nnode, ident):
+    """Strike parameter arrays nodes [N,7,8], nnode [N], ident [N,7] (device tensors or host arrays) -> (rows float64
+    [N,7,6], count int32 [N], ident int32 [N,7]) of the same kind in augmentation.pad_metadata's layout: the present slots
+    moved to the front in slot order with their identities, zeros behind them.  The values rows_from_params gives, for
+    parameters whose slots are no longer all at the front."""
+    if hasattr(nodes, "is_cuda"):
+        import torch
+        j = torch.arange(7, device=nodes.device)
+        valid = (nodes[..., 7] != 0) & (j[None, :] < nnode[:, None])
+        order = torch.argsort((~valid).to(torch.int32), dim=1, stable=True)
+        kept = torch.gather(valid, 1, order)
+        rows = torch.gather(nodes[..., :6].trunc().double(), 1, order[..., None].expand(-1, -1, 6)) * kept[..., None]
+        return (rows.contiguous(), valid.sum(1).to(torch.int32), (torch.gather(ident, 1, order) * kept).to(torch.int32))
+    nodes, ident = np.asarray(nodes), np.asarray(ident)
+    valid = (nodes[..., 7] != 0) & (np.arange(7)[None, :] < np.asarray(nnode)[:, None])
+    order = np.argsort(~valid, axis=1, kind="stable")
+    kept = np.take_along_axis(valid, order, 1)
+    rows = np.take_along_axis(np.trunc(nodes[..., :6]).astype(np.float64), order[..., None], 1) * kept[..., None]
+    return np.ascontiguousarray(rows), valid.sum(1).astype(np.int32), (np.take_along_axis(ident, order, 1) * kept).astype(np.int32)
+
+
+def generate_strike_device(S, T, seed=0, jitter=0, first_sequence=0, count_range=(1, 7), device="cuda:0", noise=True,
+                           want_u8=False, chunk=1024, size=None):
+    """S strike sequences of T frames rasterised in HBM: strike_params_device, then generate_device on those parameters (the
+    rasteriser, sensor model and resize unchanged).  -> (X float32 [S*T,H,W,1], (rows float64 [S*T,7,6], count int32 [S*T]),
+    ident int32 [S*T,7][, uint8 frames]) device tensors; rows and ident are strike_rows'.  The sensor noise is keyed by the
+    first FRAME, first_sequence * T, so another range of sequences gets other noise."""
+    waves, nodes, nnode, ident = strike_params_device(S, T, seed, jitter, first_sequence, count_range, device)
+    rows, count, ident = strike_rows(nodes, nnode, ident)
+    if S == 0:
+        import torch
+        from .resize import _size
+        OH, OW = (IM_H, IM_W) if size is None else _size(size)
+        X = torch.empty((0, OH, OW, 1), dtype=torch.float32, device=device)
+        U = torch.empty((0, OH, OW), dtype=torch.uint8, device=device)
+        return (X, (rows, count), ident, U) if want_u8 else (X, (rows, count), ident)
+    # labels="device" only keeps the slot-by-slot labels of generate_device off the host; they are NOT the movie's labels
+    # (absent slots are zero rows there) and are dropped: rows, count and ident above are
+    out = generate_device(S * T, seed, device, noise=noise, want_u8=want_u8, chunk=chunk, size=size,
+                          params=(waves, nodes, nnode), first_frame=int(first_sequence) * int(T), labels="device")
+    return (out[0], (rows, count), ident) + tuple(out[2:])
+
+
 def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk=1024, count_range=(1, 7),
                     bandpass_real=None, size=None, params="host", first_frame=0, labels="host", full_u8=None):
     """n frames rasterised directly in HBM (csrc/espi.hip): the SAME per-frame parameters as generate(n, seed)
@@ -220,14 +355,22 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
     by chunk, the labels read back in one copy per chunk: the same distributions, other frames, and parameters / labels /
     noise-free pixels that do not depend on `chunk`.  The sensor noise keeps its seed of (seed, chunk start) as before
     (first_frame shifts the chunk start, so that another range of frames gets other noise); first_frame needs "device".
+    params may also be the three parameter arrays themselves, (waves [n,5], nodes [n,7,8], nnode [n]) contiguous device
+    tensors (generate_strike_device): they are rasterised as they are and the labels are read from them slot by slot.
     labels: "host" (default) = the label rows as Python lists; "device" (needs params="device") = rows_from_params' pair of
     device tensors instead, and no label crosses to the host.
     full_u8 (with size; a uint8 device tensor [n,384,512]): also receives the frames at their full size, as rasterised (and
     mixed), i.e. what the resize reads."""
     import torch
     from . import _lib as L
+    given = isinstance(params, (tuple, list))
+    if given:
+        if len(params) != 3 or tuple(params[0].shape) != (n, 5) or tuple(params[1].shape) != (n, 7, 8) or \
+                tuple(params[2].shape) != (n,) or not all(a.is_cuda and a.is_contiguous() for a in params):
+            raise ValueError("generate_device: params as arrays are contiguous device tensors waves [n,5], nodes [n,7,8], nnode [n]")
+        given, params = params, "device"
     if params not in ("host", "device"):
-        raise ValueError("generate_device: params must be 'host' or 'device', got %r" % (params,))
+        raise ValueError("generate_device: params must be 'host', 'device' or three device tensors, got %r" % (params,))
     if labels not in ("host", "device") or (labels == "device" and params != "device"):
         raise ValueError("generate_device: labels must be 'host' or 'device' (which needs params='device'), got %r" % (labels,))
     if full_u8 is not None and (size is None or full_u8.dtype != torch.uint8 or tuple(full_u8.shape) != (n, IM_H, IM_W)
@@ -256,7 +399,8 @@ def generate_device(n, seed=0, device="cuda:0", noise=True, want_u8=False, chunk
     for lo in range(0, n, chunk):
         hi = min(n, lo + chunk)
         if params == "device":
-            wd, ndd, nnd = draw_params_device(hi - lo, seed, dev, count_range, first_frame + lo)
+            wd, ndd, nnd = (a[lo:hi] for a in given) if given else \
+                draw_params_device(hi - lo, seed, dev, count_range, first_frame + lo)
             if dev_labels:
                 r, c = rows_from_params(ndd, nnd)
                 rows_d[lo:hi].copy_(r)

@@ -24,6 +24,16 @@ overlap, no link); re-identification after more than max_gap frames.
   track_summary            one record per kept track: frames, length, mean and maximal ring count
   write_tracks             both as CSV files
 
+THE SCORE (include/spnet_hip.h "Tracking score"; csrc/track_score.hip): linked tracks against ground-truth
+identities, in the rule's own vocabulary -- per frame truth and prediction matched where each is the other's best eligible
+candidate, per identity present and matched frames, identity switches, fragments and the first matched frame.
+
+  score_tracks_device      truth + predicted tracks -> (match, frame_counts, ident_stats) int32 device tensors
+  score_tracks_host        the same in numpy (match_tracks_host, ident_stats_host)
+  track_score              those integers -> the dictionary (MOTA, precision, recall, ...): one function for both paths
+  write_truth_tracks / read_truth_tracks / truth_arrays     ground truth as a table in TABLE_FIELDS, and back
+  write_track_score        the dictionary and the per-identity statistics as CSV files
+
 Nothing here imports torch or the HIP library until a device function is called.
 """
 import os
@@ -89,13 +99,18 @@ def _overlap_host(wins, t0, n_pairs, d, K):
     """inter int32 [n_pairs,K,K] of the pairs (t, t + d), t = t0 .. t0 + n_pairs - 1."""
     inter = np.zeros((n_pairs, K, K), np.int32)
     for p in range(n_pairs):
-        for i, ax, ay, A in wins[t0 + p]:
-            for j, bx, by, B in wins[t0 + p + d]:
-                x0, y0 = max(ax, bx), max(ay, by)
-                x1, y1 = min(ax + A.shape[1], bx + B.shape[1]), min(ay + A.shape[0], by + B.shape[0])
-                if x1 > x0 and y1 > y0:
-                    inter[p, i, j] = np.count_nonzero(A[y0 - ay:y1 - ay, x0 - ax:x1 - ax] & B[y0 - by:y1 - by, x0 - bx:x1 - bx])
+        _inter_frames_host(wins[t0 + p], wins[t0 + p + d], inter[p])
     return inter
+
+
+def _inter_frames_host(wins_a, wins_b, out):
+    """out [Ka,Kb] (zeros) receives |S(a, i) & S(b, j)| of two frames' window lists."""
+    for i, ax, ay, A in wins_a:
+        for j, bx, by, B in wins_b:
+            x0, y0 = max(ax, bx), max(ay, by)
+            x1, y1 = min(ax + A.shape[1], bx + B.shape[1]), min(ay + A.shape[0], by + B.shape[0])
+            if x1 > x0 and y1 > y0:
+                out[i, j] = np.count_nonzero(A[y0 - ay:y1 - ay, x0 - ax:x1 - ax] & B[y0 - by:y1 - by, x0 - bx:x1 - bx])
 
 
 def _best_host(I, a_self, a_other, open_self, open_other, iou_q):
@@ -310,3 +325,298 @@ def write_tracks(path, rows, track, age, names=None, min_len=1):
             for rec in records:
                 f.write(",".join(repr(v) if isinstance(v, float) else str(v) for v in rec) + "\n")
     return table, summary
+
+
+# ----------------------------------------------------------------------------- the tracking score (csrc/track_score.hip)
+MAX_M = 65536               # csrc/track_score_core.h
+STAT_FIELDS = ("ident", "present", "matched", "switches", "fragments", "first_matched_frame")
+SCORE_FIELDS = ("gt", "tp", "fn", "fp", "switches", "fragments", "mota", "precision", "recall", "identities", "mostly_tracked",
+                "mostly_lost", "ring_mae", "onset_error")
+
+
+def score_path(path):
+    root, ext = os.path.splitext(path)
+    return root + "_score" + ext
+
+
+def _check_score(N, Kt, Kp, H, W, M):
+    MK._check_size(H, W, max(Kt, 1))
+    MK._check_size(H, W, max(Kp, 1))
+    if N * Kt > MAX_FLAT or N * Kp > MAX_FLAT:
+        raise ValueError("tracks: N * K = %d exceeds %d" % (N * max(Kt, Kp), MAX_FLAT))
+    if not (isinstance(M, (int, np.integer)) and 1 <= M <= MAX_M):
+        raise ValueError("tracks: the number of identities M is an integer 1 .. %d, got %r" % (MAX_M, M))
+
+
+def frame_chunks(N, Kt, Kp, ws_bytes):
+    """[(n0, n), ...] covering the frames so that a chunk's inter int32 [n][Kt][Kp] fits ws_bytes (one frame at least) and
+    the limit n * Kt * Kp <= 2^31 - 2."""
+    per = max(1, min(int(ws_bytes) // (4 * Kt * Kp), MAX_FLAT // (Kt * Kp)))
+    return [(n0, min(per, N - n0)) for n0 in range(0, N, per)]
+
+
+def effective_ident_host(live, ident, M):
+    """eff int32 [N,Kt]: ident where the row is live, 1 <= ident <= M and no live row of a lower index in the frame has the
+    same ident; 0 otherwise (the rule's "Identity")."""
+    ident = np.asarray(ident).astype(np.int64)
+    ok = live & (ident >= 1) & (ident <= M)
+    eff = np.where(ok, ident, 0)
+    for n, k in zip(*np.nonzero(ok)):
+        if k and (eff[n, :k] == ident[n, k]).any():
+            eff[n, k] = 0
+    return eff.astype(np.int32)
+
+
+def match_tracks_host(rows_t, count_t, ident, rows_p, count_p, track, H=384, W=512, iou=DEFAULT_IOU, M=None):
+    """The match rule in numpy (include/spnet_hip.h "Tracking score"): (match int32 [N,Kt], frame_counts int32 [N,3] =
+    (tp, fn, fp), eff int32 [N,Kt] the effective identities).  M None: the largest ident."""
+    rows_t, count_t = MK._host_rows(np.asarray(rows_t, np.float64), np.asarray(count_t))
+    rows_p, count_p = MK._host_rows(np.asarray(rows_p, np.float64), np.asarray(count_p))
+    ident, track = np.asarray(ident).astype(np.int64), np.asarray(track).astype(np.int64)
+    N, Kt, Kp = rows_t.shape[0], rows_t.shape[1], rows_p.shape[1]
+    if rows_p.shape[0] != N or ident.shape != (N, Kt) or track.shape != (N, Kp):
+        raise ValueError("tracks: truth [N,Kt] and prediction [N,Kp] of the same N frames, got %s, %s, %s, %s"
+                         % (rows_t.shape, ident.shape, rows_p.shape, track.shape))
+    M = _default_M(ident) if M is None else M
+    _check_score(N, Kt, Kp, int(H), int(W), M)
+    iou_q = iou_to_q(iou)
+    live_t, area_t, wins_t = _windows_host(rows_t, count_t, int(H), int(W))
+    live_p, area_p, wins_p = _windows_host(rows_p, count_p, int(H), int(W))
+    eff = effective_ident_host(live_t, ident, M)
+    open_t, open_p = eff > 0, live_p & (track > 0)
+    match, counts = np.full((N, Kt), -1, np.int32), np.zeros((N, 3), np.int32)
+    for n in range(N):
+        I = np.zeros((Kt, Kp), np.int64)
+        _inter_frames_host(wins_t[n], wins_p[n], I)
+        at, ap = area_t[n].astype(np.int64), area_p[n].astype(np.int64)
+        fwd = _best_host(I, at, ap, open_t[n], open_p[n], iou_q)
+        bwd = _best_host(I.T, ap, at, open_p[n], open_t[n], iou_q)
+        for i in np.flatnonzero(fwd >= 0):
+            if bwd[fwd[i]] == i:
+                match[n, i] = fwd[i]
+        tp = int((match[n] >= 0).sum())
+        counts[n] = (tp, int(open_t[n].sum()) - tp, int(open_p[n].sum()) - tp)
+    return match, counts, eff
+
+
+def ident_stats_host(eff, match, track, M):
+    """The identity statistics in numpy: int32 [M + 1, 5] = (present, matched, switches, fragments, first_matched_frame),
+    row 0 zeroed.  eff: effective_ident_host's array; a match entry outside 0 .. Kp-1 counts as unmatched."""
+    eff, match, track = np.asarray(eff), np.asarray(match).astype(np.int64), np.asarray(track)
+    Kp = track.shape[1] if track.ndim == 2 else 0
+    stats = np.zeros((M + 1, 5), np.int32)
+    stats[1:, 4] = -1
+    last_track, gap = {}, {}
+    for n, k in zip(*np.nonzero(eff > 0)):                         # row-major: time order
+        g, m = int(eff[n, k]), int(match[n, k])
+        s = stats[g]
+        s[0] += 1
+        if not 0 <= m < Kp:
+            gap[g] = s[1] > 0
+            continue
+        tr = int(track[n, m])
+        if s[1] > 0 and tr != last_track[g]:
+            s[2] += 1
+        if gap.get(g):
+            s[3] += 1
+        if s[1] == 0:
+            s[4] = n
+        s[1] += 1
+        last_track[g], gap[g] = tr, False
+    return stats
+
+
+def _default_M(ident):
+    size = ident.numel() if hasattr(ident, "numel") else ident.size
+    m = int(ident.max()) if size else 0
+    if m > MAX_M:
+        raise ValueError("tracks: the largest identity %d exceeds %d; renumber the identities" % (m, MAX_M))
+    return max(m, 1)
+
+
+def score_tracks_host(rows_t, count_t, ident, rows_p, count_p, track, H=384, W=512, iou=DEFAULT_IOU, M=None):
+    """(match int32 [N,Kt], frame_counts int32 [N,3], ident_stats int32 [M+1,5]) by the numpy rule."""
+    ident = np.asarray(ident)
+    M = _default_M(ident) if M is None else M
+    match, counts, eff = match_tracks_host(rows_t, count_t, ident, rows_p, count_p, track, H, W, iou, M)
+    return match, counts, ident_stats_host(eff, match, track, M)
+
+
+def score_tracks_device(rows_t, count_t, ident, rows_p, count_p, track, H=384, W=512, iou=DEFAULT_IOU, M=None,
+                        ws_bytes=256 << 20):
+    """(match int32 [N,Kt], frame_counts int32 [N,3], ident_stats int32 [M+1,5]) device tensors on the current stream
+    (spnet_track_match a range of frames at a time, ws_bytes of inter each, then spnet_track_ident over the whole movie; the
+    result is identical for any chunking).  Truth rows_t float64 [N,Kt,6], count_t int32 [N], ident int32 [N,Kt]; prediction
+    rows_p [N,Kp,6], count_p [N] (None: every row counts), track int32 [N,Kp] as link_tracks_device returns it: all device
+    tensors.  M None: the largest ident (one scalar read back)."""
+    import torch
+    from . import _lib as L
+    dev = rows_t.device
+    if count_p is None:
+        count_p = torch.full((int(rows_p.shape[0]),), int(rows_p.shape[1]), dtype=torch.int32, device=dev)
+    f64 = (rows_t, rows_p)
+    i32 = (count_t, ident, count_p, track)
+    if not (all(isinstance(a, torch.Tensor) and a.is_cuda for a in f64 + i32) and all(a.dtype == torch.float64 for a in f64)
+            and all(a.dtype == torch.int32 for a in i32) and rows_t.dim() == 3 and rows_p.dim() == 3 and rows_t.shape[2] == 6
+            and rows_p.shape[2] == 6 and rows_p.shape[0] == rows_t.shape[0] and tuple(ident.shape) == tuple(rows_t.shape[:2])
+            and tuple(track.shape) == tuple(rows_p.shape[:2]) and tuple(count_t.shape) == (rows_t.shape[0],)
+            and tuple(count_p.shape) == (rows_t.shape[0],)):
+        raise TypeError("score_tracks_device expects device tensors: rows float64 [N,K,6], count int32 [N], ident int32 [N,Kt], "
+                        "track int32 [N,Kp]")
+    rows_t, count_t, ident, rows_p, count_p, track = (a.contiguous() for a in (rows_t, count_t, ident, rows_p, count_p, track))
+    N, Kt, Kp = int(rows_t.shape[0]), int(rows_t.shape[1]), int(rows_p.shape[1])
+    M = _default_M(ident) if M is None else M
+    _check_score(N, Kt, Kp, int(H), int(W), M)
+    iou_q = iou_to_q(iou)
+    match = torch.empty((N, Kt), dtype=torch.int32, device=dev)
+    counts = torch.empty((N, 3), dtype=torch.int32, device=dev)
+    stats = torch.empty((M + 1, 5), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = L.current_stream()
+        chunks = frame_chunks(N, Kt, Kp, ws_bytes)
+        if chunks:
+            ws = torch.empty((int(L.spnet_track_match_ws(max(n for _, n in chunks), Kt, Kp)),), dtype=torch.uint8, device=dev)
+        for n0, n in chunks:                                # stream order: a chunk is done with ws before the next one
+            L.spnet_track_match(rows_t[n0:].data_ptr(), count_t[n0:].data_ptr(), ident[n0:].data_ptr(), Kt,
+                                rows_p[n0:].data_ptr(), count_p[n0:].data_ptr(), track[n0:].data_ptr(), Kp, n, int(H), int(W),
+                                iou_q, M, ws.data_ptr(), match[n0:].data_ptr(), counts[n0:].data_ptr(), st)
+        ws2 = torch.empty((int(L.spnet_track_ident_ws(N, Kt, M)),), dtype=torch.uint8, device=dev)
+        L.spnet_track_ident(L.ptr(rows_t) if N else ws2.data_ptr(), L.ptr(count_t) if N else ws2.data_ptr(),
+                            L.ptr(ident) if N else ws2.data_ptr(), L.ptr(match) if N else ws2.data_ptr(),
+                            L.ptr(track) if N else ws2.data_ptr(), N, Kt, Kp, M, ws2.data_ptr(), stats.data_ptr(), st)
+    return match, counts, stats
+
+
+def live_rows_host(rows, count=None):
+    """live bool [N,K]: k < count (clamped to 0 .. K; None: every row) and masks.quantise_row accepts the row."""
+    rows = np.asarray(rows, np.float64)
+    N, K = rows.shape[:2]
+    live = np.zeros((N, K), bool)
+    for n in range(N):
+        for k in range(K if count is None else min(max(int(count[n]), 0), K)):
+            live[n, k] = MK.quantise_row(rows[n, k]) is not None
+    return live
+
+
+def track_score(match, frame_counts, ident_stats, rows_t, rows_p, ident=None, count_t=None):
+    """The score as a dictionary (SCORE_FIELDS), in float64 on the host from the integer arrays of either path -- ONE
+    function for both, so the device and the host scores agree bit for bit.  gt = tp + fn; mota = 1 - (fn + fp + switches) /
+    gt; precision = tp / (tp + fp); recall = tp / (tp + fn); identities = those present in some frame, mostly_tracked /
+    mostly_lost = those with matched / present >= 0.8 / <= 0.2 (compared as integers); ring_mae = the mean |rings_t -
+    rings_p| over the matched pairs; onset_error = the mean over the identities that are ever matched of first_matched_frame
+    minus the identity's first PRESENT frame, which ident_stats does not hold: it is found from `ident` (the truth
+    identities [N,Kt]) and count_t ([N]; None: every row counts) by the rule's own effective identity -- live rows, 1 ..
+    M, the lower index of a duplicate -- so it is the first of the frames that `present` counts; None without ident.  A
+    ratio with a zero denominator is None."""
+    match, fc, st = _host(match).astype(np.int64), _host(frame_counts).astype(np.int64), _host(ident_stats).astype(np.int64)
+    rows_t, rows_p = np.asarray(_host(rows_t), np.float64), np.asarray(_host(rows_p), np.float64)
+    tp, fn, fp = (int(v) for v in fc.sum(0)) if fc.size else (0, 0, 0)
+    switches, fragments = int(st[1:, 2].sum()), int(st[1:, 3].sum())
+    gt = tp + fn
+
+    def ratio(a, b):
+        return float(a) / float(b) if b else None
+
+    present, matched = st[1:, 0], st[1:, 1]
+    nn, ii = np.nonzero(match >= 0)
+    err = np.abs(rows_t[nn, ii, 5] - rows_p[nn, match[nn, ii], 5])
+    onset = None
+    if ident is not None:
+        eff = effective_ident_host(live_rows_host(rows_t, None if count_t is None else _host(count_t)), _host(ident),
+                                   st.shape[0] - 1).astype(np.int64)
+        first = np.full(st.shape[0], eff.shape[0], np.int64)
+        np.minimum.at(first, eff[eff > 0], np.nonzero(eff > 0)[0])
+        sel = np.flatnonzero(st[:, 4] >= 0)
+        sel = sel[sel >= 1]
+        onset = float((st[sel, 4] - first[sel]).sum()) / len(sel) if len(sel) else None
+    return {"gt": gt, "tp": tp, "fn": fn, "fp": fp, "switches": switches, "fragments": fragments,
+            "mota": None if not gt else 1.0 - float(fn + fp + switches) / float(gt),
+            "precision": ratio(tp, tp + fp), "recall": ratio(tp, tp + fn), "identities": int((present > 0).sum()),
+            "mostly_tracked": int(((present > 0) & (5 * matched >= 4 * present)).sum()),
+            "mostly_lost": int(((present > 0) & (5 * matched <= present)).sum()),
+            "ring_mae": float(err.sum()) / len(err) if len(err) else None, "onset_error": onset}
+
+
+def truth_table(rows, ident, names=None):
+    """Ground-truth identities as track_table records: `track` is the identity, `age` the number of frames since its first
+    frame.  rows [N,K,6], ident [N,K] (0: no identity)."""
+    ident = _host(ident).astype(np.int64)
+    first = {}
+    age = np.zeros_like(ident)
+    for n, k in zip(*np.nonzero(ident > 0)):
+        age[n, k] = n - first.setdefault(int(ident[n, k]), n)
+    return track_table(rows, ident, age, names, 1)
+
+
+def write_truth_tracks(path, rows, ident, names=None):
+    """truth_table as a CSV with the header TABLE_FIELDS (floats by repr: they read back exactly).  Returns the table."""
+    table = truth_table(rows, ident, names)
+    _write_csv(path, TABLE_FIELDS, table)
+    return table
+
+
+def _write_csv(path, fields, records):
+    with open(path, "w") as f:
+        f.write(",".join(fields) + "\n")
+        for rec in records:
+            f.write(",".join(repr(v) if isinstance(v, float) else str(v) for v in rec) + "\n")
+
+
+def read_truth_tracks(path):
+    """The records of a truth_tracks.csv (or of any table write_tracks wrote), typed as track_table gives them."""
+    with open(path) as f:
+        lines = f.read().splitlines()
+    if not lines or tuple(lines[0].split(",")) != TABLE_FIELDS:
+        raise ValueError("read_truth_tracks: %s does not start with the header %s" % (path, ",".join(TABLE_FIELDS)))
+    out = []
+    for line in lines[1:]:
+        v = line.split(",")
+        if len(v) != len(TABLE_FIELDS):
+            raise ValueError("read_truth_tracks: %s: %d fields in %r" % (path, len(v), line))
+        out.append((int(v[0]), v[1], int(v[2]), int(v[3])) + tuple(float(x) for x in v[4:]))
+    return out
+
+
+def truth_arrays(records, names=None, n_frames=None, skip_unknown=False):
+    """Truth records -> (rows float64 [N,K,6], count int32 [N], ident int32 [N,K]), a frame's rows in record order.  names (a
+    list of file names, one per frame of the prediction): records are joined BY NAME and a record of an unknown name is an
+    error, or left out with skip_unknown (a loader that rounds the frames down to whole batches); otherwise by frame index, with n_frames frames (default: the largest index + 1)."""
+    if names is not None:
+        index = {os.path.basename(str(nm)): n for n, nm in enumerate(names)}
+        if skip_unknown:
+            records = [r for r in records if os.path.basename(r[1]) in index]
+        frames = []
+        for r in records:
+            if os.path.basename(r[1]) not in index:
+                raise ValueError("tracks: truth frame %r is not among the predicted frames" % (r[1],))
+            frames.append(index[os.path.basename(r[1])])
+        N = len(names)
+    else:
+        frames = [r[0] for r in records]
+        N = int(n_frames) if n_frames is not None else (max(frames) + 1 if frames else 0)
+        if frames and (min(frames) < 0 or max(frames) >= N):
+            raise ValueError("tracks: truth frames %d .. %d outside the movie's %d frames" % (min(frames), max(frames), N))
+    per = [[] for _ in range(N)]
+    for f, r in sorted(zip(frames, records), key=lambda fr: (fr[0], fr[1][2])):
+        per[f].append(r)
+    K = max(max((len(p) for p in per), default=0), 1)
+    if K > MAX_K:
+        raise ValueError("tracks: %d truth rows in one frame exceed %d" % (K, MAX_K))
+    rows, count, ident = np.zeros((N, K, 6), np.float64), np.zeros(N, np.int32), np.zeros((N, K), np.int32)
+    for n, p in enumerate(per):
+        count[n] = len(p)
+        for k, r in enumerate(p):
+            rows[n, k], ident[n, k] = r[4:], r[2]
+    return rows, count, ident
+
+
+def write_track_score(path, score, ident_stats):
+    """The score dictionary at `path` (a header line of SCORE_FIELDS and one line of values; None as an empty field) and the
+    per-identity statistics of the identities that are present at `path` with _idents before the extension (STAT_FIELDS)."""
+    st = _host(ident_stats).astype(np.int64)
+    with open(path, "w") as f:
+        f.write(",".join(SCORE_FIELDS) + "\n")
+        f.write(",".join("" if score[k] is None else repr(score[k]) if isinstance(score[k], float) else str(score[k])
+                         for k in SCORE_FIELDS) + "\n")
+    root, ext = os.path.splitext(path)
+    _write_csv(root + "_idents" + ext, STAT_FIELDS, [(g,) + tuple(int(v) for v in st[g]) for g in range(1, st.shape[0]) if st[g, 0] > 0])

@@ -10,6 +10,13 @@
 
 static inline int spnet_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// A batch on grid y or z: those dimensions end at 65,535, so a batch of n goes out as launch(base, count) per chunk.
+constexpr int SPNET_GRID_YZ_MAX = 65535;
+template <class Launch>
+static inline void spnet_for_grid_chunks(int n, Launch&& launch) {
+  for (int base = 0; base < n; base += SPNET_GRID_YZ_MAX) launch(base, n - base < SPNET_GRID_YZ_MAX ? n - base : SPNET_GRID_YZ_MAX);
+}
+
 // Every extern "C" entry point returns 0 on success or the hipError_t of the failed launch.
 #define SPNET_RETURN_LAUNCH_STATUS()            \
   do {                                          \

@@ -259,10 +259,9 @@ extern "C" int spnet_jpeg_pixels(const int16_t* coef, long total_blocks, const i
   a.status = status; a.n_quant = n_quant; a.H = H; a.W = W; a.C = channels;
   a.tiles_x = spnet_cdiv(W, PX_TILE_W);
   const unsigned tiles = (unsigned)a.tiles_x * (unsigned)spnet_cdiv(H, PX_TILE_H);          // <= 512 * 2048
-  for (int n0 = 0; n0 < n_files; n0 += 65535) {
+  spnet_for_grid_chunks(n_files, [&](int n0, int cnt) {
     a.n0 = n0;
-    const int cnt = n_files - n0 < 65535 ? n_files - n0 : 65535;
     hipLaunchKernelGGL(jpeg_pixels_kernel, dim3(tiles, (unsigned)cnt), dim3(PX_T), 0, (hipStream_t)stream, a);
-  }
+  });
   SPNET_RETURN_LAUNCH_STATUS();
 }

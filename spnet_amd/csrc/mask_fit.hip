@@ -43,7 +43,7 @@
 //                             boundary and are not written here; the words that are written here are only ever touched by
 //                             agent-scope atomic adds and read by nobody before the launch ends.
 // Components beyond the first C of a frame are counted and otherwise ignored (their pixels find no slot).
-#include "common.h"
+#include "mask_rule.h"        // the family's argument gates
 #include "mask_fit_core.h"
 
 namespace {
@@ -53,6 +53,7 @@ using namespace maskfit;
 constexpr int MF_THREADS = 256, MF_BORDER_THREADS = 128, MF_COMPACT_THREADS = 1024;
 constexpr int MF_COMPACT_WAVES = MF_COMPACT_THREADS / SPNET_WAVE, MF_COMPACT_STEP = 4 * MF_COMPACT_THREADS;
 static_assert(BORDER_JOBS <= MF_BORDER_THREADS, "one lane per border job");
+static_assert(MAX_DIM == MK_MAX_DIM && MAX_C == MK_MAX_K, "one set of limits");
 static_assert(MF_THREADS * 4 == TILE, "a lane owns 4 pixels");
 
 struct LdsStore {                       // phase 1: tile-local indices, the store is the index itself
@@ -256,19 +257,16 @@ __global__ __launch_bounds__(MF_THREADS) void mf_moments_kernel(const unsigned c
 }  // namespace
 
 extern "C" int spnet_mask_label(const unsigned char* masks, int B, int H, int W, int join_tol, int* labels, void* stream) {
-  if (!masks || !labels || !sizes_ok(B, H, W) || join_tol < 0 || join_tol > 255 || ((uintptr_t)labels & 3))
-    return (int)hipErrorInvalidValue;
+  if (!masks || !mk_int_ok(labels) || B < 0 || !mk_dims_ok(H, W) || join_tol < 0 || join_tol > 255) return (int)hipErrorInvalidValue;
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int tx = spnet_cdiv(W, TW), ty = spnet_cdiv(H, TH);
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const dim3 grid(tx, ty, min(B - b0, 65535));
-    hipLaunchKernelGGL(mf_tile_label_kernel, grid, dim3(MF_THREADS), 0, st, masks, b0, H, W, join_tol, labels);
-  }
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const dim3 grid(tx, ty, min(B - b0, 65535));
-    hipLaunchKernelGGL(mf_border_merge_kernel, grid, dim3(MF_BORDER_THREADS), 0, st, masks, b0, H, W, join_tol, labels);
-  }
+  spnet_for_grid_chunks(B, [&](int b0, int n) {
+    hipLaunchKernelGGL(mf_tile_label_kernel, dim3(tx, ty, n), dim3(MF_THREADS), 0, st, masks, b0, H, W, join_tol, labels);
+  });
+  spnet_for_grid_chunks(B, [&](int b0, int n) {
+    hipLaunchKernelGGL(mf_border_merge_kernel, dim3(tx, ty, n), dim3(MF_BORDER_THREADS), 0, st, masks, b0, H, W, join_tol, labels);
+  });
   const long total = (long)B * H * W;
   hipLaunchKernelGGL(mf_flatten_kernel, dim3(spnet_ew_grid(total, MF_THREADS)), dim3(MF_THREADS), 0, st, labels, total, H * W);
   SPNET_RETURN_LAUNCH_STATUS();
@@ -276,15 +274,15 @@ extern "C" int spnet_mask_label(const unsigned char* masks, int B, int H, int W,
 
 extern "C" int spnet_mask_moments(const unsigned char* masks, const int* labels, int B, int H, int W, int C, int* n_components,
                                   long long* sums, void* stream) {
-  if (!masks || !labels || !n_components || !sums || !sizes_ok(B, H, W) || C < 1 || C > MAX_C || ((uintptr_t)labels & 3) ||
-      ((uintptr_t)n_components & 3) || ((uintptr_t)sums & 7))
+  if (!masks || !mk_int_ok(labels) || !mk_int_ok(n_components) || !sums || ((uintptr_t)sums & 7) || B < 0 || !mk_dims_ok(H, W) ||
+      C < 1 || C > MAX_C)
     return (int)hipErrorInvalidValue;
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mf_compact_kernel, dim3(B), dim3(MF_COMPACT_THREADS), 0, st, labels, H * W, C, n_components, sums);
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const dim3 grid(spnet_cdiv(W, TW), spnet_cdiv(H, TH), min(B - b0, 65535));
+  spnet_for_grid_chunks(B, [&](int b0, int n) {
+    const dim3 grid(spnet_cdiv(W, TW), spnet_cdiv(H, TH), n);
     hipLaunchKernelGGL(mf_moments_kernel, grid, dim3(MF_THREADS), 0, st, masks, labels, b0, H, W, C, n_components, sums);
-  }
+  });
   SPNET_RETURN_LAUNCH_STATUS();
 }

@@ -112,6 +112,4 @@ MF_HD int find_slot(const int* firsts, int m, int first) {
   return (lo < m && firsts[lo] == first) ? lo : -1;
 }
 
-MF_HD bool sizes_ok(int B, int H, int W) { return B >= 0 && H >= 1 && W >= 1 && H <= MAX_DIM && W <= MAX_DIM; }
-
 }  // namespace maskfit

@@ -41,6 +41,17 @@ __device__ __forceinline__ bool quantise_row(const double* __restrict__ r, MaskR
   return true;
 }
 
+// Row k of frame n is live: k is below the frame's count (clamped to 0 .. K) and the row quantises.
+__device__ __forceinline__ bool row_live(const double* __restrict__ rows, const int* __restrict__ count, long n, int K, int k) {
+  MaskRow q;
+  return k < min(max(count[n], 0), K) && quantise_row(rows + (n * K + k) * 6, q);
+}
+
+// The argument gates of the family's entry points (host): an int32 array, a rows / count pair, a frame size.
+static inline bool mk_int_ok(const void* p) { return p && !((uintptr_t)p & 3); }
+static inline bool mk_rows_ok(const double* rows, const int* count) { return rows && !((uintptr_t)rows & 7) && mk_int_ok(count); }
+static inline bool mk_dims_ok(int H, int W) { return H >= 1 && W >= 1 && H <= MK_MAX_DIM && W <= MK_MAX_DIM; }
+
 // Does the row's box meet the pixel rectangle [x0, x1) x [y0, y1)?
 __device__ __forceinline__ bool mask_box_meets(const MaskRow& q, int x0, int y0, int x1, int y1) {
   return q.bx0 < x1 && q.bx1 >= x0 && q.by0 < y1 && q.by1 >= y0;

@@ -131,32 +131,28 @@ __global__ __launch_bounds__(MC_THREADS) void mask_compare_kernel(const unsigned
 
 extern "C" int spnet_ring_masks(const double* rows, const int* count, int B, int K, int H, int W, unsigned char* out,
                                 void* stream) {
-  if (!rows || !count || !out || B < 0 || K < 1 || K > MK_MAX_K || H < 1 || W < 1 || H > MK_MAX_DIM || W > MK_MAX_DIM ||
-      ((uintptr_t)rows & 7) || ((uintptr_t)count & 3))
-    return (int)hipErrorInvalidValue;
+  if (!mk_rows_ok(rows, count) || !out || B < 0 || K < 1 || K > MK_MAX_K || !mk_dims_ok(H, W)) return (int)hipErrorInvalidValue;
   if (B == 0) return 0;
   const int vec16 = (W % 16 == 0) && !((uintptr_t)out & 15);
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const dim3 grid(spnet_cdiv(W, MK_TW), spnet_cdiv(H, MK_TH), min(B - b0, 65535));
+  spnet_for_grid_chunks(B, [&](int b0, int n) {
+    const dim3 grid(spnet_cdiv(W, MK_TW), spnet_cdiv(H, MK_TH), n);
     hipLaunchKernelGGL(ring_masks_kernel, grid, dim3(MK_THREADS), 0, (hipStream_t)stream, rows, count, b0, K, H, W, out, vec16);
-  }
+  });
   SPNET_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int spnet_mask_compare(const unsigned char* pred, const unsigned char* truth, int N, long n_pixels, int tol,
                                   int* counts, void* stream) {
-  if (!pred || !truth || !counts || N < 0 || n_pixels < 1 || n_pixels > 0x7fffffffL || tol < 0 || tol > 255 ||
-      ((uintptr_t)counts & 3))
+  if (!pred || !truth || !mk_int_ok(counts) || N < 0 || n_pixels < 1 || n_pixels > 0x7fffffffL || tol < 0 || tol > 255)
     return (int)hipErrorInvalidValue;
   if (N == 0) return 0;
   hipError_t e = hipMemsetAsync(counts, 0, (size_t)N * 5 * sizeof(int), (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
   const long want = (n_pixels + MC_BYTES_PER_BLOCK - 1) / MC_BYTES_PER_BLOCK;
   const int blocks = want < MC_MAX_BLOCKS ? (int)want : MC_MAX_BLOCKS;
-  for (int n0 = 0; n0 < N; n0 += 65535) {
-    const dim3 grid(blocks, min(N - n0, 65535));
-    hipLaunchKernelGGL(mask_compare_kernel, grid, dim3(MC_THREADS), 0, (hipStream_t)stream, pred, truth, n0, n_pixels, tol,
-                       counts);
-  }
+  spnet_for_grid_chunks(N, [&](int n0, int n) {
+    hipLaunchKernelGGL(mask_compare_kernel, dim3(blocks, n), dim3(MC_THREADS), 0, (hipStream_t)stream, pred, truth, n0, n_pixels,
+                       tol, counts);
+  });
   SPNET_RETURN_LAUNCH_STATUS();
 }

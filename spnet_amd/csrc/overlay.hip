@@ -252,10 +252,10 @@ extern "C" int spnet_draw_overlays(const unsigned char* frames, int N, int H, in
       (mask_bytes > 0 && !masks) || ((uintptr_t)frame_start & 3) || ((uintptr_t)cmd & 3) || ((uintptr_t)verts & 3))
     return (int)hipErrorInvalidValue;
   const int vec16 = (W % 16 == 0) && !((uintptr_t)frames & 15) && !((uintptr_t)out & 15);
-  for (int n0 = 0; n0 < N; n0 += 65535) {
-    const dim3 grid(spnet_cdiv(W, OV_TW), spnet_cdiv(H, OV_TH), min(N - n0, 65535));
+  spnet_for_grid_chunks(N, [&](int n0, int n) {
+    const dim3 grid(spnet_cdiv(W, OV_TW), spnet_cdiv(H, OV_TH), n);
     hipLaunchKernelGGL(overlay_kernel, grid, dim3(OV_THREADS), 0, (hipStream_t)stream, frames, n0, H, W, channels, frame_start,
                        cmd, n_cmd, verts, n_verts, masks, mask_bytes, out, vec16);
-  }
+  });
   SPNET_RETURN_LAUNCH_STATUS();
 }

@@ -8,8 +8,8 @@
 //              A = the frame's truth rows, B = its predicted rows; inter int32 [N][Kt][Kp] in ws, zeroed by a memset node.
 //              Every row the TRACK rule calls live is counted; identities and tracks take no part yet
 //   match      track_match_kernel: one workgroup per frame, threads 0 .. Kt-1 for the truth rows, 128 .. 128+Kp-1 for the
-//              predicted rows (track_score_core.h: liveness and effective identities, a barrier, every lane chooses its
-//              best, a barrier, then the mutual test and the three counts)
+//              predicted rows (liveness and track_score_core.h's effective identities, a barrier, then track_tile.h's
+//              track_mutual_best -- every lane chooses its best, a barrier, the mutual test -- and the three counts)
 // spnet_track_ident, the identity statistics: a LANE PER IDENTITY WALKING ITS OWN FRAMES.
 //   range      ident_range_kernel: one workgroup per frame writes the effective identities eff [N][Kt] into ws and widens
 //              first[g] / last[g] (atomicMin on uint32 / atomicMax; order-free) to the frames in which g is present
@@ -26,8 +26,6 @@
 
 namespace {
 
-static_assert(tracks::MAX_K == MK_MAX_K, "one set of limits");
-
 __global__ __launch_bounds__(TR_THREADS) void track_match_overlap_kernel(const double* __restrict__ rows_t,
                                                                          const int* __restrict__ count_t, int Kt,
                                                                          const double* __restrict__ rows_p,
@@ -37,12 +35,6 @@ __global__ __launch_bounds__(TR_THREADS) void track_match_overlap_kernel(const d
   const long n = (long)n_base + blockIdx.y;
   track_tile_overlap(rows_t + n * Kt * 6, min(max(count_t[n], 0), Kt), rows_p + n * Kp * 6, count_p + n, Kp, H, W, tiles_x,
                      (int)blockIdx.x, s, inter + n * Kt * Kp, Kp);
-}
-
-// live flags of one frame's rows for thread k < K (the track rule's liveness)
-__device__ __forceinline__ bool row_live(const double* __restrict__ rows, const int* __restrict__ count, long n, int K, int k) {
-  MaskRow q;
-  return k < min(max(count[n], 0), K) && quantise_row(rows + (n * K + k) * 6, q);
 }
 
 __global__ __launch_bounds__(TR_THREADS) void track_match_kernel(const int* __restrict__ inter, const int* __restrict__ area_t,
@@ -76,15 +68,10 @@ __global__ __launch_bounds__(TR_THREADS) void track_match_kernel(const int* __re
   __syncthreads();
   if (side == 0 && k < Kt) s_open[0][k] = track_score::effective_ident(s_ident, s_live, k, M) ? 1 : 0;
   __syncthreads();
-  const int* pin = inter + n * Kt * Kp;
-  if (k < K)
-    s_best[side][k] = side ? track_score::match_choose_pred(pin, Kt, Kp, k, s_area[0], s_area[1], s_open[0], s_open[1], iou_q)
-                           : track_score::match_choose_truth(pin, Kp, k, s_area[0], s_area[1], s_open[0], s_open[1], iou_q);
-  __syncthreads();
+  const int j = track_mutual_best(inter + n * Kt * Kp, Kt, Kp, s_area, s_open, s_best, iou_q);
   if (k < K) {
     if (s_open[side][k]) atomicAdd(&s_n[side], 1);
     if (side == 0) {
-      const int j = track_score::match_mutual(s_best[0], s_best[1], Kp, k);
       match[n * Kt + k] = j;
       if (j >= 0) atomicAdd(&s_n[2], 1);
     }
@@ -131,10 +118,6 @@ __global__ __launch_bounds__(TR_THREADS) void ident_walk_kernel(const int* __res
   track_score::ident_walk(eff, match, track, N, Kt, Kp, g, (long)(unsigned)first[g], last[g], out);
 }
 
-bool frames_ok(const double* rows, const int* count) { return rows && count && !((uintptr_t)rows & 7) && !((uintptr_t)count & 3); }
-bool int_ok(const void* p) { return p && !((uintptr_t)p & 3); }
-bool dims_ok(int H, int W) { return H >= 1 && W >= 1 && H <= MK_MAX_DIM && W <= MK_MAX_DIM; }
-
 }  // namespace
 
 extern "C" long spnet_track_match_ws(int N, int Kt, int Kp) {
@@ -146,9 +129,9 @@ extern "C" long spnet_track_match_ws(int N, int Kt, int Kp) {
 extern "C" int spnet_track_match(const double* rows_t, const int* count_t, const int* ident, int Kt, const double* rows_p,
                                  const int* count_p, const int* track, int Kp, int N, int H, int W, int iou_q, int M, void* ws,
                                  int* match, int* frame_counts, void* stream) {
-  if (!frames_ok(rows_t, count_t) || !frames_ok(rows_p, count_p) || !track_score::sizes_ok(N, Kt, Kp) || !dims_ok(H, W) ||
-      !track_score::idents_ok(M) || iou_q < 1 || iou_q > tracks::IOU_ONE || !int_ok(ident) || !int_ok(track) || !int_ok(ws) ||
-      !int_ok(match) || !int_ok(frame_counts))
+  if (!mk_rows_ok(rows_t, count_t) || !mk_rows_ok(rows_p, count_p) || !track_score::sizes_ok(N, Kt, Kp) || !mk_dims_ok(H, W) ||
+      !track_score::idents_ok(M) || iou_q < 1 || iou_q > tracks::IOU_ONE || !mk_int_ok(ident) || !mk_int_ok(track) ||
+      !mk_int_ok(ws) || !mk_int_ok(match) || !mk_int_ok(frame_counts))
     return (int)hipErrorInvalidValue;
   if (N == 0) return 0;
   int* inter = (int*)ws;
@@ -161,12 +144,14 @@ extern "C" int spnet_track_match(const double* rows_t, const int* count_t, const
   hipError_t he = hipMemsetAsync(inter, 0, (size_t)N * Kt * Kp * sizeof(int), (hipStream_t)stream);
   if (he != hipSuccess) return (int)he;
   const int tiles_x = spnet_cdiv(W, MK_TW), tiles = tiles_x * spnet_cdiv(H, MK_TH);
-  for (int n0 = 0; n0 < N; n0 += 65535)
-    hipLaunchKernelGGL(track_match_overlap_kernel, dim3(tiles, min(N - n0, 65535)), dim3(TR_THREADS), 0, (hipStream_t)stream,
-                       rows_t, count_t, Kt, rows_p, count_p, Kp, H, W, tiles_x, n0, inter);
-  for (int n0 = 0; n0 < N; n0 += 65535)
-    hipLaunchKernelGGL(track_match_kernel, dim3(min(N - n0, 65535)), dim3(TR_THREADS), 0, (hipStream_t)stream, inter, area_t,
-                       area_p, rows_t, count_t, ident, Kt, rows_p, count_p, track, Kp, n0, iou_q, M, match, frame_counts);
+  spnet_for_grid_chunks(N, [&](int n0, int n) {
+    hipLaunchKernelGGL(track_match_overlap_kernel, dim3(tiles, n), dim3(TR_THREADS), 0, (hipStream_t)stream, rows_t, count_t, Kt,
+                       rows_p, count_p, Kp, H, W, tiles_x, n0, inter);
+  });
+  spnet_for_grid_chunks(N, [&](int n0, int n) {
+    hipLaunchKernelGGL(track_match_kernel, dim3(n), dim3(TR_THREADS), 0, (hipStream_t)stream, inter, area_t, area_p, rows_t,
+                       count_t, ident, Kt, rows_p, count_p, track, Kp, n0, iou_q, M, match, frame_counts);
+  });
   SPNET_RETURN_LAUNCH_STATUS();
 }
 
@@ -177,8 +162,8 @@ extern "C" long spnet_track_ident_ws(int N, int Kt, int M) {
 
 extern "C" int spnet_track_ident(const double* rows_t, const int* count_t, const int* ident, const int* match, const int* track,
                                  int N, int Kt, int Kp, int M, void* ws, int* ident_stats, void* stream) {
-  if (!frames_ok(rows_t, count_t) || !track_score::sizes_ok(N, Kt, Kp) || !track_score::idents_ok(M) || !int_ok(ident) ||
-      !int_ok(match) || !int_ok(track) || !int_ok(ws) || !int_ok(ident_stats))
+  if (!mk_rows_ok(rows_t, count_t) || !track_score::sizes_ok(N, Kt, Kp) || !track_score::idents_ok(M) || !mk_int_ok(ident) ||
+      !mk_int_ok(match) || !mk_int_ok(track) || !mk_int_ok(ws) || !mk_int_ok(ident_stats))
     return (int)hipErrorInvalidValue;
   int* first = (int*)ws;                                                // [M + 1], then last [M + 1], then eff [N][Kt]
   int* last = first + (M + 1);
@@ -186,9 +171,10 @@ extern "C" int spnet_track_ident(const double* rows_t, const int* count_t, const
   // first as uint32 0xffffffff (above every frame), last -1
   hipError_t he = hipMemsetAsync(first, 0xff, 2 * (size_t)(M + 1) * sizeof(int), (hipStream_t)stream);
   if (he != hipSuccess) return (int)he;
-  for (int n0 = 0; n0 < N; n0 += 65535)
-    hipLaunchKernelGGL(ident_range_kernel, dim3(min(N - n0, 65535)), dim3(MK_MAX_K), 0, (hipStream_t)stream, rows_t, count_t,
-                       ident, Kt, M, n0, eff, first, last);
+  spnet_for_grid_chunks(N, [&](int n0, int n) {
+    hipLaunchKernelGGL(ident_range_kernel, dim3(n), dim3(MK_MAX_K), 0, (hipStream_t)stream, rows_t, count_t, ident, Kt, M, n0, eff,
+                       first, last);
+  });
   hipLaunchKernelGGL(ident_walk_kernel, dim3(spnet_cdiv(M + 1, TR_THREADS)), dim3(TR_THREADS), 0, (hipStream_t)stream, eff, match,
                      track, (long)N, Kt, Kp, M, first, last, ident_stats);
   SPNET_RETURN_LAUNCH_STATUS();

@@ -1,8 +1,8 @@
 // The tracking score: the parts that do not depend on where the arrays live.  The rule is stated beside the prototypes in
 // spnet_hip.h ("Tracking score").  csrc/track_score.hip calls these from its match and identity kernels, one lane per row
 // or per identity; tools/track_score_host_check.cpp calls them over exact-size heap arrays, with the lanes in a loop, under
-// AddressSanitizer.  Eligible, Better and the ascending scan with lower-index ties are tracks_core.h's best_candidate:
-// nothing of the order is defined twice.
+// AddressSanitizer.  The match of a frame -- truth rows with an effective identity against predicted rows that are live with
+// track > 0 -- is tracks_core.h's mutual best (mutual_choose_a / _b, mutual_partner), the linker's: nothing of it is here.
 //
 // EFFECTIVE IDENTITY.  eff(t, k) = ident[t][k] where truth row (t, k) is live, 1 <= ident <= M and no live row k' < k of
 // the frame has the same ident; 0 otherwise.  So an identity has at most one row a frame, and an ident outside 1 .. M is
@@ -33,28 +33,6 @@ TR_HD int effective_ident(const int* ident, const unsigned char* live, int k, in
   for (int m = 0; m < k; ++m)
     if (live[m] && ident[m] == g) return 0;
   return g;
-}
-
-// One frame, lane by lane.  inter: the frame's int32 [Kt][Kp], [i][j] = |S_t(i) ^ S_p(j)|; open_t[i]: truth row i has an
-// effective identity, open_p[j]: predicted row j is live with track > 0.
-//   match_choose_truth(i) -> the best eligible open j for i, or -1 (also -1 when i is not open)
-//   match_choose_pred(j)  -> the best eligible open i for j, or -1
-// and once ALL lanes have chosen (a barrier on the device): i <-> j iff fwd[i] == j and bwd[j] == i.
-TR_HD int match_choose_truth(const int* inter, int Kp, int i, const int* area_t, const int* area_p, const unsigned char* open_t,
-                             const unsigned char* open_p, int iou_q) {
-  if (!open_t[i]) return -1;
-  return tracks::best_candidate(inter + (long)i * Kp, 1, Kp, area_t[i], area_p, open_p, iou_q);
-}
-
-TR_HD int match_choose_pred(const int* inter, int Kt, int Kp, int j, const int* area_t, const int* area_p,
-                            const unsigned char* open_t, const unsigned char* open_p, int iou_q) {
-  if (!open_p[j]) return -1;
-  return tracks::best_candidate(inter + j, Kp, Kt, area_p[j], area_t, open_t, iou_q);
-}
-
-TR_HD int match_mutual(const int* fwd, const int* bwd, int Kp, int i) {
-  const int j = fwd[i];
-  return (j >= 0 && j < Kp && bwd[j] == i) ? j : -1;
 }
 
 struct Walk {

@@ -15,8 +15,10 @@
 // or H are masked out of every count; out is addressed by row indices below the two counts only.
 #pragma once
 #include "mask_rule.h"
+#include "tracks_core.h"
 
 constexpr int TR_THREADS = MK_THREADS;
+static_assert(tracks::MAX_K == MK_MAX_K && tracks::MAX_DIM == MK_MAX_DIM && TR_THREADS == 2 * MK_MAX_K, "one set of limits");
 
 struct TrackTileLds {
   MaskRow row[2][MK_MAX_K];
@@ -96,4 +98,17 @@ __device__ __forceinline__ void track_tile_overlap(const double* __restrict__ fr
     const unsigned c = (s.table[i][j >> 1] >> (16 * (j & 1))) & 0xffffu;
     if (c) atomicAdd(out + (long)s.list[0][i] * stride_b + s.list[1][j], (int)c);
   }
+}
+
+// The mutual best of one [Ka][Kb] table by a workgroup of 2 x 128 threads: thread side * 128 + k is lane k of side A
+// (side 0) or B (side 1).  s_area and s_open are filled and behind a barrier; every lane chooses into s_best, a barrier,
+// and a side-A lane gets its partner (tracks_core.h), every other thread -1.  Every thread of the workgroup calls it.
+__device__ __forceinline__ int track_mutual_best(const int* __restrict__ inter, int Ka, int Kb, const int (*s_area)[MK_MAX_K],
+                                                 const unsigned char (*s_open)[MK_MAX_K], int (*s_best)[MK_MAX_K], int iou_q) {
+  const int side = threadIdx.x / MK_MAX_K, k = threadIdx.x % MK_MAX_K;
+  if (k < (side ? Kb : Ka))
+    s_best[side][k] = side ? tracks::mutual_choose_b(inter, Ka, Kb, k, s_area[0], s_area[1], s_open[0], s_open[1], iou_q)
+                           : tracks::mutual_choose_a(inter, Kb, k, s_area[0], s_area[1], s_open[0], s_open[1], iou_q);
+  __syncthreads();
+  return (side == 0 && k < Ka) ? tracks::mutual_partner(s_best[0], s_best[1], Kb, k) : -1;
 }

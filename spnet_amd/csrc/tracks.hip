@@ -14,8 +14,9 @@
 // order of arrival.
 //
 // track_link_kernel: one workgroup per frame pair, threads 0 .. K-1 for the detections of frame t, 128 .. 128+K-1 for those
-// of frame t + d (tracks_core.h: every lane chooses its best, a barrier, then the mutual test).  The workgroup of pair
-// (t, t + d) is the only writer of next[t] and prev[t + d] in its launch and reads nothing that another pair writes.
+// of frame t + d (track_tile.h's track_mutual_best: every lane chooses its best, a barrier, then the mutual test).  The
+// workgroup of pair (t, t + d) is the only writer of next[t] and prev[t + d] in its launch and reads nothing that another
+// pair writes.
 //
 // track_rank_*: pointer jumping over prev (tracks_core.h) between two ping-pong halves of ws, one launch per round: a round
 // reads one half and writes the other, so no lane reads what another lane of the same launch writes.
@@ -23,11 +24,8 @@
 // Bounds: count is clamped to 0 .. K; list positions are < K <= 128; pixels beyond W or H are masked out of every count;
 // next and prev are only compared with -1 by the link step; prev is range-checked by rank_init before it is an address.
 #include "track_tile.h"
-#include "tracks_core.h"
 
 namespace {
-
-static_assert(tracks::MAX_K == MK_MAX_K && tracks::MAX_DIM == MK_MAX_DIM, "one set of limits");
 
 __global__ __launch_bounds__(TR_THREADS) void track_area_kernel(const double* __restrict__ rows, const int* __restrict__ count,
                                                                 int n_base, int K, int H, int W, int tiles_x,
@@ -83,24 +81,15 @@ __global__ __launch_bounds__(TR_THREADS) void track_link_kernel(const int* __res
   const int tid = threadIdx.x, side = tid / MK_MAX_K, k = tid % MK_MAX_K;   // side 0: frame t, 1: frame t + d
   const long t = side ? tb : ta;
   if (k < K) {
-    MaskRow q;
-    const bool live = k < min(max(count[t], 0), K) && quantise_row(rows + (t * K + k) * 6, q);
     const int link = side ? prev[t * K + k] : next[t * K + k];
-    s_open[side][k] = (live && link == -1) ? 1 : 0;
+    s_open[side][k] = (row_live(rows, count, t, K, k) && link == -1) ? 1 : 0;
     s_area[side][k] = area[t * K + k];
   }
   __syncthreads();
-  const int* pin = inter + pair * K * K;
-  if (k < K)
-    s_best[side][k] = side ? tracks::link_choose_backward(pin, K, k, s_area[0], s_area[1], s_open[0], s_open[1], iou_q)
-                           : tracks::link_choose_forward(pin, K, k, s_area[0], s_area[1], s_open[0], s_open[1], iou_q);
-  __syncthreads();
-  if (side == 0 && k < K) {
-    const int j = tracks::link_mutual(s_best[0], s_best[1], K, k);
-    if (j >= 0) {
-      next[ta * K + k] = (int)(tb * K + j);
-      prev[tb * K + j] = (int)(ta * K + k);
-    }
+  const int j = track_mutual_best(inter + pair * K * K, K, K, s_area, s_open, s_best, iou_q);
+  if (j >= 0) {                                             // lanes of frame t only
+    next[ta * K + k] = (int)(tb * K + j);
+    prev[tb * K + j] = (int)(ta * K + k);
   }
 }
 
@@ -127,18 +116,14 @@ __global__ __launch_bounds__(TR_THREADS) void track_rank_finish_kernel(const int
   for (long x = (long)blockIdx.x * TR_THREADS + threadIdx.x; x < total; x += (long)gridDim.x * TR_THREADS) {
     const long t = x / K;
     const int k = (int)(x - t * K);
-    MaskRow q;
-    const bool live = k < min(max(count[t], 0), K) && quantise_row(rows + x * 6, q);
+    const bool live = row_live(rows, count, t, K, k);
     const int a = anc[x];
     track[x] = live ? 1 + ((a >= 0 && a < total) ? a : (int)x) : 0;
     age[x] = live ? dist[x] : 0;
   }
 }
 
-bool frames_ok(const double* rows, const int* count, long N, int K) {
-  return rows && count && tracks::sizes_ok(N, K) && !((uintptr_t)rows & 7) && !((uintptr_t)count & 3);
-}
-bool dims_ok(int H, int W) { return H >= 1 && W >= 1 && H <= MK_MAX_DIM && W <= MK_MAX_DIM; }
+bool frames_ok(const double* rows, const int* count, long N, int K) { return mk_rows_ok(rows, count) && tracks::sizes_ok(N, K); }
 // pairs (t, t + d), t = t0 .. t0 + n_pairs - 1, all inside 0 .. N-1
 bool range_ok(long N, long t0, long n_pairs, int d) {
   return d >= 1 && d <= tracks::MAX_GAP && t0 >= 0 && n_pairs >= 0 && t0 + n_pairs + d <= N;
@@ -147,40 +132,43 @@ bool range_ok(long N, long t0, long n_pairs, int d) {
 }  // namespace
 
 extern "C" int spnet_track_area(const double* rows, const int* count, int N, int K, int H, int W, int* area, void* stream) {
-  if (!frames_ok(rows, count, N, K) || !dims_ok(H, W) || !area || ((uintptr_t)area & 3)) return (int)hipErrorInvalidValue;
+  if (!frames_ok(rows, count, N, K) || !mk_dims_ok(H, W) || !mk_int_ok(area)) return (int)hipErrorInvalidValue;
   if (N == 0) return 0;
   hipError_t e = hipMemsetAsync(area, 0, (size_t)N * K * sizeof(int), (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
   const int tiles_x = spnet_cdiv(W, MK_TW), tiles = tiles_x * spnet_cdiv(H, MK_TH);
-  for (int n0 = 0; n0 < N; n0 += 65535)
-    hipLaunchKernelGGL(track_area_kernel, dim3(tiles, min(N - n0, 65535)), dim3(TR_THREADS), 0, (hipStream_t)stream, rows,
-                       count, n0, K, H, W, tiles_x, area);
+  spnet_for_grid_chunks(N, [&](int n0, int n) {
+    hipLaunchKernelGGL(track_area_kernel, dim3(tiles, n), dim3(TR_THREADS), 0, (hipStream_t)stream, rows, count, n0, K, H, W,
+                       tiles_x, area);
+  });
   SPNET_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int spnet_track_overlap(const double* rows, const int* count, int N, int K, int H, int W, int t0, int n_pairs,
                                    int d, int* inter, void* stream) {
-  if (!frames_ok(rows, count, N, K) || !dims_ok(H, W) || !range_ok(N, t0, n_pairs, d) || !inter || ((uintptr_t)inter & 3))
+  if (!frames_ok(rows, count, N, K) || !mk_dims_ok(H, W) || !range_ok(N, t0, n_pairs, d) || !mk_int_ok(inter))
     return (int)hipErrorInvalidValue;
   if (n_pairs == 0) return 0;
   hipError_t e = hipMemsetAsync(inter, 0, (size_t)n_pairs * K * K * sizeof(int), (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
   const int tiles_x = spnet_cdiv(W, MK_TW), tiles = tiles_x * spnet_cdiv(H, MK_TH);
-  for (int p0 = 0; p0 < n_pairs; p0 += 65535)
-    hipLaunchKernelGGL(track_overlap_kernel, dim3(tiles, min(n_pairs - p0, 65535)), dim3(TR_THREADS), 0, (hipStream_t)stream,
-                       rows, count, K, H, W, tiles_x, (long)t0, p0, d, inter);
+  spnet_for_grid_chunks(n_pairs, [&](int p0, int n) {
+    hipLaunchKernelGGL(track_overlap_kernel, dim3(tiles, n), dim3(TR_THREADS), 0, (hipStream_t)stream, rows, count, K, H, W,
+                       tiles_x, (long)t0, p0, d, inter);
+  });
   SPNET_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int spnet_track_link(const int* inter, const int* area, const double* rows, const int* count, int N, int K, int t0,
                                 int n_pairs, int d, int iou_q, int* next, int* prev, void* stream) {
-  if (!frames_ok(rows, count, N, K) || !range_ok(N, t0, n_pairs, d) || !inter || !area || !next || !prev || iou_q < 1 ||
-      iou_q > tracks::IOU_ONE || (((uintptr_t)inter | (uintptr_t)area | (uintptr_t)next | (uintptr_t)prev) & 3))
+  if (!frames_ok(rows, count, N, K) || !range_ok(N, t0, n_pairs, d) || !mk_int_ok(inter) || !mk_int_ok(area) ||
+      !mk_int_ok(next) || !mk_int_ok(prev) || iou_q < 1 || iou_q > tracks::IOU_ONE)
     return (int)hipErrorInvalidValue;
   if (n_pairs == 0) return 0;
-  for (int p0 = 0; p0 < n_pairs; p0 += 65535)             // grid x: up to 2^31 - 1, but one form for all three kernels
-    hipLaunchKernelGGL(track_link_kernel, dim3(min(n_pairs - p0, 65535)), dim3(TR_THREADS), 0, (hipStream_t)stream, inter,
-                       area, rows, count, K, (long)t0, p0, d, iou_q, next, prev);
+  spnet_for_grid_chunks(n_pairs, [&](int p0, int n) {
+    hipLaunchKernelGGL(track_link_kernel, dim3(n), dim3(TR_THREADS), 0, (hipStream_t)stream, inter, area, rows, count, K,
+                       (long)t0, p0, d, iou_q, next, prev);
+  });
   SPNET_RETURN_LAUNCH_STATUS();
 }
 
@@ -192,8 +180,7 @@ extern "C" long spnet_track_rank_ws(int N, int K) {
 
 extern "C" int spnet_track_rank(const int* prev, const double* rows, const int* count, int N, int K, int* track, int* age,
                                 void* ws, void* stream) {
-  if (!frames_ok(rows, count, N, K) || !prev || !track || !age || !ws ||
-      (((uintptr_t)prev | (uintptr_t)track | (uintptr_t)age | (uintptr_t)ws) & 3))
+  if (!frames_ok(rows, count, N, K) || !mk_int_ok(prev) || !mk_int_ok(track) || !mk_int_ok(age) || !mk_int_ok(ws))
     return (int)hipErrorInvalidValue;
   if (N == 0) return 0;
   const long total = (long)N * K;

@@ -70,28 +70,28 @@ TR_HD int best_candidate(const int* inter, long stride, int n, int area_self, co
   return best;
 }
 
-// One frame pair (t, t + d), lane by lane.  inter: the pair's int32 [K][K], [i][j] = |S(t,i) ^ S(t+d,j)|; area_a, area_b
-// the two frames' areas; open_a[i]: detection i of frame t is live and has no successor, open_b[j]: detection j of frame
-// t + d is live and has no predecessor.
-//   link_choose_forward(i)   -> the best eligible open j for i, or -1 (also -1 when i is not open)
-//   link_choose_backward(j)  -> the best eligible open i for j, or -1
-// and once ALL lanes have chosen (a barrier on the device): i -> j is linked iff fwd[i] == j and bwd[j] == i.
-TR_HD int link_choose_forward(const int* inter, int K, int i, const int* area_a, const int* area_b, const unsigned char* open_a,
-                              const unsigned char* open_b, int iou_q) {
+// The mutual best of two sides A and B, lane by lane.  inter: int32 [Ka][Kb], [i][j] = |S_a(i) ^ S_b(j)|; area_a, area_b
+// and open_a, open_b the two sides' areas and open flags.  The linker's sides are the frames t and t + d of a pair
+// (Ka = Kb = K; open: live with no successor / no predecessor yet), the score's are a frame's truth and prediction.
+//   mutual_choose_a(i)  -> the best eligible open j for i, or -1 (also -1 when i is not open)
+//   mutual_choose_b(j)  -> the best eligible open i for j, or -1
+// and once ALL lanes have chosen (a barrier on the device): i <-> j iff best_a[i] == j and best_b[j] == i.
+TR_HD int mutual_choose_a(const int* inter, int Kb, int i, const int* area_a, const int* area_b, const unsigned char* open_a,
+                          const unsigned char* open_b, int iou_q) {
   if (!open_a[i]) return -1;
-  return best_candidate(inter + (long)i * K, 1, K, area_a[i], area_b, open_b, iou_q);
+  return best_candidate(inter + (long)i * Kb, 1, Kb, area_a[i], area_b, open_b, iou_q);
 }
 
-TR_HD int link_choose_backward(const int* inter, int K, int j, const int* area_a, const int* area_b, const unsigned char* open_a,
-                               const unsigned char* open_b, int iou_q) {
+TR_HD int mutual_choose_b(const int* inter, int Ka, int Kb, int j, const int* area_a, const int* area_b,
+                          const unsigned char* open_a, const unsigned char* open_b, int iou_q) {
   if (!open_b[j]) return -1;
-  return best_candidate(inter + j, K, K, area_b[j], area_a, open_a, iou_q);
+  return best_candidate(inter + j, Kb, Ka, area_b[j], area_a, open_a, iou_q);
 }
 
-// The mutual-best test for lane i; the partner j, or -1.  fwd and bwd hold K entries each.
-TR_HD int link_mutual(const int* fwd, const int* bwd, int K, int i) {
-  const int j = fwd[i];
-  return (j >= 0 && j < K && bwd[j] == i) ? j : -1;
+// The mutual-best test for lane i of side A; the partner j, or -1.  best_a holds Ka entries, best_b Kb.
+TR_HD int mutual_partner(const int* best_a, const int* best_b, int Kb, int i) {
+  const int j = best_a[i];
+  return (j >= 0 && j < Kb && best_b[j] == i) ? j : -1;
 }
 
 // prev of flat index x as an address: prev if it points into an earlier frame, else x (a head).

@@ -79,7 +79,7 @@ def row_box(row):
     return fx - R, fy - R, fx + R, fy + R
 
 
-def _inside_row_host(row, H, W, use_box=True, q=None):
+def inside_row_host(row, H, W, use_box=True, q=None):
     """The pixels of an H x W frame inside one row, as (x0, y0, bool [h, w]): the window's corner and the test on every
     pixel of the window (the row's box cut to the frame; the whole frame without use_box).  None where the row paints
     nothing or its window is empty.  q: quantise_row(row), if the caller has it."""
@@ -109,14 +109,14 @@ def _inside_row_host(row, H, W, use_box=True, q=None):
 
 def _paint_row_host(mask, row, use_box=True):
     q = quantise_row(row)
-    win = _inside_row_host(row, mask.shape[0], mask.shape[1], use_box, q)
+    win = inside_row_host(row, mask.shape[0], mask.shape[1], use_box, q)
     if win is None:
         return
     x0, y0, inside = win
     mask[y0:y0 + inside.shape[0], x0:x0 + inside.shape[1]][inside] = q[6]
 
 
-def _host_rows(rows, count=None):
+def host_rows(rows, count=None):
     if count is None:
         meta = rows
         if isinstance(meta, tuple):
@@ -130,7 +130,7 @@ def _host_rows(rows, count=None):
     return rows, count
 
 
-def _check_size(H, W, K=1):
+def check_size(H, W, K=1):
     if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM and 1 <= K <= MAX_K):
         raise ValueError("masks: H, W are 1 .. %d and K is 1 .. %d, got H %d, W %d, K %d" % (MAX_DIM, MAX_K, H, W, K))
 
@@ -139,10 +139,10 @@ def ring_masks_host(rows, count=None, H=384, W=512, use_box=True):
     """The rule in numpy: rows float64 [B,K,6] with count [B] (clamped to 0 .. K), or a list of label lists.  Returns uint8
     [B,H,W].  Exact (pixels near a rim are decided in Python integers), and slow.  use_box=False tests every pixel of the
     frame against every row: the same masks, since the box holds every painted pixel."""
-    rows, count = _host_rows(rows, count)
+    rows, count = host_rows(rows, count)
     B, K = rows.shape[:2]
     H, W = int(H), int(W)
-    _check_size(H, W, max(K, 1))
+    check_size(H, W, max(K, 1))
     out = np.zeros((B, H, W), np.uint8)
     for b in range(B):
         for k in range(min(max(int(count[b]), 0), K)):
@@ -180,11 +180,59 @@ def _check_tol(tol):
 
 
 # ----------------------------------------------------------------------------- the device side
-def _default_device(device):
+def host_array(a):
+    """A device tensor brought to the host; anything else through np.asarray."""
+    return a.cpu().numpy() if hasattr(a, "is_cuda") else np.asarray(a)
+
+
+def default_device(device):
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("masks: the device rasteriser needs a GPU (ring_masks_host is the host rule)")
     return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+ROWS_TEXT = "%s expects rows float64 [%s,K,6] and count int32 [%s] on the device"
+
+
+def device_rows(rows, count, device, text, every_row=False, upload=True):
+    """The gate of every entry that reads rows on the device: contiguous (rows float64 [N,K,6], count int32 [N], N, K).
+    Host input -- an array with its count, pad_metadata's pair or a list of label lists -- goes through host_rows and is
+    uploaded to `device`, unless upload is False (then it is an error like any other).  every_row: count None means that
+    every row counts (without it, None with an array is host_rows' business and None with a tensor is an error).
+    TypeError(text) for anything else."""
+    import torch
+    if isinstance(rows, torch.Tensor):
+        if count is None and every_row:                     # made where the rows are: nothing leaves the device
+            count = torch.full((int(rows.shape[0]),), int(rows.shape[1]) if rows.dim() == 3 else 0, dtype=torch.int32,
+                               device=rows.device)
+    elif upload:
+        if count is None and every_row and not isinstance(rows, (list, tuple)):
+            count = np.full(np.asarray(rows).shape[0], np.asarray(rows).shape[1], np.int64)
+        r, c = host_rows(rows, count)
+        dev = default_device(device)
+        rows, count = torch.from_numpy(np.ascontiguousarray(r)).to(dev), torch.from_numpy(c.astype(np.int32)).to(dev)
+    if not (isinstance(rows, torch.Tensor) and isinstance(count, torch.Tensor) and rows.is_cuda and count.is_cuda and
+            rows.dtype == torch.float64 and count.dtype == torch.int32 and rows.dim() == 3 and rows.shape[2] == 6 and
+            tuple(count.shape) == (rows.shape[0],)):
+        raise TypeError(text)
+    return rows.contiguous(), count.contiguous(), int(rows.shape[0]), int(rows.shape[1])
+
+
+def check_grids(Y, who, batch="N"):
+    if Y.ndim != 2 or Y.shape[1] % 8 or not Y.shape[1]:
+        raise ValueError("%s expects [%s, 8 n] grids, got %s" % (who, batch, tuple(Y.shape)))
+
+
+def device_grids(Y_denorm, device, who, batch="N"):
+    """De-normalised grids [N, 8 n] as a device tensor: a host array or a tensor elsewhere is uploaded to `device`."""
+    import torch
+    if not isinstance(Y_denorm, torch.Tensor):
+        Y_denorm = torch.from_numpy(np.ascontiguousarray(np.asarray(Y_denorm)))
+    if not Y_denorm.is_cuda:
+        Y_denorm = Y_denorm.to(default_device(device))
+    check_grids(Y_denorm, who, batch)
+    return Y_denorm
 
 
 def ring_masks_device(rows, count=None, H=384, W=512, out=None, device=None):
@@ -193,17 +241,9 @@ def ring_masks_device(rows, count=None, H=384, W=512, out=None, device=None):
     lists (or pad_metadata's pair), which is padded and uploaded.  out: a contiguous uint8 device tensor [B,H,W] to fill."""
     import torch
     from . import _lib as L
-    if not isinstance(rows, torch.Tensor):
-        r, c = _host_rows(rows, count)
-        dev = _default_device(device if out is None else out.device)
-        rows, count = torch.from_numpy(np.ascontiguousarray(r)).to(dev), torch.from_numpy(c.astype(np.int32)).to(dev)
-    if not (isinstance(count, torch.Tensor) and rows.is_cuda and count.is_cuda and rows.dtype == torch.float64 and
-            count.dtype == torch.int32 and rows.dim() == 3 and rows.shape[2] == 6 and tuple(count.shape) == (rows.shape[0],)):
-        raise TypeError("ring_masks_device expects rows float64 [B,K,6] and count int32 [B] on the device")
-    rows, count = rows.contiguous(), count.contiguous()
-    B, K = int(rows.shape[0]), int(rows.shape[1])
+    rows, count, B, K = device_rows(rows, count, device if out is None else out.device, ROWS_TEXT % ("ring_masks_device", "B", "B"))
     H, W = int(H), int(W)
-    _check_size(H, W, K)
+    check_size(H, W, K)
     if out is None:
         out = torch.empty((B, H, W), dtype=torch.uint8, device=rows.device)
     elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == rows.device and
@@ -234,15 +274,8 @@ def masks_from_predictions(Y_denorm, H=384, W=512, device=None):
     """uint8 [B,H,W] device masks of de-normalised grids [B, 576] (host array or tensor on any device): one row per
     predictor (K = 72 in the default grid), built with torch ops on the device and painted by the same kernel."""
     import torch
-    if not isinstance(Y_denorm, torch.Tensor):
-        Y_denorm = torch.from_numpy(np.ascontiguousarray(np.asarray(Y_denorm)))
-    if not Y_denorm.is_cuda:
-        Y_denorm = Y_denorm.to(_default_device(device))
-    if Y_denorm.dim() != 2 or Y_denorm.shape[1] % 8 or not Y_denorm.shape[1]:
-        raise ValueError("masks_from_predictions expects [B, 8 n] grids, got %s" % (tuple(Y_denorm.shape),))
-    rows = prediction_rows(Y_denorm, torch).contiguous()
-    B, K = int(rows.shape[0]), int(rows.shape[1])
-    count = torch.full((B,), K, dtype=torch.int32, device=rows.device)
+    rows = prediction_rows(device_grids(Y_denorm, device, "masks_from_predictions", "B"), torch)
+    count = torch.full((int(rows.shape[0]),), int(rows.shape[1]), dtype=torch.int32, device=rows.device)
     return ring_masks_device(rows, count, H, W)
 
 
@@ -287,7 +320,7 @@ def write_masks(masks, paths, png="pillow", pool=None):
         raise ValueError("write_masks: %d masks, %d paths" % (len(masks), len(paths)))
     if png == "pillow":
         from PIL import Image
-        host = masks.cpu().numpy() if hasattr(masks, "is_cuda") else np.asarray(masks)
+        host = host_array(masks)
         if host.dtype != np.uint8 or host.ndim != 3:
             raise TypeError("write_masks expects uint8 [N,H,W]")
         for m, p in zip(host, paths):
@@ -298,7 +331,7 @@ def write_masks(masks, paths, png="pillow", pool=None):
     if not isinstance(masks, torch.Tensor):
         masks = torch.from_numpy(np.ascontiguousarray(masks, dtype=np.uint8))
     if not masks.is_cuda:
-        masks = masks.to(_default_device(None))
+        masks = masks.to(default_device(None))
     write_png_device(masks, paths, pool=pool, lz77=(png == "device-lz"))
 
 
@@ -321,7 +354,7 @@ def _host_masks(masks):
     if m.dtype != np.uint8 or m.ndim != 3:
         raise TypeError("masks: expected uint8 [B,H,W], got %s %s" % (m.dtype, m.shape))
     if m.shape[0]:
-        _check_size(m.shape[1], m.shape[2])
+        check_size(m.shape[1], m.shape[2])
     return m
 
 
@@ -479,11 +512,11 @@ def _device_masks(masks):
     if not isinstance(masks, torch.Tensor):
         masks = torch.from_numpy(np.ascontiguousarray(_host_masks(masks)))
     if not masks.is_cuda:
-        masks = masks.to(_default_device(None))
+        masks = masks.to(default_device(None))
     if masks.dtype != torch.uint8 or masks.dim() != 3:
         raise TypeError("masks: expected a uint8 tensor [B,H,W], got %s %s" % (masks.dtype, tuple(masks.shape)))
     if masks.shape[0]:
-        _check_size(int(masks.shape[1]), int(masks.shape[2]))
+        check_size(int(masks.shape[1]), int(masks.shape[2]))
     return masks.contiguous()
 
 

@@ -60,7 +60,7 @@ def iou_to_q(iou):
 
 
 def _check(N, K, H, W, max_gap):
-    MK._check_size(H, W, max(K, 1))
+    MK.check_size(H, W, max(K, 1))
     if not (isinstance(max_gap, (int, np.integer)) and 1 <= max_gap <= MAX_GAP):
         raise ValueError("tracks: max_gap is an integer 1 .. %d, got %r" % (MAX_GAP, max_gap))
     if N * K > MAX_FLAT:
@@ -77,20 +77,15 @@ def pair_chunks(N, K, d, ws_bytes):
 # ----------------------------------------------------------------------------- the rule on the host
 def _windows_host(rows, count, H, W):
     """live bool [N,K], area int32 [N,K], and per frame the list of (k, x0, y0, inside) of its rows with a window."""
-    N, K = rows.shape[:2]
-    live, area = np.zeros((N, K), bool), np.zeros((N, K), np.int32)
-    wins = []
-    for t in range(N):
+    live = live_rows_host(rows, count)
+    area, wins = np.zeros(live.shape, np.int32), []
+    for t in range(live.shape[0]):
         ws = []
-        for k in range(min(max(int(count[t]), 0), K)):
-            q = MK.quantise_row(rows[t, k])
-            if q is None:
-                continue
-            live[t, k] = True
-            win = MK._inside_row_host(rows[t, k], H, W, True, q)
+        for k in np.flatnonzero(live[t]):
+            win = MK.inside_row_host(rows[t, k], H, W)
             if win is not None and win[2].any():
                 area[t, k] = int(win[2].sum())
-                ws.append((k,) + win)
+                ws.append((int(k),) + win)
         wins.append(ws)
     return live, area, wins
 
@@ -127,22 +122,27 @@ def _best_host(I, a_self, a_other, open_self, open_other, iou_q):
     return best
 
 
+def _mutual_host(I, area_a, area_b, open_a, open_b, iou_q):
+    """The mutual best of two sides: per row of I [Ka,Kb] its partner j -- the best eligible open column, whose best
+    eligible open row it is -- or -1."""
+    I, area_a, area_b = (np.asarray(v).astype(np.int64) for v in (I, area_a, area_b))
+    fwd = _best_host(I, area_a, area_b, open_a, open_b, iou_q)
+    bwd = _best_host(I.T, area_b, area_a, open_b, open_a, iou_q)
+    hit = np.flatnonzero(fwd >= 0)                          # (an empty side B leaves none: bwd is never indexed)
+    out = np.full(fwd.size, -1, np.int64)
+    out[hit] = np.where(bwd[fwd[hit]] == hit, fwd[hit], -1)
+    return out
+
+
 def _link_host(inter, area, live, t0, d, iou_q, nxt, prv):
     K = area.shape[1]
     for p in range(inter.shape[0]):
         ta, tb = t0 + p, t0 + p + d
-        I = inter[p].astype(np.int64)
-        if not I.any():
+        if not inter[p].any():
             continue
-        aa, ab = area[ta].astype(np.int64), area[tb].astype(np.int64)
-        oa, ob = live[ta] & (nxt[ta] == -1), live[tb] & (prv[tb] == -1)
-        fwd = _best_host(I, aa, ab, oa, ob, iou_q)
-        bwd = _best_host(I.T, ab, aa, ob, oa, iou_q)
-        for i in np.flatnonzero(fwd >= 0):
-            j = fwd[i]
-            if bwd[j] == i:
-                nxt[ta, i] = tb * K + j
-                prv[tb, j] = ta * K + i
+        j = _mutual_host(inter[p], area[ta], area[tb], live[ta] & (nxt[ta] == -1), live[tb] & (prv[tb] == -1), iou_q)
+        i = np.flatnonzero(j >= 0)
+        nxt[ta, i], prv[tb, j[i]] = tb * K + j[i], ta * K + i
 
 
 def _rank_host(prv, live):
@@ -166,7 +166,7 @@ def link_tracks_host(rows, count=None, H=384, W=512, iou=DEFAULT_IOU, max_gap=DE
     (the result does not depend on it).  return_inter: also {d: inter int32 [N-d,K,K]}."""
     if count is None and not isinstance(rows, (list, tuple)):
         count = np.full(np.asarray(rows).shape[0], np.asarray(rows).shape[1], np.int64)
-    rows, count = MK._host_rows(rows, count)
+    rows, count = MK.host_rows(rows, count)
     N, K = rows.shape[:2]
     H, W = int(H), int(W)
     _check(N, K, H, W, max_gap)
@@ -198,20 +198,7 @@ def link_tracks_device(rows, count=None, H=384, W=512, iou=DEFAULT_IOU, max_gap=
     {d: inter int32 [N-d,K,K]} (copies: for tests and inspection, not for a movie)."""
     import torch
     from . import _lib as L
-    if not isinstance(rows, torch.Tensor):
-        if count is None and not isinstance(rows, (list, tuple)):
-            count = np.full(np.asarray(rows).shape[0], np.asarray(rows).shape[1], np.int64)
-        r, c = MK._host_rows(rows, count)
-        dev = MK._default_device(device)
-        rows, count = torch.from_numpy(np.ascontiguousarray(r)).to(dev), torch.from_numpy(c.astype(np.int32)).to(dev)
-    if count is None:
-        count = torch.full((int(rows.shape[0]),), int(rows.shape[1]) if rows.dim() == 3 else 0, dtype=torch.int32,
-                           device=rows.device)
-    if not (isinstance(count, torch.Tensor) and rows.is_cuda and count.is_cuda and rows.dtype == torch.float64 and
-            count.dtype == torch.int32 and rows.dim() == 3 and rows.shape[2] == 6 and tuple(count.shape) == (rows.shape[0],)):
-        raise TypeError("link_tracks_device expects rows float64 [N,K,6] and count int32 [N] on the device")
-    rows, count = rows.contiguous(), count.contiguous()
-    N, K = int(rows.shape[0]), int(rows.shape[1])
+    rows, count, N, K = MK.device_rows(rows, count, device, MK.ROWS_TEXT % ("link_tracks_device", "N", "N"), every_row=True)
     H, W = int(H), int(W)
     _check(N, K, H, W, max_gap)
     iou_q = iou_to_q(iou)
@@ -250,25 +237,17 @@ def tracks_from_predictions(Y_denorm, H=384, W=512, iou=DEFAULT_IOU, max_gap=DEF
     device): one row per predictor through masks.prediction_rows, dead where noobj >= 0.5.  On the GPU (a host array is
     uploaded; rows of a device tensor never leave it) unless host=True, which runs the numpy rule and returns arrays."""
     if host:
-        Y = Y_denorm.cpu().numpy() if hasattr(Y_denorm, "is_cuda") else np.asarray(Y_denorm)
-        if Y.ndim != 2 or Y.shape[1] % 8 or not Y.shape[1]:
-            raise ValueError("tracks_from_predictions expects [N, 8 n] grids, got %s" % (Y.shape,))
+        Y = _host(Y_denorm)
+        MK.check_grids(Y, "tracks_from_predictions")
         rows = np.ascontiguousarray(MK.prediction_rows(Y))
         return (rows,) + link_tracks_host(rows, None, H, W, iou, max_gap, ws_bytes)
     import torch
-    if not isinstance(Y_denorm, torch.Tensor):
-        Y_denorm = torch.from_numpy(np.ascontiguousarray(np.asarray(Y_denorm)))
-    if not Y_denorm.is_cuda:
-        Y_denorm = Y_denorm.to(MK._default_device(device))
-    if Y_denorm.dim() != 2 or Y_denorm.shape[1] % 8 or not Y_denorm.shape[1]:
-        raise ValueError("tracks_from_predictions expects [N, 8 n] grids, got %s" % (tuple(Y_denorm.shape),))
-    rows = MK.prediction_rows(Y_denorm, torch).contiguous()
+    rows = MK.prediction_rows(MK.device_grids(Y_denorm, device, "tracks_from_predictions"), torch).contiguous()
     return (rows,) + link_tracks_device(rows, None, H, W, iou, max_gap, ws_bytes)
 
 
 # ----------------------------------------------------------------------------- tables (numpy on N * K integers)
-def _host(a):
-    return a.cpu().numpy() if hasattr(a, "is_cuda") else np.asarray(a)
+_host = MK.host_array
 
 
 def _kept(rows, track, age, min_len):
@@ -310,20 +289,29 @@ def track_summary(rows, track, age, min_len=1):
     return out
 
 
-def summary_path(path):
+def _suffixed(path, suffix):
     root, ext = os.path.splitext(path)
-    return root + "_summary" + ext
+    return root + suffix + ext
+
+
+def summary_path(path):
+    return _suffixed(path, "_summary")
+
+
+def _write_csv(path, fields, records):
+    """A header line and one line per record: None as an empty field, a float by repr (it reads back exactly)."""
+    with open(path, "w") as f:
+        f.write(",".join(fields) + "\n")
+        for rec in records:
+            f.write(",".join("" if v is None else repr(v) if isinstance(v, float) else str(v) for v in rec) + "\n")
 
 
 def write_tracks(path, rows, track, age, names=None, min_len=1):
     """The table as CSV at `path` and the summary at `path` with _summary before the extension (header lines: TABLE_FIELDS,
     SUMMARY_FIELDS; floats by repr, so they read back exactly).  Returns (table, summary)."""
     table, summary = track_table(rows, track, age, names, min_len), track_summary(rows, track, age, min_len)
-    for p, fields, records in ((path, TABLE_FIELDS, table), (summary_path(path), SUMMARY_FIELDS, summary)):
-        with open(p, "w") as f:
-            f.write(",".join(fields) + "\n")
-            for rec in records:
-                f.write(",".join(repr(v) if isinstance(v, float) else str(v) for v in rec) + "\n")
+    _write_csv(path, TABLE_FIELDS, table)
+    _write_csv(summary_path(path), SUMMARY_FIELDS, summary)
     return table, summary
 
 
@@ -335,13 +323,12 @@ SCORE_FIELDS = ("gt", "tp", "fn", "fp", "switches", "fragments", "mota", "precis
 
 
 def score_path(path):
-    root, ext = os.path.splitext(path)
-    return root + "_score" + ext
+    return _suffixed(path, "_score")
 
 
 def _check_score(N, Kt, Kp, H, W, M):
-    MK._check_size(H, W, max(Kt, 1))
-    MK._check_size(H, W, max(Kp, 1))
+    MK.check_size(H, W, max(Kt, 1))
+    MK.check_size(H, W, max(Kp, 1))
     if N * Kt > MAX_FLAT or N * Kp > MAX_FLAT:
         raise ValueError("tracks: N * K = %d exceeds %d" % (N * max(Kt, Kp), MAX_FLAT))
     if not (isinstance(M, (int, np.integer)) and 1 <= M <= MAX_M):
@@ -370,8 +357,8 @@ def effective_ident_host(live, ident, M):
 def match_tracks_host(rows_t, count_t, ident, rows_p, count_p, track, H=384, W=512, iou=DEFAULT_IOU, M=None):
     """The match rule in numpy (include/spnet_hip.h "Tracking score"): (match int32 [N,Kt], frame_counts int32 [N,3] =
     (tp, fn, fp), eff int32 [N,Kt] the effective identities).  M None: the largest ident."""
-    rows_t, count_t = MK._host_rows(np.asarray(rows_t, np.float64), np.asarray(count_t))
-    rows_p, count_p = MK._host_rows(np.asarray(rows_p, np.float64), np.asarray(count_p))
+    rows_t, count_t = MK.host_rows(np.asarray(rows_t, np.float64), np.asarray(count_t))
+    rows_p, count_p = MK.host_rows(np.asarray(rows_p, np.float64), np.asarray(count_p))
     ident, track = np.asarray(ident).astype(np.int64), np.asarray(track).astype(np.int64)
     N, Kt, Kp = rows_t.shape[0], rows_t.shape[1], rows_p.shape[1]
     if rows_p.shape[0] != N or ident.shape != (N, Kt) or track.shape != (N, Kp):
@@ -388,12 +375,7 @@ def match_tracks_host(rows_t, count_t, ident, rows_p, count_p, track, H=384, W=5
     for n in range(N):
         I = np.zeros((Kt, Kp), np.int64)
         _inter_frames_host(wins_t[n], wins_p[n], I)
-        at, ap = area_t[n].astype(np.int64), area_p[n].astype(np.int64)
-        fwd = _best_host(I, at, ap, open_t[n], open_p[n], iou_q)
-        bwd = _best_host(I.T, ap, at, open_p[n], open_t[n], iou_q)
-        for i in np.flatnonzero(fwd >= 0):
-            if bwd[fwd[i]] == i:
-                match[n, i] = fwd[i]
+        match[n] = _mutual_host(I, area_t[n], area_p[n], open_t[n], open_p[n], iou_q)
         tp = int((match[n] >= 0).sum())
         counts[n] = (tp, int(open_t[n].sum()) - tp, int(open_p[n].sum()) - tp)
     return match, counts, eff
@@ -451,20 +433,15 @@ def score_tracks_device(rows_t, count_t, ident, rows_p, count_p, track, H=384, W
     tensors.  M None: the largest ident (one scalar read back)."""
     import torch
     from . import _lib as L
+    text = ("score_tracks_device expects device tensors: rows float64 [N,K,6], count int32 [N], ident int32 [N,Kt], "
+            "track int32 [N,Kp]")
+    rows_t, count_t, N, Kt = MK.device_rows(rows_t, count_t, None, text, upload=False)
+    rows_p, count_p, Np, Kp = MK.device_rows(rows_p, count_p, None, text, every_row=True, upload=False)
     dev = rows_t.device
-    if count_p is None:
-        count_p = torch.full((int(rows_p.shape[0]),), int(rows_p.shape[1]), dtype=torch.int32, device=dev)
-    f64 = (rows_t, rows_p)
-    i32 = (count_t, ident, count_p, track)
-    if not (all(isinstance(a, torch.Tensor) and a.is_cuda for a in f64 + i32) and all(a.dtype == torch.float64 for a in f64)
-            and all(a.dtype == torch.int32 for a in i32) and rows_t.dim() == 3 and rows_p.dim() == 3 and rows_t.shape[2] == 6
-            and rows_p.shape[2] == 6 and rows_p.shape[0] == rows_t.shape[0] and tuple(ident.shape) == tuple(rows_t.shape[:2])
-            and tuple(track.shape) == tuple(rows_p.shape[:2]) and tuple(count_t.shape) == (rows_t.shape[0],)
-            and tuple(count_p.shape) == (rows_t.shape[0],)):
-        raise TypeError("score_tracks_device expects device tensors: rows float64 [N,K,6], count int32 [N], ident int32 [N,Kt], "
-                        "track int32 [N,Kp]")
-    rows_t, count_t, ident, rows_p, count_p, track = (a.contiguous() for a in (rows_t, count_t, ident, rows_p, count_p, track))
-    N, Kt, Kp = int(rows_t.shape[0]), int(rows_t.shape[1]), int(rows_p.shape[1])
+    if not (Np == N and all(isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.int32 for a in (ident, track))
+            and tuple(ident.shape) == (N, Kt) and tuple(track.shape) == (N, Kp)):
+        raise TypeError(text)
+    ident, track = ident.contiguous(), track.contiguous()
     M = _default_M(ident) if M is None else M
     _check_score(N, Kt, Kp, int(H), int(W), M)
     iou_q = iou_to_q(iou)
@@ -555,13 +532,6 @@ def write_truth_tracks(path, rows, ident, names=None):
     return table
 
 
-def _write_csv(path, fields, records):
-    with open(path, "w") as f:
-        f.write(",".join(fields) + "\n")
-        for rec in records:
-            f.write(",".join(repr(v) if isinstance(v, float) else str(v) for v in rec) + "\n")
-
-
 def read_truth_tracks(path):
     """The records of a truth_tracks.csv (or of any table write_tracks wrote), typed as track_table gives them."""
     with open(path) as f:
@@ -614,9 +584,6 @@ def write_track_score(path, score, ident_stats):
     """The score dictionary at `path` (a header line of SCORE_FIELDS and one line of values; None as an empty field) and the
     per-identity statistics of the identities that are present at `path` with _idents before the extension (STAT_FIELDS)."""
     st = _host(ident_stats).astype(np.int64)
-    with open(path, "w") as f:
-        f.write(",".join(SCORE_FIELDS) + "\n")
-        f.write(",".join("" if score[k] is None else repr(score[k]) if isinstance(score[k], float) else str(score[k])
-                         for k in SCORE_FIELDS) + "\n")
-    root, ext = os.path.splitext(path)
-    _write_csv(root + "_idents" + ext, STAT_FIELDS, [(g,) + tuple(int(v) for v in st[g]) for g in range(1, st.shape[0]) if st[g, 0] > 0])
+    _write_csv(path, SCORE_FIELDS, [[score[k] for k in SCORE_FIELDS]])
+    _write_csv(_suffixed(path, "_idents"), STAT_FIELDS,
+               [(g,) + tuple(int(v) for v in st[g]) for g in range(1, st.shape[0]) if st[g, 0] > 0])

@@ -173,3 +173,14 @@ def test_c6_host_check_program_runs_clean_under_the_sanitizers(tmp_path):
     assert r.returncode == 0 and not r.stderr, (r.stdout[-1000:], r.stderr[-3000:])
     lines = r.stdout.splitlines()
     assert lines[-1] == "all equal" and len(lines) > 100 and all(l.endswith("equal 1") for l in lines[:-1])
+
+
+def test_c8_a_side_without_rows():
+    """K = 0 on either side is admitted by the host rule: nothing matches, every open row of the other side is a miss."""
+    E = (20, 20, 10, 6, 30, 2.0)
+    rows, count, ident = np.asarray([[E], [E]], np.float64), np.asarray([1, 1]), np.asarray([[1], [1]])
+    none_r, none_i = np.zeros((2, 0, 6)), np.zeros((2, 0), np.int64)
+    match, counts, stats = TK.score_tracks_host(rows, count, ident, none_r, np.zeros(2, np.int64), none_i, 48, 80, M=1)
+    assert match.tolist() == [[-1], [-1]] and counts.tolist() == [[0, 1, 0]] * 2 and stats.tolist() == [[0] * 5, [2, 0, 0, 0, -1]]
+    match, counts, stats = TK.score_tracks_host(none_r, np.zeros(2, np.int64), none_i, rows, count, ident + 4, 48, 80, M=1)
+    assert match.shape == (2, 0) and counts.tolist() == [[0, 0, 1]] * 2 and stats.tolist() == [[0] * 5, [0, 0, 0, 0, -1]]

@@ -1,11 +1,11 @@
 // The mutual-best and identity steps of spnet_amd/csrc/track_score.hip over plain arrays: what track_match_kernel,
-// ident_range_kernel and ident_walk_kernel do, with the workgroups and lanes in loops -- the same effective_ident /
-// match_choose_truth / match_choose_pred / match_mutual / ident_walk of csrc/track_score_core.h -- over heap blocks of
-// their exact size, so that a read or write outside inter, the areas, ident, track, match, eff or ident_stats is an
-// AddressSanitizer report, and an overflowing product a UBSan report.  Beside each, a plain restatement is the oracle: an
-// all-pairs search with 128-bit cross products for the mutual best, and for an identity the list of its frames built first
-// and then read off.  The inputs are seeded, and hostile on purpose: idents below 0 and above M, duplicates, tracks of any
-// value, counts that are no counts, match entries that are no indices.
+// ident_range_kernel and ident_walk_kernel do, with the workgroups and lanes in loops -- the same effective_ident and
+// ident_walk of csrc/track_score_core.h and mutual_choose_a / mutual_choose_b / mutual_partner of csrc/tracks_core.h --
+// over heap blocks of their exact size, so that a read or write outside inter, the areas, ident, track, match, eff or
+// ident_stats is an AddressSanitizer report, and an overflowing product a UBSan report.  Beside each, a plain
+// restatement is the oracle: an all-pairs search with 128-bit cross products for the mutual best, and for an identity
+// the list of its frames built first and then read off.  The inputs are seeded, and hostile on purpose: idents below 0
+// and above M, duplicates, tracks of any value, counts that are no counts, match entries that are no indices.
 //
 //   track_score_host_check         the built-in battery; prints "case NAME ... equal 1" per case and "all equal" at the
 //                                  end; exit status 1 on the first difference
@@ -99,11 +99,11 @@ int run_case(const char* name, int N, int Kt, int Kp, int M, int iou_q, bool hug
       open_t[k] = eff[(long)n * Kt + k] ? 1 : 0;
     }
     for (int k = 0; k < Kp; ++k) open_p[k] = (live_p[(long)n * Kp + k] && track[(long)n * Kp + k] > 0) ? 1 : 0;
-    for (int k = Kt - 1; k >= 0; --k) fwd[k] = match_choose_truth(in, Kp, k, area_t + (long)n * Kt, area_p + (long)n * Kp, open_t, open_p, iou_q);
-    for (int k = Kp - 1; k >= 0; --k) bwd[k] = match_choose_pred(in, Kt, Kp, k, area_t + (long)n * Kt, area_p + (long)n * Kp, open_t, open_p, iou_q);
+    for (int k = Kt - 1; k >= 0; --k) fwd[k] = tracks::mutual_choose_a(in, Kp, k, area_t + (long)n * Kt, area_p + (long)n * Kp, open_t, open_p, iou_q);
+    for (int k = Kp - 1; k >= 0; --k) bwd[k] = tracks::mutual_choose_b(in, Kt, Kp, k, area_t + (long)n * Kt, area_p + (long)n * Kp, open_t, open_p, iou_q);
     int tp = 0, nt = 0, np = 0;
     for (int k = 0; k < Kt; ++k) {
-      match[(long)n * Kt + k] = match_mutual(fwd, bwd, Kp, k);
+      match[(long)n * Kt + k] = tracks::mutual_partner(fwd, bwd, Kp, k);
       tp += match[(long)n * Kt + k] >= 0;
       nt += open_t[k];
     }

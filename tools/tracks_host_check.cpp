@@ -1,5 +1,5 @@
 // The link and rank steps of spnet_amd/csrc/tracks.hip over plain arrays: what track_link_kernel and the track_rank_*
-// kernels do, with the workgroups and lanes in loops -- the same link_choose_forward / link_choose_backward / link_mutual /
+// kernels do, with the workgroups and lanes in loops -- the same mutual_choose_a / mutual_choose_b / mutual_partner /
 // rank_init / rank_jump of csrc/tracks_core.h -- over heap blocks of their exact size, so that a read or write outside
 // inter, area, next, prev or the ping-pong halves is an AddressSanitizer report, and an overflowing product a UBSan report.
 // Beside each, a plain restatement is the oracle: an all-pairs search with 128-bit cross products for the mutual best, a
@@ -24,16 +24,16 @@ unsigned rng() { rng_state = rng_state * 1664525u + 1013904223u; return rng_stat
 template <class T>
 T* exact(size_t n) { return (T*)malloc(sizeof(T) * (n ? n : 1)); }
 
-// ---- one frame pair as the kernel runs it: all lanes choose, then (the barrier) the mutual test
-void link_as_the_device_does(const int* inter, int K, const int* area_a, const int* area_b, const unsigned char* open_a,
+// ---- one frame pair as the kernel runs it (Ka = Kb there): all lanes choose, then (the barrier) the mutual test
+void link_as_the_device_does(const int* inter, int Ka, int Kb, const int* area_a, const int* area_b, const unsigned char* open_a,
                              const unsigned char* open_b, int iou_q, int* link_of_i) {
-  int* fwd = exact<int>(K);
-  int* bwd = exact<int>(K);
-  for (int tid = 2 * K - 1; tid >= 0; --tid) {                          // any lane order: the choices are independent
-    if (tid < K) fwd[tid] = link_choose_forward(inter, K, tid, area_a, area_b, open_a, open_b, iou_q);
-    else bwd[tid - K] = link_choose_backward(inter, K, tid - K, area_a, area_b, open_a, open_b, iou_q);
+  int* fwd = exact<int>(Ka);
+  int* bwd = exact<int>(Kb);
+  for (int tid = Ka + Kb - 1; tid >= 0; --tid) {                        // any lane order: the choices are independent
+    if (tid < Ka) fwd[tid] = mutual_choose_a(inter, Kb, tid, area_a, area_b, open_a, open_b, iou_q);
+    else bwd[tid - Ka] = mutual_choose_b(inter, Ka, Kb, tid - Ka, area_a, area_b, open_a, open_b, iou_q);
   }
-  for (int i = 0; i < K; ++i) link_of_i[i] = link_mutual(fwd, bwd, K, i);
+  for (int i = 0; i < Ka; ++i) link_of_i[i] = mutual_partner(fwd, bwd, Kb, i);
   free(fwd);
   free(bwd);
 }
@@ -59,39 +59,41 @@ int ref_best(const int* inter, long stride, int n, int a_self, const int* a_othe
   return -1;
 }
 
-bool link_case(const char* name, int K, int iou_q, int mode) {
-  int* inter = exact<int>((size_t)K * K);
-  int *aa = exact<int>(K), *ab = exact<int>(K), *got = exact<int>(K);
-  unsigned char *oa = exact<unsigned char>(K), *ob = exact<unsigned char>(K);
-  for (int k = 0; k < K; ++k) {
+bool link_case(const char* name, int Ka, int Kb, int iou_q, int mode) {
+  int* inter = exact<int>((size_t)Ka * Kb);
+  int *aa = exact<int>(Ka), *ab = exact<int>(Kb), *got = exact<int>(Ka);
+  unsigned char *oa = exact<unsigned char>(Ka), *ob = exact<unsigned char>(Kb);
+  for (int k = 0; k < Ka; ++k) {
     aa[k] = mode == 2 ? 0x7fffffff : 1 + (int)(rng() % 400u);
-    ab[k] = mode == 2 ? 0x7fffffff : 1 + (int)(rng() % 400u);
     oa[k] = rng() % 4u != 0;
+  }
+  for (int k = 0; k < Kb; ++k) {
+    ab[k] = mode == 2 ? 0x7fffffff : 1 + (int)(rng() % 400u);
     ob[k] = rng() % 4u != 0;
   }
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) {
+  for (int i = 0; i < Ka; ++i)
+    for (int j = 0; j < Kb; ++j) {
       int v;
       if (mode == 0) v = (rng() % 3u) ? 0 : (int)(rng() % (unsigned)((aa[i] < ab[j] ? aa[i] : ab[j]) + 1));   // true counts
       else if (mode == 1) v = (int)(rng() % 5u) * ((aa[i] < ab[j] ? aa[i] : ab[j]) / 4);                       // many exact ties
       else v = (int)(rng() << 8 ^ rng());                                                                      // hostile
-      inter[i * K + j] = v;
+      inter[i * Kb + j] = v;
     }
-  link_as_the_device_does(inter, K, aa, ab, oa, ob, iou_q, got);
+  link_as_the_device_does(inter, Ka, Kb, aa, ab, oa, ob, iou_q, got);
   bool equal = true;
   int links = 0;
-  for (int i = 0; i < K; ++i) {
+  for (int i = 0; i < Ka; ++i) {
     int want = -1;
     if (oa[i]) {
-      const int j = ref_best(inter + (long)i * K, 1, K, aa[i], ab, ob, iou_q);
-      if (j >= 0 && ref_best(inter + j, K, K, ab[j], aa, oa, iou_q) == i) want = j;
+      const int j = ref_best(inter + (long)i * Kb, 1, Kb, aa[i], ab, ob, iou_q);
+      if (j >= 0 && ref_best(inter + j, Kb, Ka, ab[j], aa, oa, iou_q) == i) want = j;
     }
     equal = equal && got[i] == want;
     links += want >= 0;
   }
-  for (int i = 0; i < K && equal; ++i)                                   // at most one predecessor
-    for (int o = i + 1; o < K; ++o) equal = equal && (got[i] < 0 || got[i] != got[o]);
-  printf("case link %s K %d iou_q %d links %d equal %d\n", name, K, iou_q, links, equal ? 1 : 0);
+  for (int i = 0; i < Ka && equal; ++i)                                  // at most one predecessor
+    for (int o = i + 1; o < Ka; ++o) equal = equal && (got[i] < 0 || got[i] != got[o]);
+  printf("case link %s Ka %d Kb %d iou_q %d links %d equal %d\n", name, Ka, Kb, iou_q, links, equal ? 1 : 0);
   free(inter); free(aa); free(ab); free(got); free(oa); free(ob);
   return equal;
 }
@@ -157,10 +159,14 @@ int main() {
   const int qs[] = {1, 256, 1024};
   for (int K : ks)
     for (int q : qs) {
-      ok = link_case("counts", K, q, 0) && ok;
-      ok = link_case("ties", K, q, 1) && ok;
-      ok = link_case("hostile", K, q, 2) && ok;
+      ok = link_case("counts", K, K, q, 0) && ok;
+      ok = link_case("ties", K, K, q, 1) && ok;
+      ok = link_case("hostile", K, K, q, 2) && ok;
     }
+  for (int mode = 0; mode < 3; ++mode) {                                 // a rectangle, both ways: the score's use of the matcher
+    ok = link_case("rectangle", 7, 128, 256, mode) && ok;
+    ok = link_case("rectangle", 72, 3, 256, mode) && ok;
+  }
   const int ns[] = {1, 2, 3, 4, 5, 8, 9, 33, 40, 64, 65, 257};
   for (int N : ns) {
     ok = rank_case("chains", N, 3, 0) && ok;

@@ -155,23 +155,33 @@ int spnet_conv3x3_wgrad(const float* x, const float* dy, float* dw, int B, int H
 /* njobs matrix transposes in one launch: dst_j[c][r] = src_j[r][c]; jobs: DEVICE array of {src, dst, R, C}
  * (four 64-bit words per job).  The engine keeps W^T of the pointwise kernels whose data-gradient product
  * dX = dY W^T (keras SeparableConv2D / Conv2D(1x1), call site spnet/models.py:357-359) runs through
- * spnet_gemm_f32_bnblend, which takes B in the forward (output-major) form; refreshed once per optimizer step. */
+ * spnet_gemm_f32_bnblend, which takes B in the forward (output-major) form; refreshed once per optimizer step.
+ * max_rows / max_cols: the largest R / C of the table (they size the grid; tiles beyond a job's own extent write nothing).
+ * hipErrorInvalidValue, nothing launched: jobs NULL, njobs < 1 or > 65535, max_rows < 1 or > 65535 * 32, max_cols < 1. */
 int spnet_transpose_batched(const void* jobs, int njobs, int max_rows, int max_cols, void* stream);
 /* out[M][ldc] = sum over nslab slabs of M*N floats, in slab order (the second stage of every K split). */
 int spnet_reduce_slabs(const float* ws, int nslab, int M, int N, float* out, int ldc, void* stream);
-/* Even-pixel gather / scatter-add: TF 'same' 1x1 stride-2 residual convs of Xception blocks 2,3,4,13. */
+/* Even-pixel gather / scatter-add: TF 'same' 1x1 stride-2 residual convs of Xception blocks 2,3,4,13.
+ * xs[b][oh][ow][:] = x[b][2oh][2ow][:] and dx[b][2oh][2ow][:] += dxs[b][oh][ow][:] over ceil(H/2) x ceil(W/2) pixels; the
+ * other pixels of dx are neither read nor written.  hipErrorInvalidValue, nothing launched: a NULL pointer, B, H or W < 1,
+ * C < 4 or C % 4. */
 int spnet_gather_s2(const float* x, float* xs, int B, int H, int W, int C, void* stream);
 int spnet_scatter_add_s2(const float* dxs, float* dx, int B, int H, int W, int C, void* stream);
 
 /* ---- depthwise 3x3 / SAME (34 stride-1 layers per Xception forward: keras SeparableConv2D depthwise step;
  *      MobileNet's DepthwiseConv2D, stride 1 | 2).  w is [3][3][C]. ---- */
+/* out[l] = sum over p < P of in[p][l], in a fixed order.  hipErrorInvalidValue, nothing launched: in or out NULL,
+ * P < 1, L < 1. */
 int spnet_reduce_rows(const float* in, int P, int L, float* out, void* stream);
 /* ... with 32*L floats of scratch: many rows (a Conv2D bias gradient: keras InceptionResNetV2's block convs,
- * spnet/models.py:357-359) are folded in 32 parallel slices first. */
+ * spnet/models.py:357-359) are folded in 32 parallel slices first (P > 128).  scratch NULL with scratch_floats == 0: one
+ * pass, as spnet_reduce_rows.  Refused like spnet_reduce_rows, and: scratch with scratch_floats < 32 * L, scratch NULL
+ * with scratch_floats != 0. */
 int spnet_reduce_rows_ws(const float* in, int P, int L, float* out, float* scratch, long scratch_floats, void* stream);
 /* njobs independent row reductions in one launch; jobs: DEVICE array of {in, out, P, L} (four 64-bit words
  * per job), max_L = largest L.  (All depthwise weight gradients of a step: spnet_dwconv3x3_tiled_bwd with
- * dw == NULL leaves its partial sums in the workspace.) */
+ * dw == NULL leaves its partial sums in the workspace.)  A job whose L is below max_L leaves the surplus workgroups
+ * idle.  hipErrorInvalidValue, nothing launched: jobs NULL, njobs < 1 or > 65535, max_L < 1. */
 int spnet_reduce_rows_batched(const void* jobs, int njobs, int max_L, void* stream);
 /* Strided depthwise 3x3 / TF-SAME (keras.applications.mobilenet DepthwiseConv2D, strides 1 or 2; spnet/models.py:346-355).
  * op 0: out = y [B][ceil(H/s)][ceil(W/s)][C] from a = x, b = w;  op 1: out = dx [B][H][W][C] from a = dy, b = w;
@@ -417,25 +427,35 @@ int spnet_decode(const float* y_norm, const float* means, const float* ranges, f
 
 /* ---- evaluation metric (spnet/diagnostics.py:64-161: compute_iou / calc_map) ----------------------------- */
 /* Raster IoU of npairs (predicted, true) ellipse rows [npairs][8] (denormalised cx,cy,a,b,cos2t,sin2t,noobj,
- * rings) on an nx x ny canvas; iou[i] = -1 where the true slot is empty or both rasters are. */
+ * rings) on an nx x ny canvas; iou[i] = -1 where the true slot is empty (noobj > 0.99) or both rasters are; a predictor
+ * with noobj >= 0.5, a <= 0 or b <= 0 has an empty raster.  hipErrorInvalidValue, nothing launched: a NULL pointer,
+ * npairs < 1 or >= 2^31, nx or ny < 1 or > 32768 (a union box of nx * ny <= 2^30 pixels is counted in int). */
 int spnet_ellipse_iou(const float* yp, const float* yt, long npairs, int nx, int ny, double* iou, void* stream);
 
 /* Count metrics (spnet/diagnostics.py:13-59: calc_errors) over [N][ncols] de-normalised grids: counts[7] (int, zeroed
  * by the caller) = ring_miscounts, ring_truecounts, total_obj, false_obj_pos, false_obj_neg, true_obj_pos,
- * true_obj_neg; pix_err[N] = centre error of each row's first predictor. */
+ * true_obj_neg; pix_err[N] = centre error of each row's first predictor.  The counts are ADDED to counts[].  noobj is
+ * rounded half to even; a ring count differs when |difference| > 0.5.  hipErrorInvalidValue, nothing launched: a NULL
+ * pointer, N < 1, ncols < 8 or ncols % 8. */
 int spnet_calc_errors(const float* yp, const float* yt, long N, int ncols, int* counts, float* pix_err, void* stream);
 
 /* ---- optimizer ---------------------------------------------------------------------------------- */
 /* Keras Adam + l2 on the first l2_n elements (spnet/models.py:494, 47-71).  sq_scratch >= 2048 floats.
  * mask (or NULL): n floats, 0 = frozen element (layer.trainable=False, spnet/models.py:361-373).
- * lr_t_dev (or NULL): device float overriding lr_t, so a captured hipGraph of the step can be replayed. */
+ * lr_t_dev (or NULL): device float overriding lr_t, so a captured hipGraph of the step can be replayed.
+ * sq_scratch and l2_loss_out may be NULL (no penalty is reported); n == 0 updates nothing and reports a penalty of 0.
+ * hipErrorInvalidValue, nothing launched: p, g, m or v NULL, n < 0, n % 4. */
 int spnet_adam_step(float* p, const float* g, float* m, float* v, long n, long l2_n, float lr_t,
                     float beta1, float beta2, float eps, float l2, float grad_scale, const float* mask,
                     float* sq_scratch, float* l2_loss_out, const float* lr_t_dev, void* stream);
 /* The same step over a RANGE of the flat buffers (pointers to the range's first element, n % 4 == 0, l2_n = how many of
  * its leading elements are l2-regularised): the Dense head's range is updated as soon as its gradient is final, underneath
  * the backbone's backward; the rest when backward has ended.  Leaves spnet_adam_parts(n) sum-of-squares partials in
- * sq_partial; spnet_adam_l2_sum folds the partials of every range of a step into l2_loss_out[0] = l2 * sum(w^2). */
+ * sq_partial; spnet_adam_l2_sum folds the partials of every range of a step into l2_loss_out[0] = l2 * sum(w^2).
+ * spnet_adam_parts(n) = min(2048, ceil(n / 1024)), 0 for n < 4; workgroup b of a range sums the float4 items
+ * b * 256 + t + k * 256 * parts (t < 256, k = 0, 1, ..) into sq_partial[b].  spnet_adam_part refuses (hipErrorInvalidValue,
+ * nothing launched) p, g, m or v NULL, n < 4 and n % 4: the caller skips an empty range.  spnet_adam_l2_sum refuses a
+ * NULL pointer, count < 1 and count > 32768 (the partials of 16 full ranges). */
 long spnet_adam_parts(long n);
 int spnet_adam_part(float* p, const float* g, float* m, float* v, long n, long l2_n, float lr_t, float beta1, float beta2,
                     float eps, float l2, float grad_scale, const float* mask, float* sq_partial, const float* lr_t_dev,

@@ -883,13 +883,14 @@ __global__ __launch_bounds__(256) void reduce_rows_batched_kernel(const long lon
 
 // max_L: the largest L_j (sizes the grid).
 extern "C" int spnet_reduce_rows_batched(const void* jobs, int njobs, int max_L, void* stream) {
-  if (!jobs || njobs < 1 || max_L < 1) return (int)hipErrorInvalidValue;
+  if (!jobs || njobs < 1 || njobs > 65535 || max_L < 1) return (int)hipErrorInvalidValue;   // njobs is the grid's y extent
   hipLaunchKernelGGL(reduce_rows_batched_kernel, dim3((max_L + 15) / 16, njobs), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const long long*>(jobs));
   SPNET_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int spnet_reduce_rows(const float* in, int P, int L, float* out, void* stream) {
+  if (!in || !out || P < 1 || L < 1) return (int)hipErrorInvalidValue;
   launch_reduce_rows(in, P, L, out, nullptr, (hipStream_t)stream);
   SPNET_RETURN_LAUNCH_STATUS();
 }
@@ -898,7 +899,8 @@ extern "C" int spnet_reduce_rows(const float* in, int P, int L, float* out, void
 // over tens of thousands of pixels otherwise runs on L/16 workgroups only).
 extern "C" int spnet_reduce_rows_ws(const float* in, int P, int L, float* out, float* scratch, long scratch_floats,
                                     void* stream) {
-  if (scratch && scratch_floats < 32L * L) return (int)hipErrorInvalidValue;
+  if (!in || !out || P < 1 || L < 1) return (int)hipErrorInvalidValue;
+  if (scratch ? scratch_floats < 32L * L : scratch_floats != 0) return (int)hipErrorInvalidValue;
   launch_reduce_rows(in, P, L, out, scratch, (hipStream_t)stream);
   SPNET_RETURN_LAUNCH_STATUS();
 }

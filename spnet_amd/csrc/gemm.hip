@@ -721,13 +721,14 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(const long long*
 
 extern "C" int spnet_transpose_batched(const void* jobs, int njobs, int max_rows, int max_cols, void* stream) {
   if (!jobs || njobs < 1 || max_rows < 1 || max_cols < 1) return (int)hipErrorInvalidValue;
+  if (njobs > 65535 || max_rows > 65535 * 32) return (int)hipErrorInvalidValue;   // the grid's z and y extents
   hipLaunchKernelGGL(transpose_batched_kernel, dim3((max_cols + 31) / 32, (max_rows + 31) / 32, njobs), dim3(256), 0,
                      (hipStream_t)stream, reinterpret_cast<const long long*>(jobs));
   SPNET_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int spnet_gather_s2(const float* x, float* xs, int B, int H, int W, int C, void* stream) {
-  if (C & 3) return (int)hipErrorInvalidValue;
+  if (!x || !xs || B < 1 || H < 1 || W < 1 || C < 4 || (C & 3)) return (int)hipErrorInvalidValue;
   const int OH = (H + 1) / 2, OW = (W + 1) / 2;
   const long total = (long)B * OH * OW * (C / 4);
   hipLaunchKernelGGL(gather_s2_kernel, dim3(spnet_ew_grid(total, 256)), dim3(256), 0,
@@ -737,7 +738,7 @@ extern "C" int spnet_gather_s2(const float* x, float* xs, int B, int H, int W, i
 
 extern "C" int spnet_scatter_add_s2(const float* dxs, float* dx, int B, int H, int W, int C,
                                     void* stream) {
-  if (C & 3) return (int)hipErrorInvalidValue;
+  if (!dxs || !dx || B < 1 || H < 1 || W < 1 || C < 4 || (C & 3)) return (int)hipErrorInvalidValue;
   const int OH = (H + 1) / 2, OW = (W + 1) / 2;
   const long total = (long)B * OH * OW * (C / 4);
   hipLaunchKernelGGL(scatter_add_s2_kernel, dim3(spnet_ew_grid(total, 256)), dim3(256), 0,

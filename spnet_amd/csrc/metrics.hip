@@ -80,9 +80,12 @@ __global__ __launch_bounds__(256) void ellipse_iou_kernel(const float* __restric
 }
 
 // yp / yt: [npairs][8] DENORMALISED predictor rows (cx, cy, a, b, cos2t, sin2t, noobj, rings); iou: npairs doubles.
+// nx, ny <= ELLIPSE_MAX_EXTENT: a union box holds at most nx * ny <= 2^30 pixels, which the kernel counts in int.
+#define ELLIPSE_MAX_EXTENT 32768
 extern "C" int spnet_ellipse_iou(const float* yp, const float* yt, long npairs, int nx, int ny, double* iou,
                                  void* stream) {
-  if (!yp || !yt || !iou || npairs < 1 || nx < 1 || ny < 1 || npairs > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  if (!yp || !yt || !iou || npairs < 1 || nx < 1 || ny < 1 || npairs > 0x7fffffffL ||
+      nx > ELLIPSE_MAX_EXTENT || ny > ELLIPSE_MAX_EXTENT) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(ellipse_iou_kernel, dim3((unsigned)npairs), dim3(256), 0, (hipStream_t)stream, yp, yt, nx, ny, iou);
   SPNET_RETURN_LAUNCH_STATUS();
 }
@@ -124,7 +127,7 @@ __global__ __launch_bounds__(256) void calc_errors_kernel(const float* __restric
 
 extern "C" int spnet_calc_errors(const float* yp, const float* yt, long N, int ncols, int* counts, float* pix_err,
                                  void* stream) {
-  if (N < 1 || ncols < 8 || (ncols & 7) || !counts || !pix_err) return (int)hipErrorInvalidValue;
+  if (N < 1 || ncols < 8 || (ncols & 7) || !yp || !yt || !counts || !pix_err) return (int)hipErrorInvalidValue;
   const long npairs = N * (ncols / 8);
   hipLaunchKernelGGL(calc_errors_kernel, dim3(spnet_ew_grid(npairs, 256)), dim3(256), 0, (hipStream_t)stream, yp, yt,
                      npairs, ncols / 8, counts, pix_err);

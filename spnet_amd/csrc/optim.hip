@@ -105,20 +105,23 @@ extern "C" int spnet_adam_part(float* p, const float* g, float* m, float* v, lon
                      beta2, eps, l2, grad_scale, mask, sq_partial, lr_t_dev);
   SPNET_RETURN_LAUNCH_STATUS();
 }
-// l2_loss_out[0] = l2 * sum of `count` partials (double accumulation, fixed order)
+// l2_loss_out[0] = l2 * sum of `count` partials (double accumulation, fixed order).  One workgroup folds them: count is
+// capped at ADAM_L2_MAX_PARTS, the partials of 16 full ranges.
+#define ADAM_L2_MAX_PARTS (16 * ADAM_BLOCKS)
 extern "C" int spnet_adam_l2_sum(const float* sq_partial, int count, float l2, float* l2_loss_out, void* stream) {
-  if (!sq_partial || !l2_loss_out || count < 1) return (int)hipErrorInvalidValue;
+  if (!sq_partial || !l2_loss_out || count < 1 || count > ADAM_L2_MAX_PARTS) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sq_partial, count, l2, l2_loss_out);
   SPNET_RETURN_LAUNCH_STATUS();
 }
 
-// n must be a multiple of 4 (the flat buffer is padded).  sq_scratch: ADAM_BLOCKS floats.
+// n >= 0 must be a multiple of 4 (the flat buffer is padded; n == 0 updates nothing and leaves a penalty of 0).
+// sq_scratch: ADAM_BLOCKS floats.
 // l2_loss_out[0] = l2 * sum_{i<l2_n} p_i^2 evaluated BEFORE the update (the penalty of this step's loss).
 extern "C" int spnet_adam_step(float* p, const float* g, float* m, float* v, long n, long l2_n,
                                float lr_t, float beta1, float beta2, float eps, float l2,
                                float grad_scale, const float* mask, float* sq_scratch,
                                float* l2_loss_out, const float* lr_t_dev, void* stream) {
-  if (n & 3) return (int)hipErrorInvalidValue;
+  if (n < 0 || (n & 3) || !p || !g || !m || !v) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   long g4 = (n / 4 + 255) / 256;
   int grid = (int)(g4 > ADAM_BLOCKS ? ADAM_BLOCKS : (g4 < 1 ? 1 : g4));

@@ -18,7 +18,9 @@ the device from the parameter arrays the frames were rasterised from, or from th
 loaders glob X/*.png only and do not see the sub-directory).  Without a GPU the script stops, as before; only --masks
 then still runs, on the host generator's frames (fake_espi.generate, the reference-ordered stream) and the host mask rule,
 and says so.  --strike S --strike_frames T [--strike_jitter J] [--movie]: instead of a data set, S movies of T frames with
-known tracks (gen_strike below), for predict_spnet.py --tracks --track_truth.
+known tracks (gen_strike below), for predict_spnet.py --tracks --track_truth.  --audio [--audio_rate R] [--audio_fps F]
+[--audio_lag FRAMES] [--audio_noise LSB] (with --strike): also the strike's SOUND with known onsets -- strike_NNNN.wav,
+strike_NNNN/notes.csv and strike_NNNN/truth_audio.csv -- for predict_spnet.py --tracks --audio --notes.
 
 The PNGs are encoded (by default) and written by at most 16 threads of this process; nothing is forked once the GPU is
 initialised."""
@@ -137,12 +139,16 @@ def gen_dataset(datapath=".", numframes=500, everything=False, seed=0, count_ran
 
 
 def gen_strike(datapath=".", sequences=1, frames=64, jitter=0, seed=0, count_range=(1, 7), device="cuda:0", threads=None,
-               device_png=False, device_png_lz=False, movie=False, movie_fps=5.0):
+               device_png=False, device_png_lz=False, movie=False, movie_fps=5.0, audio=False, audio_rate=48000, audio_fps=200.0,
+               audio_lag=4, audio_noise=8):
     """Strike movies with known tracks (spnet_amd.fake_espi.generate_strike_device): for sequence s the directory
     datapath/strike_NNNN with steelpan_NNNNNNN.png + .csv per frame in time order -- the loaders' own format -- and
     truth_tracks.csv (spnet_amd.tracks.write_truth_tracks: `track` is the identity, `age` the frames since it first
     appeared); movie: also datapath/strike_NNNN.avi, the frames as a grey Motion-JPEG movie encoded on the GPU.  Returns per
-    sequence the truth table."""
+    sequence the truth table.  audio: also the sequence's sound (fake_espi.strike_audio_host, host numpy: every antinode is a
+    note that becomes audible audio_lag frames after its rings appear, the struck one at once) as datapath/strike_NNNN.wav,
+    PCM16 at audio_rate with audio_fps movie frames a second; strike_NNNN/notes.csv (name, freq_hz and the antinode's frame-0
+    centre cx, cy); strike_NNNN/truth_audio.csv (ident, name, freq_hz, video_onset, audio_onset at audio.DEFAULT_ONSET_FRAC)."""
     import torch
     from spnet_amd import fake_espi as F
     from spnet_amd import tracks as TK
@@ -172,6 +178,17 @@ def gen_strike(datapath=".", sequences=1, frames=64, jitter=0, seed=0, count_ran
                 j.result()
             tables.append(TK.write_truth_tracks(os.path.join(root, "truth_tracks.csv"), rows, ident,
                                                 [os.path.basename(st) + ".png" for st in stems]))
+            if audio:
+                from spnet_amd import audio as AU
+                _, n0, c0 = (a.cpu().numpy() for a in F.draw_params_device(1, seed, device, count_range, first_frame=s))
+                pcm, info = F.strike_audio_host(n0, c0, T, seed, first_sequence=s, rate=audio_rate, fps=audio_fps,
+                                                lag=audio_lag, noise=audio_noise)
+                AU.write_wav(root + ".wav", pcm[0], audio_rate)
+                AU.write_notes(os.path.join(root, "notes.csv"),
+                               [(info["name"][0][j], float(info["freq"][0, j]), float(n0[0, j, 0]), float(n0[0, j, 1]))
+                                for j in np.flatnonzero(info["valid"][0])])
+                TK._write_csv(os.path.join(root, "truth_audio.csv"), F.TRUTH_AUDIO_FIELDS,
+                              F.strike_audio_truth(info, 0, T, first_sequence=s))
             if movie:
                 from spnet_amd.jpeg import MjpegWriter
                 with MjpegWriter(root + ".avi", F.IM_W, F.IM_H, fps=movie_fps, channels=1) as w:
@@ -227,14 +244,30 @@ def main(argv=None):
     p.add_argument('--strike_jitter', type=int, default=0, metavar='J',
                    help="the centres move by up to J whole pixels from frame to frame, 0 .. 8")
     p.add_argument('--movie', action='store_true', help="(with --strike) also DIR/strike_NNNN.avi, Motion-JPEG encoded on the GPU")
+    p.add_argument('--audio', action='store_true',
+                   help="(with --strike) also the strike's sound with known onsets: DIR/strike_NNNN.wav (PCM16, one channel), "
+                        "DIR/strike_NNNN/notes.csv and DIR/strike_NNNN/truth_audio.csv; every antinode is a note that becomes "
+                        "audible --audio_lag frames after its rings appear, the struck one at once")
+    p.add_argument('--audio_rate', type=int, default=48000, help="samples per second of --audio, at least 16000")
+    p.add_argument('--audio_fps', type=float, default=200.0, help="movie frames per second that --audio is synchronous with")
+    p.add_argument('--audio_lag', type=int, default=4, metavar='FRAMES',
+                   help="frames by which a sympathetic note's sound follows its rings, 0 .. 64 (put in by construction: it shows "
+                        "what the lag analysis recovers, nothing about a drum)")
+    p.add_argument('--audio_noise', type=int, default=8, metavar='LSB', help="uniform noise of +- this many LSB on --audio, 0 .. 1024")
     args = p.parse_args(argv)
+    if args.audio and args.strike is None:
+        p.error("--audio goes with --strike")
+    if args.audio and not (args.audio_rate >= 16000 and args.audio_fps > 0 and 0 <= args.audio_lag <= 64
+                           and 0 <= args.audio_noise <= 1024):
+        p.error("--audio_rate is at least 16000, --audio_fps above 0, --audio_lag 0 .. 64 and --audio_noise 0 .. 1024")
     if args.strike is not None:
         if args.strike < 0 or not 1 <= args.strike_frames <= 4096 or not 0 <= args.strike_jitter <= 8:
             p.error("--strike is at least 0, --strike_frames 1 .. 4096 and --strike_jitter 0 .. 8")
         if args.bp_real or args.bp_path or args.host_params or args.masks or args.all:
-            p.error("--strike combines with --seed, --count_range, --device_png, --device_png_lz and --movie only")
+            p.error("--strike combines with --seed, --count_range, --device_png, --device_png_lz, --movie and --audio only")
         return gen_strike(args.datapath, args.strike, args.strike_frames, args.strike_jitter, args.seed, tuple(args.count_range),
-                          device_png=args.device_png, device_png_lz=args.device_png_lz, movie=args.movie)
+                          device_png=args.device_png, device_png_lz=args.device_png_lz, movie=args.movie, audio=args.audio,
+                          audio_rate=args.audio_rate, audio_fps=args.audio_fps, audio_lag=args.audio_lag, audio_noise=args.audio_noise)
     if args.movie:
         p.error("--movie goes with --strike")
     gen_dataset(datapath=args.datapath, numframes=args.numframes, everything=args.all, seed=args.seed,

@@ -632,7 +632,18 @@ int spnet_fake_espi_params(long first_frame, int N, int H, int W, unsigned seed,
  *     ident = 1 + 7 g + j.  absent: the slot's eight floats are 0 (valid = 0: the rasteriser skips it) and ident = 0
  *   waves are the base row's; nnode = clamp(nnode0[s], 0, 7) in every frame
  * S == 0: nothing to do, success.  hipErrorInvalidValue (nothing launched): a NULL pointer, S < 0, first_sequence < 0, T
- * outside 1 .. 4096, J outside 0 .. 8, S * T > 2^31 - 1, 7 (first_sequence + S) > 2^31 - 2. */
+ * outside 1 .. 4096, J outside 0 .. 8, S * T > 2^31 - 1, 7 (first_sequence + S) > 2^31 - 2.
+ * ADDENDUM, the sequence's SOUND (host only: spnet_amd/fake_espi.py strike_audio_host; no kernel implements it, and no
+ * frame or label above depends on it).  hop = rate / fps samples per frame as an exact rational hop_num / hop_den; a
+ * sequence is floor(T * hop_num / hop_den) samples of int16.  Draws 4 and up of key(0, j) are free (0 .. 3 are the envelope):
+ *   pitch_j = 60 + 5 j + randint(u(key(0, j), 4), 0, 2) (MIDI: adjacent slots at least 3 semitones apart); f_j = 440 *
+ *     2^((pitch_j - 69) / 12) in double; step_j = round(f_j / rate * 2^32), the note step of "Note envelopes"
+ *   lag_j = 0 for the struck slot, the caller's lag (0 .. 64 frames) for a sympathetic one: the sound of a sympathetic note
+ *     follows its rings by lag frames
+ *   e_j(n) = the envelope above at frame floor(n * hop_den / hop_num) - lag_j (0 before the onset, so for a negative frame)
+ *   sample n = ((sum over VALID slots of R_j * e_j(n) * ctab[((((uint32)(n * step_j)) >> 20) + 3072) & 4095]) >> 18) +
+ *     randint(u(nkey, low32(n)), -noise, noise), nkey = u(key(0, 0), 5), noise 0 .. 1024; >> is an arithmetic shift.  Seven
+ *     slots at R = 255 and e = 256 give at most 7 * 255 * 256 * 16384 >> 18 = 28,560, with the noise below 32,767: no clipping */
 int spnet_fake_espi_strike(const float* waves0, const float* nodes0, const int* nnode0, long first_sequence, int S, int T,
                            unsigned seed, int J, float* waves, float* nodes, int* nnode, int* ident, void* stream);
 
@@ -1097,6 +1108,30 @@ int spnet_track_match(const double* rows_t, const int* count_t, const int* ident
 long spnet_track_ident_ws(int N, int Kt, int M);
 int spnet_track_ident(const double* rows_t, const int* count_t, const int* ident, const int* match, const int* track, int N,
                       int Kt, int Kp, int M, void* ws, int* ident_stats, void* stream);
+
+/* ---- Note envelopes (csrc/audio.hip, csrc/audio_core.h): how loud each pan note is in a strike's sound recording at the
+ *      instant of every video frame -- a bank of single-frequency DFTs ("Goertzel bank"), one per note.  spnet_amd/audio.py
+ *      is the host side and holds the same rule in numpy; DESIGN.md 5k -------------------------------------------------- */
+/* THE RULE.  pcm int16 [S][L]: S recordings, row stride L samples, the first len[s] of row s valid (len clamped to 0 .. L).
+ * Frame t = 0 .. T-1 has a window of Wn samples that starts at start(t) = offset + floor(t * hop_num / hop_den) -- hop =
+ * hop_num / hop_den samples per frame, an exact rational; offset may be negative.  Note k has the phase step step[k] =
+ * round(f_k / rate * 2^32), uint32.  For i = 0 .. Wn-1 and n = start(t) + i:
+ *   x  = pcm[s][n] if 0 <= n < len[s], else 0
+ *   p  = (uint32)(i * step[k]), wrapping;  q = p >> 20                     (a position in a table of 4096)
+ *   re[s][t][k] += x * win[i] * ctab[q]
+ *   im[s][t][k] += x * win[i] * ctab[(q + 3072) & 4095]
+ * win int16 [Wn] (the host's Hann table, 0 .. 32,767) and ctab int16 [4096] (round(16384 cos(2 pi i / 4096))) are INPUTS:
+ * the device, the host twin and the oracle read the same two tables, so no library cosine takes part in what is compared.
+ * A term is at most 2^15 * 2^15 * 2^15 = 2^45 in magnitude for any int16 content and there are at most 2^13: the int64 sums
+ * cannot overflow.  Integer sums: the result does not depend on the order of summation, on the grid, or on how S or T is
+ * split into calls (a later range of frames is the same call with offset advanced to its first start).
+ * Limits: S >= 0 (S == 0: nothing to do, success); T 1 .. 2^20; S * T * K <= 2^31 - 1; Wn 64 .. 8192; K 1 .. 64; L 1 ..
+ * 2^31 - 1; hop_num, hop_den 1 .. 2^31 - 1; |offset| <= 2^40.  Writes (not accumulates) every element of re and im, int64
+ * [S][T][K].  hipErrorInvalidValue, and nothing launched or written, for a NULL pointer, a size outside these limits, or an
+ * array not aligned to its element.  No value in pcm, len, win, step or ctab causes an access outside the arrays. */
+int spnet_note_envelopes(const int16_t* pcm, const int* len, int S, long L, int T, long offset, long hop_num, long hop_den,
+                         const int16_t* win, int Wn, const uint32_t* step, int K, const int16_t* ctab, long long* re,
+                         long long* im, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,8 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
                     batch_size=16, model=None, X_pred='', u8_frames=False, device_resize=False, device_png=False,
                     device_decode=False, device_overlay=False, device_png_lz=False, device_jpeg=False, jpeg_quality=90,
                     movie=None, movie_fps=5.0, movie_in=None, tracks=None, track_iou=0.25, track_gap=1, track_min_len=3,
-                    track_truth=None):
+                    track_truth=None, audio=None, notes=None, audio_fps=None, audio_offset=0, audio_window=2048, onset_frac=0.1,
+                    note_radius=40):
     img_file_list = []
     resize = False
     frames = None
@@ -31,6 +32,7 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
             raise ValueError("movie_in is for grayscale input (model_type 'big' / 'monolithic')")
         force_dim = None if cf.model_type == 'big' else 331
         reader = MjpegReader(movie_in)
+        audio_fps = reader.fps if audio_fps is None else audio_fps      # (additive) the sound is read on the movie's own clock
         total_load = int(len(reader) * fraction)
         if batch_size is not None:
             total_load = nearest_multiple(total_load, batch_size)
@@ -137,11 +139,27 @@ def predict_network(weights_file="spnet.model", datapath=default_image_dir, frac
             score = TK.track_score(*got, rows_t, rows, ident=ident, count_t=count_t)
             TK.write_track_score(TK.score_path(tracks), score, got[2])
             print(f"    Track score against {track_truth}: {score} -> {TK.score_path(tracks)}")
+        if audio is not None:
+            # (additive) the audio half: how loud every note of notes.csv is in the recording at the instant of each frame
+            # (computed on the GPU: the recording goes up once, [frames][notes] integers come back), an onset per note by
+            # the rule that gives a track's ring-count curve its onset, and the lag between the two per track
+            from spnet_amd import audio as AU
+            if notes is None or audio_fps is None:
+                raise ValueError("predict_network: audio needs notes (a notes.csv) and audio_fps (frames per second)")
+            pcm, rate = AU.read_wav(audio)
+            note_rows = AU.read_notes(notes)
+            env = AU.note_curves(pcm, rate, note_rows, len(names), audio_fps, offset=audio_offset, window=audio_window,
+                                 device=rows.device)
+            AU.write_envelopes(AU.envelopes_path(tracks), env, note_rows)
+            lag = AU.audio_lag(table, note_rows, env, float(audio_fps), frac=onset_frac, radius=note_radius)
+            AU.write_lag(AU.lag_path(tracks), lag)
+            print(f"    Audio: {len(note_rows)} notes in {audio} ({pcm.size} samples at {rate} Hz, {audio_fps} frames per "
+                  f"second), {sum(1 for r in lag if r[2] is not None)} with a track -> {AU.envelopes_path(tracks)}, "
+                  f"{AU.lag_path(tracks)}")
     return model
 
 
-if __name__ == '__main__':
-    np.random.seed(1)
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description="predicts ellipses for a directory of images",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('-w', '--weights', default="spnet.model", help='weights file (.hdf5) or whole-model file')
@@ -195,7 +213,34 @@ if __name__ == '__main__':
                    help="(additive, with --tracks) score the linked tracks against the ground-truth identities of a "
                         "truth_tracks.csv (gen_fake_espi.py --strike): frames joined by file name, or by index with "
                         "--movie_in; prints the score and writes it to PATH_score.csv and PATH_score_idents.csv")
-    args = p.parse_args()
+    p.add_argument('--audio', default=None, metavar='REC.wav',
+                   help="(additive, with --tracks and --notes) a PCM16 sound recording of the same strike (first channel): the "
+                        "envelope of every note at the instant of each frame, computed on the GPU, to PATH_envelopes.csv, and "
+                        "per note its track, the onsets of its ring-count curve and of its envelope and their lag to PATH_lag.csv")
+    p.add_argument('--notes', default=None, metavar='notes.csv',
+                   help="(with --audio) the notes: name, freq_hz and the position cx, cy of the note on the pan in frame pixels")
+    p.add_argument('--audio_fps', type=float, default=None,
+                   help="video frames per second, the clock that places the frames in the recording; required with -d, the "
+                        "movie's own rate with --movie_in")
+    p.add_argument('--audio_offset', type=int, default=0, metavar='SAMPLES',
+                   help="the sample of the recording at which frame 0 begins (may be negative)")
+    p.add_argument('--audio_window', type=int, default=2048,
+                   help="samples of the Hann window that starts at each frame's instant, 64 .. 8192: an onset is resolved no "
+                        "finer than this (a choice, not a measurement)")
+    p.add_argument('--onset_frac', type=float, default=0.1,
+                   help="an onset is the first frame at which a curve reaches this fraction of its maximum, for the envelopes "
+                        "and the ring counts alike (a choice, not a measurement)")
+    p.add_argument('--note_radius', type=float, default=40,
+                   help="a track belongs to the nearest note within this many pixels of its mean centre (a choice, not a "
+                        "measurement)")
+    args = p.parse_args(argv)
+    if args.audio is not None and (args.tracks is None or args.notes is None):
+        p.error("--audio compares a recording with the tracks of --tracks PATH.csv at the notes of --notes notes.csv: give all three")
+    if args.audio is not None and args.movie_in is None and args.audio_fps is None:
+        p.error("--audio with -d needs --audio_fps, the frames per second of the video")
+    if args.audio is not None and not (64 <= args.audio_window <= 8192 and 0 <= args.onset_frac <= 1 and args.note_radius >= 0
+                                       and (args.audio_fps is None or args.audio_fps > 0)):
+        p.error("--audio_window is 64 .. 8192, --onset_frac 0 .. 1, --note_radius at least 0 and --audio_fps above 0")
     if args.track_truth is not None and args.tracks is None:
         p.error("--track_truth scores the tracks of --tracks PATH.csv: give both")
     if args.device_jpeg and (args.device_png or args.device_png_lz):
@@ -204,6 +249,12 @@ if __name__ == '__main__':
         p.error("--jpeg_quality is 1 .. 100")
     if not 1 <= args.track_gap <= 8 or args.track_min_len < 1:
         p.error("--track_gap is 1 .. 8 and --track_min_len at least 1")
+    return args
+
+
+if __name__ == '__main__':
+    np.random.seed(1)
+    args = parse_args()
     for attr, val in (("model_type", args.model_type), ("loss_type", args.loss_type)):
         if val is not None:
             setattr(cf, attr, val)
@@ -213,4 +264,6 @@ if __name__ == '__main__':
                     device_png_lz=args.device_png_lz, device_jpeg=args.device_jpeg, jpeg_quality=args.jpeg_quality,
                     movie=args.movie, movie_fps=args.movie_fps, movie_in=args.movie_in, tracks=args.tracks,
                     track_iou=args.track_iou, track_gap=args.track_gap, track_min_len=args.track_min_len,
-                    track_truth=args.track_truth)
+                    track_truth=args.track_truth, audio=args.audio, notes=args.notes, audio_fps=args.audio_fps,
+                    audio_offset=args.audio_offset, audio_window=args.audio_window, onset_frac=args.onset_frac,
+                    note_radius=args.note_radius)

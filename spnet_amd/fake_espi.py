@@ -225,19 +225,14 @@ def strike_envelope(t, onset, rise, hold, decay):
     return np.where(t < onset, 0, e)
 
 
-def strike_params_host(waves0, nodes0, nnode0, T, seed=0, jitter=0, first_sequence=0):
-    """spnet_fake_espi_strike in numpy, bit for bit: base arrays waves0 [S,5], nodes0 [S,7,8], nnode0 [S] (frame-0
-    parameters, row s for the global sequence first_sequence + s) -> (waves float32 [S*T,5], nodes float32 [S*T,7,8], nnode
-    int32 [S*T], ident int32 [S*T,7]); frame s * T + t is time step t of sequence s."""
+def _strike_draws(nodes0, nnode0, T, seed, first_sequence):
+    """The per-slot draws of the strike rule for base rows nodes0 [S,7,8], nnode0 [S]: (g [S], skey [S], nn [S], valid [S,7],
+    is_struck [S,7], ek [S,7] = key(0, j), onset, rise, hold, decay, R [S,7]), int64 but for the uint64 keys.  One place
+    for the frames (strike_params_host) and the sound (strike_audio_host)."""
     from .augmentation import _keyed_draw, _mix32
-    waves0, nodes0 = np.asarray(waves0, np.float32), np.asarray(nodes0, np.float32)
-    S, T, J = int(nodes0.shape[0]), int(T), int(jitter)
-    _check_strike(S, T, J, int(first_sequence))
+    S = int(nodes0.shape[0])
     nn = np.clip(np.asarray(nnode0, np.int64), 0, 7)
     u64 = np.uint64
-
-    def randint(u, lo, hi):
-        return lo + ((u * u64(max(hi - lo + 1, 1))) >> u64(32)).astype(np.int64)
 
     g = np.arange(S, dtype=np.int64) + int(first_sequence)
     skey = _mix32(_mix32(_mix32(u64((int(seed) & 0xFFFFFFFF) ^ STRIKE_KEY)) + (g.astype(u64) & u64(0xFFFFFFFF)))
@@ -247,12 +242,31 @@ def strike_params_host(waves0, nodes0, nnode0, T, seed=0, jitter=0, first_sequen
     struck = np.where(valid.any(1), valid.argmax(1), 7)
     ek = _mix32(skey[:, None] + j.astype(u64)[None, :])                               # key(0, j)
     is_struck = j[None, :] == struck[:, None]
-    onset = np.where(is_struck, 0, randint(_keyed_draw(ek, 0), 0, T // 2))
-    rise = np.where(is_struck, 0, randint(_keyed_draw(ek, 1), 1, max(T // 4, 1)))
-    hold = randint(_keyed_draw(ek, 2), 0, T // 4)
-    decay = randint(_keyed_draw(ek, 3), 1, T)
+    onset = np.where(is_struck, 0, _randint(_keyed_draw(ek, 0), 0, T // 2))
+    rise = np.where(is_struck, 0, _randint(_keyed_draw(ek, 1), 1, max(T // 4, 1)))
+    hold = _randint(_keyed_draw(ek, 2), 0, T // 4)
+    decay = _randint(_keyed_draw(ek, 3), 1, T)
     with np.errstate(invalid="ignore"):
         R = np.where(nodes0[:, :, 5] == nodes0[:, :, 5], np.clip(nodes0[:, :, 5], 0, 255), 0).astype(np.int64)
+    return g, skey, nn, valid, is_struck, ek, onset, rise, hold, decay, R
+
+
+def _randint(u, lo, hi):
+    """randint of the counter stream (include/spnet_hip.h) on uint64 arrays holding uint32 draws."""
+    return lo + ((u * np.uint64(max(hi - lo + 1, 1))) >> np.uint64(32)).astype(np.int64)
+
+
+def strike_params_host(waves0, nodes0, nnode0, T, seed=0, jitter=0, first_sequence=0):
+    """spnet_fake_espi_strike in numpy, bit for bit: base arrays waves0 [S,5], nodes0 [S,7,8], nnode0 [S] (frame-0
+    parameters, row s for the global sequence first_sequence + s) -> (waves float32 [S*T,5], nodes float32 [S*T,7,8], nnode
+    int32 [S*T], ident int32 [S*T,7]); frame s * T + t is time step t of sequence s."""
+    from .augmentation import _keyed_draw, _mix32
+    waves0, nodes0 = np.asarray(waves0, np.float32), np.asarray(nodes0, np.float32)
+    S, T, J = int(nodes0.shape[0]), int(T), int(jitter)
+    _check_strike(S, T, J, int(first_sequence))
+    u64, randint = np.uint64, _randint
+    g, skey, nn, valid, _, _, onset, rise, hold, decay, R = _strike_draws(nodes0, nnode0, T, seed, first_sequence)
+    j = np.arange(7, dtype=np.int64)
     t = np.arange(T, dtype=np.int64)[None, :, None]
     env = strike_envelope(t, onset[:, None, :], rise[:, None, :], hold[:, None, :], decay[:, None, :])
     rings = np.where(valid[:, None, :], (R[:, None, :] * env + 128) >> 8, 0)         # [S,T,7]
@@ -270,6 +284,76 @@ def strike_params_host(waves0, nodes0, nnode0, T, seed=0, jitter=0, first_sequen
     waves = np.repeat(waves0[:, :5], T, axis=0)
     return (np.ascontiguousarray(waves), nodes.reshape(S * T, 7, 8), np.repeat(nn.astype(np.int32), T),
             ident.reshape(S * T, 7))
+
+
+STRIKE_AUDIO_SHIFT, STRIKE_AUDIO_MAX_LAG, STRIKE_AUDIO_MAX_NOISE, STRIKE_AUDIO_MIN_RATE = 18, 64, 1024, 16000
+TRUTH_AUDIO_FIELDS = ("ident", "name", "freq_hz", "video_onset", "audio_onset")
+_PITCH_NAMES = ("C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B")
+
+
+def strike_audio_host(nodes0, nnode0, T, seed=0, first_sequence=0, rate=48000, fps=200, lag=4, noise=8):
+    """The SOUND of strike sequences, the addendum of the strike rule (include/spnet_hip.h "Strike sequences"): host numpy,
+    integers after the note steps.  Every valid slot is a note whose pitch is drawn (draw 4 of its envelope key), whose
+    loudness follows the slot's own ring-count envelope `lag` frames late (the struck slot: at once), so that the truth a
+    lag analysis (spnet_amd/audio.py) has to recover is "a sympathetic note is audible `lag` frames after it is visible".
+    nodes0 [S,7,8], nnode0 [S]: the base rows strike_params_host evolves; the frames and labels do not depend on anything
+    here.  hop = rate / fps samples per frame (audio.hop_fraction).  -> (pcm int16 [S, floor(T hop)], info): info is a
+    dict of [S,7] arrays -- valid, struck (bool), pitch (MIDI), freq (Hz, float64), step (uint32), lag, onset, rise, hold,
+    decay, R (int64) -- and name, a list of 7 note names per sequence."""
+    from . import audio as AU
+    from .augmentation import _keyed_draw, _mix32
+    nodes0 = np.asarray(nodes0, np.float32)
+    S, T, lag, noise = int(nodes0.shape[0]), int(T), int(lag), int(noise)
+    _check_strike(S, T, 0, int(first_sequence))
+    if not (0 <= lag <= STRIKE_AUDIO_MAX_LAG and 0 <= noise <= STRIKE_AUDIO_MAX_NOISE and rate == int(rate)
+            and int(rate) >= STRIKE_AUDIO_MIN_RATE):
+        raise ValueError("strike audio: lag 0 .. %d frames, noise 0 .. %d, a whole sample rate of at least %d; got lag %r, "
+                         "noise %r, rate %r" % (STRIKE_AUDIO_MAX_LAG, STRIKE_AUDIO_MAX_NOISE, STRIKE_AUDIO_MIN_RATE, lag, noise, rate))
+    num, den = AU.hop_fraction(int(rate), fps)
+    u64, M32 = np.uint64, np.uint64(0xFFFFFFFF)
+    _, _, _, valid, is_struck, ek, onset, rise, hold, decay, R = _strike_draws(nodes0, nnode0, T, seed, first_sequence)
+    pitch = 60 + 5 * np.arange(7, dtype=np.int64)[None, :] + _randint(_keyed_draw(ek, 4), 0, 2)
+    freq = 440.0 * 2.0 ** ((pitch - 69).astype(np.float64) / 12.0)
+    step = AU.note_steps(freq.reshape(-1), int(rate)).reshape(S, 7)
+    lag_j = np.where(is_struck, 0, lag).astype(np.int64)
+    Ls = (T * num) // den
+    n = np.arange(Ls, dtype=np.int64)
+    frame = (n * den) // num
+    ctab = AU.cos_table().astype(np.int64)
+    pcm = np.zeros((S, Ls), np.int16)
+    for s in range(S):
+        acc = np.zeros(Ls, np.int64)
+        for j in np.flatnonzero(valid[s]):
+            e = strike_envelope(frame - lag_j[s, j], onset[s, j], rise[s, j], hold[s, j], decay[s, j])
+            q = ((n.astype(u64) * u64(step[s, j])) & M32) >> u64(AU.TAB_SHIFT)
+            acc += R[s, j] * e * ctab[(q.astype(np.int64) + 3072) & (AU.TAB - 1)]
+        nkey = _keyed_draw(ek[s, 0], 5)
+        draw = _mix32(nkey ^ ((n.astype(u64) & M32) * u64(0x85ebca6b) + u64(0xc2b2ae35) & M32))     # u(nkey, low32(n))
+        pcm[s] = np.clip((acc >> STRIKE_AUDIO_SHIFT) + _randint(draw, -noise, noise), -32768, 32767)
+    names = [["%s%d" % (_PITCH_NAMES[p % 12], p // 12 - 1) for p in row] for row in pitch.tolist()]
+    info = {"valid": valid, "struck": is_struck & valid, "pitch": pitch, "freq": freq, "step": step, "lag": lag_j, "onset": onset,
+            "rise": rise, "hold": hold, "decay": decay, "R": R, "name": names}
+    return pcm, info
+
+
+def strike_audio_truth(info, s, T, first_sequence=0, frac=None):
+    """What a lag analysis of sequence s (row s of info, the global sequence first_sequence + s) should find: one record
+    (ident, name, freq_hz, video_onset, audio_onset) per valid slot whose ring count ever reaches 1.  video_onset =
+    audio.onset_frame of the truth ring curve (R e(t) + 128) >> 8, audio_onset = onset_frame of the loudness the sound was
+    synthesised with, R e(t - lag), both on the frame grid, at frac (default audio.DEFAULT_ONSET_FRAC)."""
+    from . import audio as AU
+    frac = AU.DEFAULT_ONSET_FRAC if frac is None else frac
+    t = np.arange(int(T), dtype=np.int64)
+    out = []
+    for j in np.flatnonzero(info["valid"][s]):
+        args = tuple(info[k][s, j] for k in ("onset", "rise", "hold", "decay"))
+        rings = (info["R"][s, j] * strike_envelope(t, *args) + 128) >> 8
+        if not (rings >= 1).any():
+            continue
+        loud = info["R"][s, j] * strike_envelope(t - info["lag"][s, j], *args)
+        out.append((1 + 7 * (int(first_sequence) + s) + int(j), info["name"][s][j], float(info["freq"][s, j]),
+                    AU.onset_frame(rings, frac), AU.onset_frame(loud, frac)))
+    return out
 
 
 def strike_params_device(S, T, seed=0, jitter=0, first_sequence=0, count_range=(1, 7), device="cuda:0"):
